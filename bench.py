@@ -15,10 +15,15 @@ under torchrun (RANK set) it is a worker.  Workers shard the points and exchange
 torch.distributed is used for the rendezvous of the ncclUniqueId, the barriers and the max-over-ranks of the time.
 --scaling weak (default): every rank owns a full per-GPU grid.  --scaling strong: BASELINE's global size is split over ranks.
 
-Prints ONE JSON line on rank 0 (contract in the task description) with two extra objects:
+Prints ONE JSON line on rank 0 (contract in the task description).  A plain run sets up, warms up, times ONE block of exactly
+--steps steps and prints the headline figure (value, ms_per_step).  --full adds what the headline does not need:
+  timing        -- the K-step block repeated (default 50, >= 3 s of GPU time), median block reported with min and max
   roofline      -- dominant kernel (jet reverse pass) algorithmic FLOP / HIP-event time vs the fp32 MFMA peak
+  split_bf16_mode, parity_check -- a second timed pass on the split-bf16 kernels; the in-run check against the fp64 oracle
   cpu_baseline  -- the reference's op sequence (torch-autograd restatement, oracle/torch_ref.py) and the native C++/OpenMP
                    jet restatement (oracle/cpu_ref) timed on this host
+--dump-outputs DIR writes what the last timed step computed (DIR/params.npy, grad.npy, scalars.npy) for output-for-output
+comparison of two builds; the inputs (seeded weights, grid points) are the same in every run with the same arguments.
 """
 import argparse
 import json
@@ -348,6 +353,17 @@ def dp_crosscheck(eng, flat, lr=1e-3):
     return ok, {"grad_rel": gerr, "loss_rel": lerr, "mu_rel": merr}
 
 
+def dump_outputs(eng, out_dir):
+    """What a caller of the timed path holds after its last step: the parameters after the Adam update (float32), that step's
+    gradient (float32) and its scalars (float64, in the order of Engine.HISTORY_FIELDS: loss, pde, bc, ..., mu, ...)."""
+    os.makedirs(out_dir, exist_ok=True)
+    sc = eng.read_scalars()
+    arrays = {"params": eng.get_params(), "grad": eng.get_grad(),
+              "scalars": np.array([sc[k] for k in eng.HISTORY_FIELDS], dtype=np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -357,11 +373,17 @@ def main():
     ap.add_argument("--scaling", default=None, choices=["weak", "strong"],
                     help="default: weak (every rank a full per-GPU grid); cfg3 / cfg4 / cfg5 at --gpus 8 default to strong, i.e. to "
                          "BASELINE's global sizes")
-    ap.add_argument("--blocks", type=int, default=50,
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: repeated timed blocks, per-kernel events and "
+                         "the roofline, the split-bf16 pass, the in-run oracle parity check, the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (parameters, gradient, scalars)")
+    ap.add_argument("--blocks", type=int, default=None,
                     help="the timed K-step block is repeated this many times (each bracketed by barrier + synchronize); the line "
-                         "reports the median block, min and max.  Shortened automatically when 50 blocks would exceed ~20 s")
+                         "reports the median block, min and max.  Default 1, with --full 50; shortened automatically when the "
+                         "blocks would exceed ~20 s")
     ap.add_argument("--launch-timeout", type=float, default=1500.0, help="launcher (--gpus N): overall limit in seconds")
-    ap.add_argument("--no-parity-check", action="store_true")
+    ap.add_argument("--no-parity-check", action="store_true", help="--full: skip the in-run oracle check")
     ap.add_argument("--parity-points", type=int, default=0,
                     help="points of the in-run oracle check; 0 = the whole timed batch when the oracle fits --parity-budget, else a slice")
     ap.add_argument("--parity-budget", type=float, default=90.0, help="seconds of host time the in-run oracle check may take")
@@ -369,9 +391,11 @@ def main():
                     help="N > 1: all-reduces issued by the engine (native RCCL) or by torch.distributed between the phases")
     ap.add_argument("--async-grad", action="store_true",
                     help="OPT-IN one-step-stale gradient: the gradient all-reduce overlaps the next forward (changes the trajectory; labelled)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-alt-mode", action="store_true", help="skip the second timed pass on the split-bf16 kernels (H <= 64 workloads)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-alt-mode", action="store_true", help="--full: skip the second timed pass on the split-bf16 kernels (H <= 64 workloads)")
     args = ap.parse_args()
+    if args.blocks is None:
+        args.blocks = 50 if args.full else 1
 
     if args.scaling is None:
         big = args.workload in ("cfg3_2d_5x128", "cfg4_2d_6x128_rot", "cfg5_3d_6x256")
@@ -464,7 +488,8 @@ def main():
     coll0 = eng.comm_info()["collectives"] if native else 0          # (the cross-check above issued some)
     run_steps(args.warmup)
     eng.synchronize()
-    eng.profile_enable(True)           # HIP events around the two dominant kernels, on the engine's stream, over the timed region
+    if args.full:
+        eng.profile_enable(True)       # HIP events around the two dominant kernels, on the engine's stream, over the timed region
 
     def timed_block():
         """EXACTLY args.steps steps between barrier + synchronize on both sides; the maximum over the ranks."""
@@ -484,20 +509,47 @@ def main():
         return el
 
     # One K-step block is a few tens of milliseconds -- a single scheduling hiccup moves it by per cent and an outside observer
-    # never sees the GPU busy.  The block is therefore repeated (>= 3 s of GPU time for the default workload) and the line reports
-    # the MEDIAN block next to min and max; every block is a contract-conforming measurement of exactly K steps.
+    # never sees the GPU busy.  With --full the block is therefore repeated (>= 3 s of GPU time for the default workload) and the
+    # line reports the MEDIAN block next to min and max; every block is a contract-conforming measurement of exactly K steps.
     block_s = [timed_block()]
     n_blocks = max(1, min(args.blocks, max(5, int(20.0 / max(block_s[0], 1e-6)))))
     for _ in range(n_blocks - 1):
         block_s.append(timed_block())
     elapsed = float(np.median(block_s))
-    prof = eng.profile_read()
-    eng.profile_enable(False)
+    if args.full:
+        prof = eng.profile_read()
+        eng.profile_enable(False)
     sc = eng.read_scalars()
     comm = eng.comm_info()
     steps_from_init = args.warmup + args.steps * len(block_s)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(eng, args.dump_outputs)
 
     if rank == 0:
+        pts = n_local * world * args.steps
+        value = pts / elapsed
+        out = {
+            "metric": "collocation-point residual evals/sec (full training step: jets fwd + residual + reverse + Adam)",
+            "value": value, "unit": "points/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": args.scaling,
+            "timing": {"blocks": len(block_s), "steps_per_block": args.steps, "statistic": "median block (value, ms_per_step)",
+                       "ms_per_step_min": min(block_s) / args.steps * 1e3, "ms_per_step_max": max(block_s) / args.steps * 1e3,
+                       "ms_per_step_first_block": block_s[0] / args.steps * 1e3, "timed_seconds": float(sum(block_s))},
+            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": args.workload, "layers": layers, "points_per_gpu": n_local,
+                       "global_points": n_local * world, "gamma": wl["gamma"], "boundary_points": int(xb.shape[0]),
+                       "parallelism": f"dp{world}", "kernel_path": "fused_mfma_f32_16x16x4" if fused else "generic_layerwise_mfma",
+                       "exchange": (("engine_rccl_stale1" if args.async_grad else "engine_rccl") if native else "torch_distributed") if use_dist else "none"},
+            "per_gpu_points_per_s": value / world,
+            "rccl_ranks": comm["world"] if native else (world if use_dist else 0),
+            "collectives_per_step": ((comm["collectives"] - coll0) / max(1, steps_from_init)) if native else (2 if use_dist else 0),
+            "exchange_crosscheck": xcheck,
+            "trajectory": {"steps_from_seeded_init": steps_from_init, "loss": sc["loss"], "mu": sc["mu"],
+                           "note": "state after the warm-up and timed steps from a random init -- NOT a converged eigenvalue; the "
+                                   "converged accuracy is mu_abs_err (tools/accuracy_nd.py), the correctness of the kernels parity_check "
+                                   "(both with --full)"},
+        }
+    if rank == 0 and args.full:
         flops_pt, bmat_pt = eng.step_cost()
         f_fwd = flops_pt / 3.0
         # channels the training batches carry: value, d first derivatives, ONE Laplacian channel (SURVEY 8(d) counts 1 + 2d;
@@ -506,8 +558,6 @@ def main():
         chan = d_in + 2
         gemm_fwd = 2.0 * d_in * Hh + chan * (2.0 * Hh * Hh * (Lh - 1) + 2.0 * Hh * layers[-1])
         survey_fwd = 2.0 * d_in * Hh + (1 + 2 * d_in) * (2.0 * Hh * Hh * (Lh - 1) + 2.0 * Hh * layers[-1]) + Hh * Lh * (3 + 5 * d_in)
-        pts = n_local * world * args.steps
-        value = pts / elapsed
         n_rows = n_local + (int(xb.shape[0]) if xb.shape[0] * 8 <= n_local else 0)     # merged boundary rows ride in the launch
         bwd_s = prof["bwd_ms"] / max(1, prof["bwd_launches"]) * 1e-3
         fwd_s = prof["fwd_ms"] / max(1, prof["fwd_launches"]) * 1e-3
@@ -536,25 +586,7 @@ def main():
         if uj:
             util = dict(uj, source=f"from_profile: {usrc}" + (f" -- STALE: recorded on the {ustale} build" if ustale else ""))
         aj, asrc, astale = load_profile_json(f"accuracy_{args.workload}.json")
-        out = {
-            "metric": "collocation-point residual evals/sec (full training step: jets fwd + residual + reverse + Adam)",
-            "value": value, "unit": "points/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": args.scaling,
-            "timing": {"blocks": len(block_s), "steps_per_block": args.steps, "statistic": "median block (value, ms_per_step)",
-                       "ms_per_step_min": min(block_s) / args.steps * 1e3, "ms_per_step_max": max(block_s) / args.steps * 1e3,
-                       "ms_per_step_first_block": block_s[0] / args.steps * 1e3, "timed_seconds": float(sum(block_s))},
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": args.workload, "layers": layers, "points_per_gpu": n_local,
-                       "global_points": n_local * world, "gamma": wl["gamma"], "boundary_points": int(xb.shape[0]),
-                       "parallelism": f"dp{world}", "kernel_path": "fused_mfma_f32_16x16x4" if fused else "generic_layerwise_mfma",
-                       "exchange": (("engine_rccl_stale1" if args.async_grad else "engine_rccl") if native else "torch_distributed") if use_dist else "none"},
-            "per_gpu_points_per_s": value / world,
-            "rccl_ranks": comm["world"] if native else (world if use_dist else 0),
-            "collectives_per_step": ((comm["collectives"] - coll0) / max(1, steps_from_init)) if native else (2 if use_dist else 0),
-            "exchange_crosscheck": xcheck,
-            "trajectory": {"steps_from_seeded_init": steps_from_init, "loss": sc["loss"], "mu": sc["mu"],
-                           "note": "state after the warm-up and timed steps from a random init -- NOT a converged eigenvalue; the "
-                                   "converged accuracy is mu_abs_err (tools/accuracy_nd.py), the correctness of the kernels parity_check"},
+        out.update({
             "mu_abs_err": (aj or {}).get("mu_abs_err"), "mu_ref": (aj or {}).get("mu_ref"),
             "mu_abs_err_source": f"from_profile: {asrc} (converged run of tools/accuracy_nd.py vs oracle/gp_ground_state_nd.py)" if aj else None,
             "mu_abs_err_round": (f"{astale} (stale: a converged run of the previous round's build)" if astale else PROFILE_ROUND) if aj else None,
@@ -573,7 +605,7 @@ def main():
             "jet_channels": chan, "survey_8d_step_flop_per_point": 3.0 * survey_fwd,
             "step_flop_per_point": flops_pt, "whole_step_tflops": flops_pt * value / world / 1e12,
             "b_mat_bytes_per_point": bmat_pt, "b_mat_gbps": bmat_pt * value / world / 1e9,
-        }
+        })
         if not fused:       # layer-wise generic set (MFMA maps for wide layers): no per-kernel events, the whole step is rated
             tf = flops_pt * value / world / 1e12
             out["roofline"] = {"bound": "mfma", "kernel": "generic layer-wise set (%s, %s + head/activation kernels), whole step" % (kernels["fwd"], kernels["bwd"]),
@@ -600,6 +632,7 @@ def main():
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(wl, flat)
             out["cpu_baseline_native"] = cpu_baseline_native(wl, flat)
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if use_dist:
         dist.barrier()

@@ -140,7 +140,7 @@ def test_bench_native_exchange_path_world_1():
 @pytest.mark.gpu
 def test_bench_line_contract():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "cfg2_1d_4x64", "--steps", "3", "--warmup", "1",
-                          "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                          "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]
     d = json.loads(line)
@@ -162,3 +162,33 @@ def test_bench_line_contract():
     # ... taken on the batch AS TIMED, through the kernels that were timed (not on a slice with another launch configuration)
     assert pc["points"] == d["config"]["points_per_gpu"] and pc["same_kernels_as_timed"] is True, pc
     assert "mu_after_timed_steps" not in d and "trajectory" in d
+
+
+@pytest.mark.gpu
+def test_plain_bench_line_times_exactly_the_steps_and_dumps_outputs(tmp_path):
+    """A plain run (no --full) times one block of exactly --steps steps and carries the headline keys only; --dump-outputs writes the
+    state after the last timed step, and two runs with the same arguments give the same outputs."""
+    import gpe_pinn
+    dumps = []
+    for run in ("a", "b"):
+        d_out = tmp_path / run
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "cfg2_1d_4x64", "--steps", "7", "--warmup", "2",
+                              "--dump-outputs", str(d_out)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in d, k
+        assert d["steps"] == 7 and d["warmup"] == 2 and d["timing"]["blocks"] == 1 and d["trajectory"]["steps_from_seeded_init"] == 9
+        assert abs(d["value"] * d["ms_per_step"] * 1e-3 / d["config"]["points_per_gpu"] - 1.0) < 1e-6
+        for k in ("roofline", "roofline_forward", "split_bf16_mode", "parity_check", "cpu_baseline", "cpu_baseline_native", "mu_abs_err"):
+            assert k not in d, k
+        arrs = {n: np.load(d_out / f"{n}.npy") for n in ("params", "grad", "scalars")}
+        P = sum(a * b + b for a, b in zip(d["config"]["layers"][:-1], d["config"]["layers"][1:]))
+        assert arrs["params"].dtype == np.float32 and arrs["params"].shape == (P,) and arrs["grad"].dtype == np.float32
+        assert arrs["grad"].shape == (P,) and arrs["scalars"].dtype == np.float64
+        assert all(np.isfinite(a).all() for a in arrs.values()) and sum(a.nbytes for a in arrs.values()) <= 64 << 20
+        sc = dict(zip(gpe_pinn.Engine.HISTORY_FIELDS, arrs["scalars"]))
+        assert sc["step"] == 9 and sc["loss"] == d["trajectory"]["loss"]          # warm-up + timed steps, nothing more
+        dumps.append(arrs)
+    for n in ("params", "grad", "scalars"):
+        np.testing.assert_allclose(dumps[1][n], dumps[0][n], rtol=1e-5, atol=1e-7, err_msg=n)

@@ -1,11 +1,12 @@
 #!/bin/bash
 # usage: tools/bench_env.sh <tag> "ENV1=a ENV2=b" "ENV1=c" ...   -- bench.py under each environment setting; print a table
 tag=$1; shift
+out=${OUT:-bench_out}; mkdir -p $out
 i=0
 for envs in "$@"; do
   i=$((i+1))
-  env $envs python bench.py --steps 10 --warmup 3 --no-cpu-baseline > gpurun_out/bench_${tag}_${i}.json 2>> gpurun_out/bench_${tag}.err
-  python - "gpurun_out/bench_${tag}_${i}.json" "$envs" <<'PY'
+  env $envs python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline > $out/bench_${tag}_${i}.json 2>> $out/bench_${tag}.err
+  python - "$out/bench_${tag}_${i}.json" "$envs" <<'PY'
 import json,sys
 try:
     d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -1,5 +1,5 @@
 import cProfile, pstats, sys, os, time
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 import gpe_pinn
 from gpe_pinn import refine
