@@ -704,10 +704,14 @@ static size_t fused_fwd_lds(gpe_engine* e, bool staged) { return fused_small_byt
 
 static bool coop_shape(gpe_engine* e);
 static unsigned fused_grid(gpe_engine* e, int64_t n, int waves_per_block, int blocks_per_cu);
+// residual blocks on the fused path: only the cooperative kernels (<..., RES>) implement the skip connection -- they run whatever
+// GPE_COOP says (the per-wave-tile kernels would evaluate a plain MLP)
+static bool coop_only(gpe_engine* e) { return coop_shape(e) && e->H <= 64 && e->cfg.net_kind == GPE_NET_RESIDUAL; }
 static bool fwd_coop(gpe_engine* e, const Batch& b) {
+    if (coop_only(e)) return true;
     if (!coop_shape(e) || e->coop == 0) return false;
     if (e->H == 128) return e->coop_fwd128;           // wide layers: the cooperative forward wins at every size (measured)
-    if (e->nd.n_lin - 2 > 3 || e->cfg.net_kind == GPE_NET_RESIDUAL) return true;    // four / five maps at H <= 64, residual blocks: only the cooperative kernels take them
+    if (e->nd.n_lin - 2 > 3) return true;             // four / five maps at H <= 64: the cooperative kernels take them whenever allowed
     return (b.n + 15) / 16 <= e->coop_fwd_max_tiles;
 }
 #define HEAD_SLOTS 512
@@ -871,7 +875,8 @@ static bool seed_in_reverse(gpe_engine* e) {
 // tiles, -4 % at 1 024; profiles/r04/wide_small_batch_ab.txt).  The per-map form from wide_min_tiles tiles on (GPE_WIDE_MIN_TILES).
 static bool wide_reverse(gpe_engine* e, const Batch& b);
 static int bwd_kind(gpe_engine* e, const Batch& b) {
-    if (coop_shape(e) && e->coop != 0 && (e->coop == 1 || (b.n + 15) / 16 <= e->coop_max_tiles || (e->H <= 64 && (e->nd.n_lin - 2 > 3 || e->cfg.net_kind == GPE_NET_RESIDUAL)))) return 3;
+    if (coop_only(e)) return 3;
+    if (coop_shape(e) && e->coop != 0 && (e->coop == 1 || (b.n + 15) / 16 <= e->coop_max_tiles || (e->H <= 64 && e->nd.n_lin - 2 > 3))) return 3;
     if (e->H > 64 || !staged_batch(e, b)) return 0;
     return e->bwd_racc ? 2 : 0;
 }
@@ -909,11 +914,16 @@ static void set_pipe_lds(int bytes) {
         }
     }
 }
+// GPE_BWD_B6: the cooperative reverse kernel with its adjoint products on the bf16 pipe exists for plain MLPs of one to three maps at
+// H <= 64; residual blocks and four / five maps keep the fp32 f_backward_coop
+static bool coop_b6(const gpe_engine* e) {
+    return e->bwd_b6 && e->H <= 64 && e->nd.n_lin - 2 <= 3 && e->cfg.net_kind == GPE_NET_MLP;
+}
 template <int HH, int CC, int EE, int NO>
 static void launch_coop_no(gpe_engine* e, Batch& b, unsigned grid, size_t lds) {
 #define CARGS e->nd, e->theta, e->WpkT, b.pts, b.stored, b.Ob, e->gslab, b.n, b.ld, e->Ppad
     if constexpr (HH <= 64) {
-        if (e->bwd_b6 && e->nd.n_lin - 2 <= 3 && e->cfg.net_kind == GPE_NET_MLP) {
+        if (coop_b6(e)) {
             switch (e->nd.n_lin - 2) {
                 case 1: hipLaunchKernelGGL((f_backward_coop<HH, CC, EE, NO, 1, true>), dim3(grid), dim3(HH * 4), lds, e->stream, CARGS); break;
                 case 2: hipLaunchKernelGGL((f_backward_coop<HH, CC, EE, NO, 2, true>), dim3(grid), dim3(HH * 4), lds, e->stream, CARGS); break;
@@ -1394,7 +1404,7 @@ int gpe_active_kernels(gpe_engine* e, char* buf, size_t n) {
         if (kind == 3 && use_pipe(e, b.C)) snprintf(r, sizeof r, "f_backward_pipe<%d,%d,%d,%d,%d%s>", e->H, b.C, b.E, e->nd.n_out, maps,
                                                     seed_in_reverse(e) ? ",seeds" : "");
         else if (kind == 3) snprintf(r, sizeof r, "f_backward_coop<%d,%d,%d,%d,%d%s>", e->H, b.C, b.E, e->nd.n_out, maps > 5 ? 5 : maps,
-                                (e->bwd_b6 && e->H <= 64) ? ",b6" : "");
+                                coop_b6(e) ? ",b6" : "");
         else if (kind == 2) snprintf(r, sizeof r, "f_backward<%d,%d,%d,%d,wlds,racc%d>", e->H, b.C, b.E, e->nd.n_out, maps > 3 ? 3 : maps);
         else snprintf(r, sizeof r, "f_backward<%d,%d,%d,%d,l2,%s>", e->H, b.C, b.E, e->nd.n_out, e->H > 64 ? "gacc" : "ldsacc");
         // (whole steps, gpe_step / gpe_run: the split-phase protocol of the data-parallel driver keeps k_head_pde)
@@ -1557,6 +1567,13 @@ int gpe_create(const gpe_config* cfg, int device, void* hip_stream, gpe_engine**
         CFAIL("fused path needs >=2 hidden layers of one width: 32 or 64 (P*4 <= 160KB LDS), 128 or 256");
     e->path = (c.path == GPE_PATH_GENERIC || !fused_ok) ? GPE_PATH_GENERIC : GPE_PATH_FUSED;
     e->H = H;
+    if (e->path == GPE_PATH_FUSED) {
+        // f_forward is compiled for GPE_FWD_WAVES resident workgroups per CU (__launch_bounds__): more cannot be honoured by this build
+        const char* envfw = getenv("GPE_FWD_WG_PER_CU");
+        if (envfw && (atoi(envfw) < 1 || atoi(envfw) > GPE_FWD_WAVES))
+            CFAIL("GPE_FWD_WG_PER_CU=%s: this build runs f_forward at 1..%d workgroups per CU (more need a build with -DGPE_FWD_WAVES raised to match)",
+                  envfw, GPE_FWD_WAVES);
+    }
 #undef CFAIL
     e->device = device;
     e->stream = (hipStream_t)hip_stream;
@@ -1635,7 +1652,7 @@ int gpe_create(const gpe_config* cfg, int device, void* hip_stream, gpe_engine**
             const char* envw = getenv("GPE_COOP_WG_PER_CU");
             if (envw && atoi(envw) >= 1 && atoi(envw) <= 2) e->coop_wg_per_cu = atoi(envw);
             const char* envfw = getenv("GPE_FWD_WG_PER_CU");
-            if (envfw && atoi(envfw) >= 1 && atoi(envfw) <= 4) e->fwd_wg_per_cu = atoi(envfw);
+            if (envfw) e->fwd_wg_per_cu = atoi(envfw);                 // (range checked above, before any allocation)
             const char* envc = getenv("GPE_COOP");
             e->coop = envc ? atoi(envc) : 1;          // measured: faster than the per-wave-tile kernels at every batch size
             const char* envm = getenv("GPE_COOP_MAX_TILES");
