@@ -59,6 +59,15 @@ class gpe_scalars(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class gpe_observables(C.Structure):
+    """include/gpe_hip.h: struct gpe_observables -- energy parts, chemical potential, <L_z>, moments of the normalised state."""
+    _fields_ = [(n, C.c_double) for n in ("n", "dv", "step", "norm", "kin", "pot", "inter", "rot", "energy", "mu", "mu_lap", "lz")] + \
+               [("mean_x", C.c_double * 3), ("var_x", C.c_double * 3), ("peak_density", C.c_double), ("res_rms", C.c_double)]
+
+    def as_dict(self):
+        return {n: (list(getattr(self, n)) if n in ("mean_x", "var_x") else getattr(self, n)) for n, _ in self._fields_}
+
+
 _vp, _i64, _int, _f = C.c_void_p, C.c_int64, C.c_int, C.c_float
 _P = C.POINTER
 
@@ -67,6 +76,7 @@ SYMBOLS = {
     "gpe_abi_version": (_int, []),
     "gpe_sizeof_config": (C.c_size_t, []),
     "gpe_sizeof_scalars": (C.c_size_t, []),
+    "gpe_sizeof_observables": (C.c_size_t, []),
     "gpe_exchange_dbl_count": (_i64, []),
     "gpe_use_external_exchange": (_int, [_vp, _vp, _i64, _vp, _i64]),
     "gpe_create": (_int, [_P(gpe_config), _int, _vp, _P(_vp)]),
@@ -96,6 +106,9 @@ SYMBOLS = {
     "gpe_forward_jets": (_int, [_vp, _vp, _i64, _vp]),
     "gpe_residual": (_int, [_vp, _P(gpe_scalars), _vp, _vp]),
     "gpe_eval_density": (_int, [_vp, _vp, _i64, _f, _int, _vp, _vp]),
+    "gpe_observables": (_int, [_vp, _vp, _i64, _vp, _f, _P(gpe_observables)]),
+    "gpe_bind_monitor": (_int, [_vp, _vp, _i64, _vp, _f, _i64, C.c_int32]),
+    "gpe_read_monitor": (_int, [_vp, _i64, _i64, _P(gpe_observables), _P(_i64)]),
     "gpe_step_begin": (_int, [_vp]),
     "gpe_step_backward": (_int, [_vp]),
     "gpe_step_update": (_int, [_vp]),
@@ -151,7 +164,8 @@ def load():
         fn.argtypes = args
     if lib.gpe_abi_version() != GPE_ABI_VERSION:
         raise ImportError(f"{path}: ABI version {lib.gpe_abi_version()} != {GPE_ABI_VERSION}")
-    if lib.gpe_sizeof_config() != C.sizeof(gpe_config) or lib.gpe_sizeof_scalars() != C.sizeof(gpe_scalars):
+    if lib.gpe_sizeof_config() != C.sizeof(gpe_config) or lib.gpe_sizeof_scalars() != C.sizeof(gpe_scalars) or \
+            lib.gpe_sizeof_observables() != C.sizeof(gpe_observables):
         raise ImportError(f"{path}: struct layout mismatch between include/gpe_hip.h and _capi.py")
     _lib = lib
     return lib

@@ -30,6 +30,7 @@ typedef enum { ncclFloat = 7, ncclDouble = 8 } ncclDataType_t;
 
 #include "gpe_common.h"
 #include "gpe_head.h"
+#include "gpe_observe.h"
 #include "gpe_generic.h"
 #include "gpe_fused.h"
 #include "gpe_wide_api.h"
@@ -586,6 +587,17 @@ struct gpe_engine {
     bool dp_bucket = false;                           // set by gpe_step_dp: the generic reverse pass hands finished layers to the comm stream
     int64_t dp_collectives = 0;                       // all-reduces issued since gpe_comm_init (bench / tests)
     bool dp_inline = true;                            // synchronous step on the fused / wide sets: collectives on the compute stream (GPE_DP_INLINE=0: exchange stream)
+    // ---- observables (gpe_observe.h) ----
+    double* obs_buf = nullptr;                        // [pass-1 slab | pass-2 slab | raw totals], allocated on first use
+    struct gpe_observables* obs_out = nullptr;        // staging slot of gpe_observables
+    // held-out monitor (gpe_bind_monitor): its own forward batch, sized at the bind -- gpe_run must neither allocate nor synchronise
+    Batch mon;
+    const float* mon_x = nullptr; const float* mon_V = nullptr;
+    float mon_dv = 0.f;
+    int64_t mon_n = 0, mon_every = 0;                 // every == 0: no monitor
+    int64_t mon_steps = 0, mon_records = 0;           // steps enqueued / records appended since the bind
+    int mon_cap = 0;
+    struct gpe_observables* mon_ring = nullptr;       // [mon_cap]
     int phase = 0;                 // 0 idle, 1 after begin, 2 after backward
     std::string err;
     double* sums() { return dbl; }
@@ -1364,6 +1376,7 @@ extern "C" {
 int gpe_abi_version(void) { return GPE_ABI_VERSION; }
 size_t gpe_sizeof_config(void) { return sizeof(gpe_config); }
 size_t gpe_sizeof_scalars(void) { return sizeof(gpe_scalars); }
+size_t gpe_sizeof_observables(void) { return sizeof(struct gpe_observables); }
 int64_t gpe_exchange_dbl_count(void) { return S_COUNT + LS_COUNT + 4; }
 
 int gpe_use_external_exchange(gpe_engine* e, void* d_dbl, int64_t n_dbl, void* d_grad, int64_t n_grad) {
@@ -1782,10 +1795,10 @@ void gpe_destroy(gpe_engine* e) {
     if (e->cap_stream) (void)hipStreamDestroy(e->cap_stream);
     if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
     if (e->ev_join) (void)hipEventDestroy(e->ev_join);
-    free_batch(e->main); free_batch(e->bc); free_batch(e->sym); free_batch(e->aux); free_batch(e->mse);
+    free_batch(e->main); free_batch(e->bc); free_batch(e->sym); free_batch(e->aux); free_batch(e->mse); free_batch(e->mon);
     for (hipEvent_t ev : e->ev_pool) (void)hipEventDestroy(ev);
     if (e->ext_exchange) { e->grad = nullptr; e->dbl = nullptr; }
-    void* ps[] = {e->theta, e->am, e->av, e->grad, e->dbl, e->od, e->hist, e->last, (void*)e->orth_dev, e->Wpk, e->WpkT, e->gslab, e->gslab_bc, e->grad_bc, (void*)e->upd_snap, (void*)e->head_slots, (void*)e->upd_ticket, (void*)e->upd_snap_small};
+    void* ps[] = {e->theta, e->am, e->av, e->grad, e->dbl, e->od, e->hist, e->last, (void*)e->orth_dev, e->Wpk, e->WpkT, e->gslab, e->gslab_bc, e->grad_bc, (void*)e->upd_snap, (void*)e->head_slots, (void*)e->upd_ticket, (void*)e->upd_snap_small, (void*)e->obs_buf, (void*)e->obs_out, (void*)e->mon_ring};
     for (void* p : ps) if (p) (void)hipFree(p);
     delete e;
 }
@@ -1875,6 +1888,12 @@ int gpe_reset_optimizer(gpe_engine* e, float lr) {
 }
 
 // (re)build the collocation batch from what is bound; decides whether the boundary points ride in it
+static void monitor_clear(gpe_engine* e);
+// a precomputed base lives on the bound points: a monitor on them (the only one allowed then) does not outlive a new bind
+static void monitor_drop_if_on_bound_points(gpe_engine* e) {
+    if (e->mon_every > 0 && e->cfg.base_mode >= 0 && e->cfg.base_kind == GPE_BASE_PRECOMPUTED) monitor_clear(e);
+}
+
 static int rebuild_main(gpe_engine* e) {
     if (!e->ux) return GPE_OK;
     const bool merged = e->merge_bc && e->uxb && e->nb_user > 0 && e->nb_user * 8 <= e->n_pde;
@@ -1893,6 +1912,8 @@ int gpe_bind_points(gpe_engine* e, const float* d_x, int64_t n_local, const floa
     if (!e) return GPE_ERR_INVALID;
     if (!d_x || n_local <= 0) FAIL(e, GPE_ERR_INVALID, "bind_points: need n_local > 0 points");
     if (e->cfg.potential == GPE_POT_PRECOMPUTED && !d_V) FAIL(e, GPE_ERR_INVALID, "precomputed potential requested but d_V is NULL");
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    monitor_drop_if_on_bound_points(e);
     e->ux = d_x; e->uV = d_V; e->n_pde = n_local;
     int rc = rebuild_main(e);
     if (rc) return rc;
@@ -1944,6 +1965,8 @@ int gpe_bind_orth(gpe_engine* e, int k, const float* d_psi) {
 
 int gpe_bind_base(gpe_engine* e, const float* d_phi, const float* d_phi1, const float* d_phi2) {
     if (!e) return GPE_ERR_INVALID;
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    monitor_drop_if_on_bound_points(e);
     e->orth_host[4] = d_phi; e->orth_host[5] = d_phi1; e->orth_host[6] = d_phi2;
     HIPCHK(e, hipMemcpyAsync((void*)e->orth_dev, e->orth_host, sizeof e->orth_host, hipMemcpyHostToDevice, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));
@@ -1993,6 +2016,139 @@ int gpe_eval_density(gpe_engine* e, const float* d_x, int64_t n, float dx, int a
                        n, e->aux.ld, e->nd.n_out);
     HIPCHK(e, hipGetLastError());
     HIPCHK(e, hipStreamSynchronize(e->stream));
+    return GPE_OK;
+}
+
+
+// ---- observables of the current state (gpe_observe.h) --------------------------------------------------------------------
+static int obs_ensure(gpe_engine* e) {
+    if (e->obs_buf) return GPE_OK;
+    int rc;
+    if ((rc = dev_alloc(e, (Batch*)nullptr, &e->obs_buf, (size_t)2 * OBS_MAX_WG * OB_ROW + OB_ROW))) return rc;
+    return dev_alloc(e, (Batch*)nullptr, &e->obs_out, 1);
+}
+static bool precomputed_base(const gpe_engine* e) { return e->cfg.base_mode >= 0 && e->cfg.base_kind == GPE_BASE_PRECOMPUTED; }
+// which points an observables call / a monitor may look at: any, unless something exists on the bound points only
+static int obs_check_points(gpe_engine* e, const char* who, const float* d_x, int64_t n, const float* d_V) {
+    if (n <= 0) FAIL(e, GPE_ERR_INVALID, "%s: need n > 0 points", who);
+    if (precomputed_base(e)) {
+        if (!(d_x == e->ux && n == e->n_pde))
+            FAIL(e, GPE_ERR_INVALID, "%s needs an analytic base on other points than the bound ones (the precomputed base exists on the bound points only)", who);
+        if (!e->orth_host[4] || !e->orth_host[5] || !e->orth_host[6]) FAIL(e, GPE_ERR_STATE, "%s: precomputed base not bound (gpe_bind_base)", who);
+    }
+    if (e->cfg.potential == GPE_POT_PRECOMPUTED && !d_V) FAIL(e, GPE_ERR_INVALID, "%s: precomputed potential requested but d_V is NULL", who);
+    return GPE_OK;
+}
+// the two reduction passes over the full jets b.O of the points x, and the struct into *dst (device memory); nothing synchronises
+static int launch_observe(gpe_engine* e, Batch& b, const float* x, int64_t n, const float* V, float dv, struct gpe_observables* dst) {
+    const unsigned g = (unsigned)std::min<int64_t>(cdiv(n, OBS_THREADS), OBS_MAX_WG);        // a function of n alone: fixed point -> thread map
+    double* slab1 = e->obs_buf;
+    double* slab2 = slab1 + (size_t)OBS_MAX_WG * OB_ROW;
+    double* raw = slab2 + (size_t)OBS_MAX_WG * OB_ROW;
+    const float* const* bp = (const float* const*)e->orth_dev;
+#define OBS_CHAIN(DD)                                                                                                                     \
+    hipLaunchKernelGGL((k_obs_pass1<DD>), dim3(g), dim3(OBS_THREADS), 0, e->stream, e->ph, e->base_norm, x, V, (const float*)b.O, bp, n, b.ld, slab1); \
+    hipLaunchKernelGGL(k_obs_reduce, dim3(1), dim3(OBS_THREADS), 0, e->stream, (const double*)slab1, (int)g, raw);                       \
+    hipLaunchKernelGGL((k_obs_pass2<DD>), dim3(g), dim3(OBS_THREADS), 0, e->stream, e->ph, e->base_norm, x, V, (const float*)b.O, bp, n, b.ld, \
+                       (const double*)raw, (double)dv, slab2);
+    switch (e->nd.dim) {
+        case 1: OBS_CHAIN(1) break;
+        case 2: OBS_CHAIN(2) break;
+        default: OBS_CHAIN(3) break;
+    }
+#undef OBS_CHAIN
+    hipLaunchKernelGGL(k_obs_finish, dim3(1), dim3(OBS_THREADS), 0, e->stream, e->ph, (const double*)slab2, (int)g, (const double*)raw, (double)dv,
+                       (double)n, (const OptDev*)e->od, dst);
+    HIPCHK(e, hipGetLastError());
+    return GPE_OK;
+}
+
+int gpe_observables(gpe_engine* e, const float* d_x, int64_t n, const float* d_V, float dv, struct gpe_observables* out) {
+    if (!e || !out) return GPE_ERR_INVALID;
+    if (!d_x) {
+        if (!e->ux) FAIL(e, GPE_ERR_STATE, "observables of the bound points before bind_points");
+        d_x = e->ux; n = e->n_pde; d_V = e->uV;
+    }
+    int rc;
+    if ((rc = obs_check_points(e, "observables", d_x, n, d_V))) return rc;
+    if ((rc = obs_ensure(e))) return rc;
+    if ((rc = aux_forward(e, d_x, n, 1 + 2 * e->nd.dim, e->nd.dim))) return rc;       // full diagonal second derivatives, as gpe_forward_jets
+    if ((rc = launch_observe(e, e->aux, d_x, n, d_V, dv, e->obs_out))) return rc;
+    HIPCHK(e, hipMemcpyAsync(out, e->obs_out, sizeof *out, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    return GPE_OK;
+}
+
+static void monitor_clear(gpe_engine* e) {
+    e->mon_every = 0; e->mon_steps = 0; e->mon_records = 0;
+    e->mon_x = nullptr; e->mon_V = nullptr; e->mon_n = 0;
+    free_batch(e->mon);
+    if (e->mon_ring) { (void)hipFree(e->mon_ring); e->mon_ring = nullptr; e->mon_cap = 0; }
+}
+
+int gpe_bind_monitor(gpe_engine* e, const float* d_x, int64_t n, const float* d_V, float dv, int64_t every, int32_t capacity) {
+    if (!e) return GPE_ERR_INVALID;
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    if (!d_x || every <= 0) { monitor_clear(e); return GPE_OK; }
+    // validate and allocate first, swap last: a bind that fails leaves the monitor that was there, records included
+    int rc;
+    if ((rc = obs_check_points(e, "monitor", d_x, n, d_V))) return rc;
+    if ((rc = obs_ensure(e))) return rc;
+    const int cap = capacity > 0 ? capacity : 4096;
+    struct gpe_observables* ring = e->mon_ring;
+    if (cap != e->mon_cap) {
+        ring = nullptr;
+        if (hipMalloc((void**)&ring, (size_t)cap * sizeof(struct gpe_observables)) != hipSuccess) {
+            (void)hipGetLastError();
+            FAIL(e, GPE_ERR_NOMEM, "monitor: no memory for a ring of %d records", cap);
+        }
+    }
+    Batch nb;
+    if (e->mon.n == n && e->mon.O) std::swap(nb, e->mon);           // same size: the batch is reused
+    if ((rc = setup_batch(e, nb, d_x, n, 1 + 2 * e->nd.dim, e->nd.dim, false, d_V, /*with_store=*/false))) {
+        free_batch(nb);
+        if (ring != e->mon_ring) (void)hipFree(ring);
+        return rc;                                                   // (a reused batch cannot fail: nothing is allocated for it)
+    }
+    free_batch(e->mon);
+    e->mon = nb;
+    if (ring != e->mon_ring) { if (e->mon_ring) (void)hipFree(e->mon_ring); e->mon_ring = ring; e->mon_cap = cap; }
+    HIPCHK(e, hipMemsetAsync(e->mon_ring, 0, (size_t)cap * sizeof(struct gpe_observables), e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    e->mon_x = d_x; e->mon_V = d_V; e->mon_n = n; e->mon_dv = dv; e->mon_every = every;
+    e->mon_steps = 0; e->mon_records = 0;
+    return GPE_OK;
+}
+
+// k steps were just enqueued (never past a monitor step: gpe_run cuts there).  On a monitor step: forward of the monitor points with the
+// parameters that step left behind -- on the fused path through the packed weight copies the update refreshed, or ensure_packed
+// refreshes here, the path gpe_forward between two gpe_run calls takes -- the reduction chain, one record into the ring.
+static int monitor_after_steps(gpe_engine* e, int64_t k) {
+    if (e->mon_every <= 0) return GPE_OK;
+    e->mon_steps += k;
+    if (e->mon_steps % e->mon_every != 0) return GPE_OK;
+    int rc;
+    if ((rc = mlp_forward(e, e->mon, false))) return rc;
+    if ((rc = launch_observe(e, e->mon, e->mon_x, e->mon_n, e->mon_V, e->mon_dv, e->mon_ring + (e->mon_records % e->mon_cap)))) return rc;
+    e->mon_records++;
+    return GPE_OK;
+}
+
+int gpe_read_monitor(gpe_engine* e, int64_t first, int64_t count, struct gpe_observables* out, int64_t* available) {
+    if (!e || first < 0 || count < 0 || (count > 0 && !out)) return GPE_ERR_INVALID;
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    if (available) *available = e->mon_records;
+    if (count == 0) return GPE_OK;
+    if (first + count > e->mon_records)
+        FAIL(e, GPE_ERR_INVALID, "monitor records [%lld, %lld) requested, %lld exist", (long long)first, (long long)(first + count), (long long)e->mon_records);
+    if (first < e->mon_records - e->mon_cap)
+        FAIL(e, GPE_ERR_INVALID, "monitor record %lld is gone: the ring keeps the newest %d of %lld", (long long)first, e->mon_cap, (long long)e->mon_records);
+    for (int64_t i = 0; i < count;) {
+        const int64_t slot = (first + i) % e->mon_cap;
+        const int64_t run = std::min<int64_t>(count - i, e->mon_cap - slot);
+        HIPCHK(e, hipMemcpy(out + i, e->mon_ring + slot, run * sizeof(struct gpe_observables), hipMemcpyDeviceToHost));
+        i += run;
+    }
     return GPE_OK;
 }
 
@@ -2483,6 +2639,7 @@ int gpe_step(gpe_engine* e, gpe_scalars* out) {
     e->fu_want = false;
     if (rc) { e->fu_done = false; e->fu_parts = false; return rc; }
     if ((rc = gpe_step_update(e))) return rc;
+    if ((rc = monitor_after_steps(e, 1))) return rc;
     if (out) return gpe_read_scalars(e, out);
     return GPE_OK;
 }
@@ -2552,9 +2709,23 @@ int gpe_run(gpe_engine* e, int64_t n_steps) {
         }
         if (e->graph_exec) {
             int64_t done = 0;
-            for (; done + e->graph_steps <= n_steps; done += e->graph_steps) HIPCHK(e, hipGraphLaunch(e->graph_exec, e->stream));
-            after_update(e);
-            e->phase = 0;
+            while (done + e->graph_steps <= n_steps) {
+                // a replay must not run past a monitor step: up to there with plain launches when fewer than a graph's steps are left to it
+                const int64_t room = e->mon_every > 0 ? e->mon_every - e->mon_steps % e->mon_every : e->graph_steps;
+                if (room >= e->graph_steps) {
+                    HIPCHK(e, hipGraphLaunch(e->graph_exec, e->stream));
+                    after_update(e);
+                    e->phase = 0;
+                    done += e->graph_steps;
+                    int rc = monitor_after_steps(e, e->graph_steps);
+                    if (rc) return rc;
+                } else {
+                    for (int64_t i = 0; i < room && done < n_steps; ++i, ++done) {
+                        int rc = gpe_step(e, nullptr);
+                        if (rc) return rc;
+                    }
+                }
+            }
             for (; done < n_steps; ++done) {          // remainder: plain launches
                 int rc = gpe_step(e, nullptr);
                 if (rc) return rc;

@@ -1,0 +1,226 @@
+// gpe_observe.h -- observables of the NORMALISED state on a point set, formed on the device from the full NN output jets
+// O [C][n_out][ld], C = 1 + 2 D (value, D first derivatives, D diagonal second derivatives; point index contiguous):
+// norm, energy parts, chemical potential, <L_z>, density moments, peak density and the residual of the normalised state
+// (include/gpe_hip.h: struct gpe_observables).  Replaces the host-side sums of tools/accuracy_cfg4.py:state_numbers (the reference has no
+// counterpart: it never evaluates the energy of a trained state).
+//
+// Launch chain (all on the engine's stream, nothing synchronises):
+//   k_obs_pass1   per point u and its derivatives as the head forms them (fp32: u_jets_from), then the summands in fp64;
+//                 one partial row per workgroup into a slab
+//   k_obs_reduce  one workgroup adds the slab rows in index order -> raw totals
+//   k_obs_pass2   with I and mu from the totals: sum |H[phi] phi - mu phi|^2, phi = u / sqrt(I), one partial per workgroup
+//   k_obs_finish  one workgroup adds those partials in index order and writes the struct (staging slot or monitor ring)
+// Every point belongs to a fixed thread, every partial to a fixed slab row, every sum is added in a fixed tree: no atomics, so a
+// record repeats bit for bit (README, "Reproducibility").
+#pragma once
+#include "gpe_head.h"
+
+// raw sums over the points (no quadrature weight): rho = |u|^2
+enum { OB_I = 0,      // sum rho
+       OB_K = 1,      // sum |grad u|^2
+       OB_P = 2,      // sum V rho
+       OB_S = 3,      // sum Re(u* N(u)), N the engine's nonlinear term (gamma included)
+       OB_L = 4,      // sum psi_r D psi_i - psi_i D psi_r, D = x d_y - y d_x   (k_head_pde: rzl)
+       OB_LAP = 5,    // sum Re(u* lap u)
+       OB_X = 6,      // [3] sum x_k rho
+       OB_XX = 9,     // [3] sum x_k^2 rho
+       OB_NSUM = 12,
+       OB_MAX = 12,   // max rho
+       OB_COUNT = 13,
+       OB_ROW = 16 }; // doubles per slab row
+#define OBS_THREADS 256
+#define OBS_MAX_WG 1024          // slab rows: the grid never exceeds it, whatever the device
+
+GPE_DEV int obs_power(const Phys& ph) { return ph.complex_psi ? 3 : ph.p; }      // complex psi: gamma |psi|^2 psi
+
+// K values per thread -> per workgroup, in thread k < K of the workgroup (values [0, nsum) are added, the rest take the maximum).
+// Wave: shuffle tree over 64 lanes; workgroup: one LDS row per wave, added in wave order.
+template <int K>
+GPE_DEV double obs_block_reduce(double (&v)[K], int nsum, double* lds /*[waves][K]*/) {
+    const int w = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        double t = v[k];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const double q = __shfl_down(t, o, 64);
+            t = k < nsum ? t + q : fmax(t, q);
+        }
+        if ((threadIdx.x & 63) == 0) lds[w * K + k] = t;
+    }
+    __syncthreads();
+    double r = 0.0;
+    if (threadIdx.x < K) {
+        const int k = threadIdx.x;
+        r = lds[k];
+        for (int i = 1; i < nw; ++i) r = k < nsum ? r + lds[i * K + k] : fmax(r, lds[i * K + k]);
+    }
+    return r;
+}
+
+// u-jets of both components of point m in fp32, exactly as k_head_pde forms them
+template <int D>
+GPE_DEV void obs_point(const Phys& ph, float base_norm, const float* __restrict__ x, const float* __restrict__ O,
+                       const float* const* __restrict__ bptr, int64_t ld, int64_t m, float* xv, float (&U)[2][1 + 2 * D]) {
+    constexpr int C = 1 + 2 * D;
+#pragma unroll
+    for (int k = 0; k < D; ++k) xv[k] = x[m * D + k];
+#pragma unroll
+    for (int c = 0; c < C; ++c) U[1][c] = 0.f;
+    for (int o = 0; o < ph.n_out; ++o) load_u_jets<C, D>(ph, O, ld, m, o, xv, base_norm, bptr, U[o]);
+}
+
+template <int D>
+__global__ __launch_bounds__(OBS_THREADS) void k_obs_pass1(Phys ph, float base_norm, const float* __restrict__ x,
+                                                           const float* __restrict__ Vpre, const float* __restrict__ O,
+                                                           const float* const* __restrict__ bptr, int64_t N, int64_t ld,
+                                                           double* __restrict__ slab) {
+    constexpr int C = 1 + 2 * D;
+    __shared__ double lds[(OBS_THREADS / 64) * OB_COUNT];
+    double acc[OB_COUNT];
+#pragma unroll
+    for (int k = 0; k < OB_COUNT; ++k) acc[k] = 0.0;
+    for (int64_t m = (int64_t)blockIdx.x * OBS_THREADS + threadIdx.x; m < N; m += (int64_t)gridDim.x * OBS_THREADS) {
+        float xv[3] = {0.f, 0.f, 0.f};
+        float U[2][C];
+        obs_point<D>(ph, base_norm, x, O, bptr, ld, m, xv, U);
+        const double V = (double)potential_at(ph, xv, Vpre, m);
+        double rho = 0.0, g2 = 0.0, ulap = 0.0;
+        for (int o = 0; o < ph.n_out; ++o) {
+            const double u = (double)U[o][0];
+            rho += u * u;
+            double lap = 0.0;
+#pragma unroll
+            for (int k = 0; k < D; ++k) { const double uk = (double)U[o][1 + k]; g2 += uk * uk; lap += (double)U[o][1 + D + k]; }
+            ulap += u * lap;
+        }
+        double s;
+        if (!ph.complex_psi) {
+            const double u = (double)U[0][0], a = ph.abs_power ? fabs(u) : u;
+            double pw = 1.0;
+            for (int i = 0; i < ph.p - 1; ++i) pw *= a;
+            s = (double)ph.gamma * pw * u * u;                // u * gamma u^p  |  u * gamma |u|^(p-1) u
+        } else {
+            s = (double)ph.gamma * rho * rho;
+            if constexpr (D >= 2) {
+                const double xx = (double)xv[0], yy = (double)xv[1];
+                const double Dr = xx * (double)U[0][2] - yy * (double)U[0][1];
+                const double Di = xx * (double)U[1][2] - yy * (double)U[1][1];
+                acc[OB_L] += (double)U[0][0] * Di - (double)U[1][0] * Dr;
+            }
+        }
+        acc[OB_I] += rho; acc[OB_K] += g2; acc[OB_P] += V * rho; acc[OB_S] += s; acc[OB_LAP] += ulap;
+#pragma unroll
+        for (int k = 0; k < D; ++k) { const double xk = (double)xv[k]; acc[OB_X + k] += xk * rho; acc[OB_XX + k] += xk * xk * rho; }
+        acc[OB_MAX] = fmax(acc[OB_MAX], rho);              // (fmax drops NaNs: k_obs_finish takes the NaN of the norm instead)
+    }
+    const double r = obs_block_reduce<OB_COUNT>(acc, OB_NSUM, lds);
+    if (threadIdx.x < OB_COUNT) slab[(size_t)blockIdx.x * OB_ROW + threadIdx.x] = r;
+}
+
+// rows of a slab added in index order by ONE workgroup: thread t takes rows t, t + 256, ..., then the workgroup tree
+template <int K>
+GPE_DEV double obs_slab_total(const double* __restrict__ slab, int rows, int nsum, double* lds) {
+    double v[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) v[k] = 0.0;
+    for (int r = threadIdx.x; r < rows; r += OBS_THREADS) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) { const double q = slab[(size_t)r * OB_ROW + k]; v[k] = k < nsum ? v[k] + q : fmax(v[k], q); }
+    }
+    return obs_block_reduce<K>(v, nsum, lds);
+}
+
+__global__ __launch_bounds__(OBS_THREADS) void k_obs_reduce(const double* __restrict__ slab, int rows, double* __restrict__ raw) {
+    __shared__ double lds[(OBS_THREADS / 64) * OB_COUNT];
+    const double r = obs_slab_total<OB_COUNT>(slab, rows, OB_NSUM, lds);
+    if (threadIdx.x < OB_COUNT) raw[threadIdx.x] = r;
+}
+
+// energy parts of the normalised state from the raw totals (formulas of GPE_RIESZ_VARIATIONAL, include/gpe_hip.h)
+struct ObsParts { double I, kin, pot, inter, rot, lz, mu, mu_lap; };
+GPE_DEV ObsParts obs_parts(const Phys& ph, const double* __restrict__ raw, double dv) {
+    ObsParts q;
+    const int p = obs_power(ph);
+    const double c = (double)ph.kin, sr = raw[OB_I];
+    q.I = dv * sr;
+    q.kin = c * raw[OB_K] / sr;
+    q.pot = raw[OB_P] / sr;
+    q.inter = 2.0 / (double)(p + 1) * (dv * raw[OB_S]) / pow(q.I, 0.5 * (double)(p + 1));
+    q.lz = raw[OB_L] / sr;
+    q.rot = -(double)ph.omega_rot * q.lz;
+    const double tail = q.pot + 0.5 * (double)(p + 1) * q.inter + q.rot;
+    q.mu = q.kin + tail;
+    q.mu_lap = -c * raw[OB_LAP] / sr + tail;
+    return q;
+}
+
+template <int D>
+__global__ __launch_bounds__(OBS_THREADS) void k_obs_pass2(Phys ph, float base_norm, const float* __restrict__ x,
+                                                           const float* __restrict__ Vpre, const float* __restrict__ O,
+                                                           const float* const* __restrict__ bptr, int64_t N, int64_t ld,
+                                                           const double* __restrict__ raw, double dv, double* __restrict__ slab) {
+    constexpr int C = 1 + 2 * D;
+    __shared__ double lds[OBS_THREADS / 64];
+    const ObsParts q = obs_parts(ph, raw, dv);
+    const int p = obs_power(ph);
+    const double is1 = 1.0 / sqrt(q.I), isp = pow(q.I, -0.5 * (double)p), c = (double)ph.kin, g = (double)ph.gamma, Om = (double)ph.omega_rot;
+    double acc[1] = {0.0};
+    for (int64_t m = (int64_t)blockIdx.x * OBS_THREADS + threadIdx.x; m < N; m += (int64_t)gridDim.x * OBS_THREADS) {
+        float xv[3] = {0.f, 0.f, 0.f};
+        float U[2][C];
+        obs_point<D>(ph, base_norm, x, O, bptr, ld, m, xv, U);
+        const double V = (double)potential_at(ph, xv, Vpre, m);
+        double lin[2] = {0.0, 0.0}, non[2] = {0.0, 0.0};          // linear part of H u, nonlinear term N(u)
+        for (int o = 0; o < ph.n_out; ++o) {
+            double lap = 0.0;
+#pragma unroll
+            for (int k = 0; k < D; ++k) lap += (double)U[o][1 + D + k];
+            lin[o] = -c * lap + V * (double)U[o][0];
+        }
+        if (!ph.complex_psi) {
+            const double u = (double)U[0][0], a = ph.abs_power ? fabs(u) : u;
+            double pw = 1.0;
+            for (int i = 0; i < ph.p - 1; ++i) pw *= a;
+            non[0] = g * pw * u;
+        } else {
+            const double ur = (double)U[0][0], ui = (double)U[1][0], rho = ur * ur + ui * ui;
+            non[0] = g * rho * ur; non[1] = g * rho * ui;
+            if constexpr (D >= 2) {                               // -Omega L_z psi = i Omega (x d_y - y d_x) psi
+                const double xx = (double)xv[0], yy = (double)xv[1];
+                const double Dr = xx * (double)U[0][2] - yy * (double)U[0][1];
+                const double Di = xx * (double)U[1][2] - yy * (double)U[1][1];
+                lin[0] += -Om * Di; lin[1] += Om * Dr;
+            }
+        }
+        for (int o = 0; o < ph.n_out; ++o) {
+            const double r = (lin[o] - q.mu * (double)U[o][0]) * is1 + non[o] * isp;      // H[phi] phi - mu phi
+            acc[0] += r * r;
+        }
+    }
+    const double r = obs_block_reduce<1>(acc, 1, lds);
+    if (threadIdx.x == 0) slab[(size_t)blockIdx.x * OB_ROW] = r;
+}
+
+__global__ __launch_bounds__(OBS_THREADS) void k_obs_finish(Phys ph, const double* __restrict__ slab, int rows, const double* __restrict__ raw,
+                                                            double dv, double n_points, const OptDev* __restrict__ od,
+                                                            struct gpe_observables* __restrict__ dst) {
+    __shared__ double lds[OBS_THREADS / 64];
+    const double r2 = obs_slab_total<1>(slab, rows, 1, lds);
+    if (threadIdx.x != 0) return;
+    const ObsParts q = obs_parts(ph, raw, dv);
+    struct gpe_observables o;
+    o.n = n_points; o.dv = dv; o.step = (double)od->step;
+    o.norm = q.I;
+    o.kin = q.kin; o.pot = q.pot; o.inter = q.inter; o.rot = q.rot;
+    o.energy = q.kin + q.pot + q.inter + q.rot;
+    o.mu = q.mu; o.mu_lap = q.mu_lap; o.lz = q.lz;
+    for (int k = 0; k < 3; ++k) {
+        const double mk = raw[OB_X + k] / raw[OB_I];
+        o.mean_x[k] = mk;
+        o.var_x[k] = raw[OB_XX + k] / raw[OB_I] - mk * mk;
+    }
+    o.peak_density = raw[OB_MAX] / q.I;              // I = NaN (a diverged state) makes this NaN too, whatever fmax kept
+    o.res_rms = sqrt(dv * r2);
+    *dst = o;
+}

@@ -439,6 +439,73 @@ class Engine:
         self._chk(self.lib.gpe_read_history(self._h, int(first_step), int(count), arr))
         return np.frombuffer(arr, dtype=np.float64).reshape(count, len(self.HISTORY_FIELDS)).copy()
 
+    # ---- observables of the current state, formed on the device (include/gpe_hip.h: struct gpe_observables) ------------------------------
+    OBSERVABLE_FIELDS = ("n", "dv", "step", "norm", "kin", "pot", "inter", "rot", "energy", "mu", "mu_lap", "lz",
+                         "mean_x0", "mean_x1", "mean_x2", "var_x0", "var_x1", "var_x2", "peak_density", "res_rms")
+
+    def _obs_args(self, x, V, dv, name):
+        x = self._to_dev(x, "x")
+        if x.dim() != 2 or x.shape[1] != self.cfg.dim:
+            raise ValueError(f"x must be [N,{self.cfg.dim}]")
+        Vt = None if V is None else self._to_dev(V, "V").reshape(-1)
+        if Vt is not None and Vt.numel() != x.shape[0]:
+            raise ValueError("V must hold one value per point")
+        self._keep[name + "_x"], self._keep[name + "_V"] = x, Vt
+        return x, Vt, float(self.cfg.dx if dv is None else dv)
+
+    def observables(self, x=None, V=None, dv=None) -> dict:
+        """E, mu, <L_z>, norm, moments, peak density and residual of the normalised state on the points x (None: the bound collocation
+        points with their bound potential); dv: quadrature weight (None: cfg.dx).  What tools/accuracy_cfg4.py:state_numbers used to
+        form on the host from forward_jets."""
+        out = capi.gpe_observables()
+        if x is None:
+            self._chk(self.lib.gpe_observables(self._h, None, 0, None, float(self.cfg.dx if dv is None else dv), C.byref(out)))
+        else:
+            x, Vt, dv = self._obs_args(x, V, dv, "obs")
+            self._chk(self.lib.gpe_observables(self._h, C.c_void_p(x.data_ptr()), x.shape[0],
+                                               C.c_void_p(Vt.data_ptr()) if Vt is not None else None, dv, C.byref(out)))
+        return out.as_dict()
+
+    def bind_monitor(self, x, every: int, V=None, dv=None, capacity: int = 0):
+        """Held-out monitor: after every `every`-th step enqueued by step() / run() the observables on x are appended to a device ring
+        (capacity 0: 4096 records) with no host synchronisation; read them with read_monitor()."""
+        if x is None or every <= 0:
+            return self.clear_monitor()
+        x, Vt, dv = self._obs_args(x, V, dv, "mon")
+        self._chk(self.lib.gpe_bind_monitor(self._h, C.c_void_p(x.data_ptr()), x.shape[0],
+                                            C.c_void_p(Vt.data_ptr()) if Vt is not None else None, dv, int(every), int(capacity)))
+        self._mon_cap = int(capacity) if capacity > 0 else 4096
+
+    def clear_monitor(self):
+        self._chk(self.lib.gpe_bind_monitor(self._h, None, 0, None, 0.0, 0, 0))
+        self._keep.pop("mon_x", None); self._keep.pop("mon_V", None)
+
+    def monitor_available(self) -> int:
+        """Records appended since bind_monitor (synchronises); the ring keeps the newest `capacity` of them."""
+        n = C.c_int64()
+        self._chk(self.lib.gpe_read_monitor(self._h, 0, 0, None, C.byref(n)))
+        return int(n.value)
+
+    def _read_monitor_raw(self, first, count):
+        avail = self.monitor_available()
+        if count is None:                                   # everything from `first` on that the ring still holds
+            first = max(int(first), avail - getattr(self, "_mon_cap", 4096), 0)
+            count = max(avail - first, 0)
+        arr = (capi.gpe_observables * max(int(count), 1))()
+        if count > 0:
+            self._chk(self.lib.gpe_read_monitor(self._h, int(first), int(count), arr, None))
+        return arr, int(count)
+
+    def read_monitor(self, first: int = 0, count=None):
+        """Monitor records [first, first+count) (0-based since bind_monitor; count None: up to the newest) as dicts."""
+        arr, count = self._read_monitor_raw(first, count)
+        return [arr[i].as_dict() for i in range(count)]
+
+    def read_monitor_array(self, first: int = 0, count=None) -> np.ndarray:
+        """The same records as one float64 array [count, len(OBSERVABLE_FIELDS)]."""
+        arr, count = self._read_monitor_raw(first, count)
+        return np.frombuffer(arr, dtype=np.float64).reshape(-1, len(self.OBSERVABLE_FIELDS))[:count].copy()
+
     # ---- pre-training on an analytic target (refine/harmonic_pinn_simulation.py:650-701) -----------------------------------
     def bind_target(self, target):
         t = None if target is None else self._to_dev(target, "target").reshape(-1, self.cfg.n_out)

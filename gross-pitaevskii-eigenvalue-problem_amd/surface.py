@@ -300,6 +300,25 @@ class _PINNBase:
         integral = torch.sum(u ** 2) * dx
         return (integral - 1.0) ** 2
 
+    def observables(self, X, dx, V=None):
+        """Energy, chemical potential, <L_z>, norm, centre / variance per axis, peak density and residual of the NORMALISED state of the
+        model, on the points X with quadrature weight dx: one device-side call (Engine.observables; the reference has no counterpart).
+        The state is the model's own: its gamma and its perturb_scale are set on the engine first (pde_loss / riesz_loss leave the engine
+        with the scale recovered from their `predictions` and the gamma of that call); power p and the kind of potential are those of
+        the engine as last used (the constructor's until a pde_loss call names others).  V: the potential on X where the model's
+        potential is handed over as an array and the flavour cannot form it itself.  Flavours whose base function is handed over as
+        arrays (gravity well) have it on the bound points only: X must be the very tensor that was bound, anything else is refused."""
+        eng = self._engine if self._engine is not None else self._get_engine()
+        eng.set_gamma(float(self.gamma))
+        eng.set_perturb_scale(float(self.perturb_scale))
+        if V is None and eng.cfg.potential == capi.POT_PRECOMPUTED:
+            V = self._potential_on(eng._to_dev(X, "x"))
+        return eng.observables(X, V=V, dv=dx)
+
+    def _potential_on(self, x):
+        """the potential array of flavours that hand it to the engine, on new points (None: the caller has to pass it)"""
+        return None
+
     def close(self):
         if self._engine is not None:
             self._pull()
@@ -1025,6 +1044,9 @@ class _PINN2D(_PINNBase):
         """V0 exp(-((x - x0)^2 + (y - y0)^2) / (2 sigma^2))   (src/gross_pitaevskii_2D.py:244-274) -> [N]"""
         x, y = inputs[:, 0], inputs[:, 1]
         return V0 * torch.exp(-((x - x0) ** 2 + (y - y0) ** 2) / (2 * sigma ** 2))
+
+    def _potential_on(self, x):
+        return self.compute_potential(x)
 
     def _bind(self, eng, inputs, boundary=None):
         x = eng._to_dev(inputs.detach() if isinstance(inputs, torch.Tensor) else inputs, "x")

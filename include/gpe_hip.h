@@ -150,10 +150,37 @@ typedef struct gpe_scalars {
     double reg;                   /* w_reg_f / (mean u^2 + eps) + w_reg_lam / (lambda^2 + eps)  (0 when both weights are 0) */
 } gpe_scalars;
 
+/* Observables of the state on a point set, formed on the device (gpe_observables, the monitor ring).  Replaces the host-side sums of
+ * tools/accuracy_cfg4.py:state_numbers and tools/accuracy_nd.py (jets copied to the host, numpy); the reference has no counterpart:
+ * it never evaluates energy, chemical potential or <L_z> of a trained state.
+ * u is the physical wavefunction as the head forms it (envelope, perturb_scale, analytic base included), c = kinetic_coeff, dv the
+ * quadrature weight, I = dv sum |u|^2.  With K = c dv sum |grad u|^2, P = dv sum V |u|^2, S = dv sum Re(u* N(u)) (N the engine's nonlinear
+ * term: gamma u^p, gamma |u|^(p-1) u under abs_power, gamma |psi|^2 psi for complex psi, where p counts as 3) and
+ * L = dv sum [psi_r D psi_i - psi_i D psi_r], D = x d_y - y d_x  (-Omega L_z psi = i Omega D psi):
+ *   kin = K/I, pot = P/I, inter = 2/(p+1) S / I^((p+1)/2), rot = -Omega L/I, lz = L/I
+ * -- the energy of the NORMALISED state u/sqrt(I), the formulas of GPE_RIESZ_VARIATIONAL above.  Sums in fp64 from the fp32 jets, added
+ * in a fixed order (no atomics): a record repeats bit for bit.  Single-rank semantics: every rank of a data-parallel run gets the
+ * numbers of its own points; combining ranks is left to the caller.
+ * (The struct has no typedef of its own name: C keeps typedef names and functions in one name space, and the entry point is called
+ * gpe_observables.  Write `struct gpe_observables`.) */
+struct gpe_observables {
+    double n, dv, step;          /* points, quadrature weight, optimiser step of the parameters evaluated (device-side value) */
+    double norm;                 /* I = dv * sum |u|^2 of the RAW state */
+    double kin, pot, inter, rot; /* energy parts of the NORMALISED state u / sqrt(I) */
+    double energy;               /* kin + pot + inter + rot */
+    double mu;                   /* kin + pot + (p+1)/2 * inter + rot */
+    double mu_lap;               /* mu with the kinetic part taken as -c * dv * sum Re(u* lap u) / I instead of kin */
+    double lz;                   /* <L_z> of the normalised state (0 for real psi) */
+    double mean_x[3], var_x[3];  /* density-weighted centre and variance per axis (unused axes 0) */
+    double peak_density;         /* max |u|^2 / I */
+    double res_rms;              /* sqrt(dv * sum |H[phi] phi - mu phi|^2), phi = u / sqrt(I): the residual of the normalised state (two-pass) */
+};
+
 /* ---- lifetime ------------------------------------------------------------------------------ */
 int gpe_abi_version(void);
 size_t gpe_sizeof_config(void);   /* sizeof(gpe_config)  -- lets a foreign-language binding verify its struct layout */
 size_t gpe_sizeof_scalars(void);  /* sizeof(gpe_scalars) */
+size_t gpe_sizeof_observables(void);   /* sizeof(struct gpe_observables) */
 /* replaces: GrossPitaevskiiPINN(...).to(device) + torch.optim.Adam(...) + scheduler construction
  * (refine/harmonic_pinn_simulation.py:295,309-314 ; nb c10:L63,L73-78) */
 int gpe_create(const gpe_config* cfg, int device, void* hip_stream, gpe_engine** out);
@@ -200,6 +227,26 @@ int gpe_residual(gpe_engine* e, gpe_scalars* out, float* d_psi, float* d_residua
 /* plot_wavefunction normalisation (refine/...:463-474 ; nb c12:L30-42): u = base + scale*NN on the grid d_x,
  * u /= sqrt(sum u^2 * dx), |u| if abs_flag; d_u [n,out], d_density [n] (either may be NULL) */
 int gpe_eval_density(gpe_engine* e, const float* d_x, int64_t n, float dx, int abs_flag, float* d_u, float* d_density);
+
+/* ---- observables of the current state, on the device (replaces tools/accuracy_cfg4.py:state_numbers; no reference counterpart) ------
+ * gpe_observables: jets of the current parameters on d_x [n, dim] (the forward pass behind gpe_forward_jets, one allocation of that
+ * size: n is not cut into chunks), two reduction passes, synchronise, fill *out.  d_x == NULL: the bound collocation points and their
+ * bound potential (d_V, n ignored).  d_V [n]: needed exactly where gpe_bind_points needs it (GPE_POT_PRECOMPUTED).  A precomputed base
+ * exists on the bound points only: other point sets are refused with GPE_ERR_INVALID.  dv: quadrature weight. */
+int gpe_observables(gpe_engine* e, const float* d_x, int64_t n, const float* d_V, float dv, struct gpe_observables* out);
+/* Held-out monitor: after every `every`-th step enqueued since this call by gpe_step / gpe_run, the observables of the parameters
+ * that step left behind are evaluated on d_x and appended to a device ring of `capacity` records (<= 0: 4096) -- no host
+ * synchronisation, no host copy; the monitor writes nothing a step reads, so the training trajectory is the one without it.
+ * The cadence counts ENQUEUED steps (the host has no mirror of the optimiser step: early stopping is decided on the device);
+ * the record's `step` field is read on the device.  gpe_run cuts its graph replays at monitor steps and fills in with plain
+ * launches.  d_x == NULL or every <= 0 clears the monitor.  A bind that fails leaves the monitor that was there, its records
+ * included.  With a precomputed base (monitor on the bound points only) gpe_bind_points and gpe_bind_base clear the monitor.
+ * Buffers stay the caller's.  gpe_step_dp / gpe_run_dp and the
+ * three-phase entry points ignore the monitor. */
+int gpe_bind_monitor(gpe_engine* e, const float* d_x, int64_t n, const float* d_V, float dv, int64_t every, int32_t capacity);
+/* synchronise; *available = records written since the bind; copies records [first, first+count) (0-based since the bind) to out.
+ * Only the newest `capacity` records survive: an older one is GPE_ERR_INVALID.  count == 0 with out == NULL just asks. */
+int gpe_read_monitor(gpe_engine* e, int64_t first, int64_t count, struct gpe_observables* out, int64_t* available);
 
 /* ---- training step: the epoch body refine/...:328-361 ; nb c10:L84-103 ------------------------------ */
 /* phase 1: forward jets + local sums  -> exchange buffer "sums" */

@@ -40,6 +40,8 @@ ap.add_argument("--sets", type=int, default=16, help="number of jittered colloca
 ap.add_argument("--no-basin", action="store_true", help="skip the second solver run (started from the trained network state)")
 ap.add_argument("--solver-n", type=int, default=192)
 ap.add_argument("--seed", type=int, default=0)
+ap.add_argument("--monitor", type=int, default=0, help="record the observables on the REGULAR grid every this many epochs while training on the "
+                "jittered sets (device-side monitor, no host synchronisation); the records go into the JSON")
 ap.add_argument("--out", default="")
 a = ap.parse_args()
 layers = [int(v) for v in a.layers.split(",")]
@@ -97,20 +99,15 @@ eng.bind_boundary(torch.as_tensor(xb, device="cuda"))
 t0 = time.time()
 
 
-def state_numbers():
-    """E, mu, Lz, norm of the network state on the training grid from its output jets (fp64 sums on the host)."""
-    J = eng.forward_jets(xd).cpu().numpy().astype(np.float64)            # [5][N][2]: psi, d_x, d_y, d_xx, d_yy
-    pr, pi_ = J[0, :, 0], J[0, :, 1]
-    x, y = X[:, 0].astype(np.float64), X[:, 1].astype(np.float64)
-    rho = pr * pr + pi_ * pi_
-    I = dv * rho.sum()
-    kin = 0.5 * dv * (J[1] ** 2 + J[2] ** 2).sum()
-    pot = dv * (0.5 * (x * x + y * y) * rho).sum()
-    inter = 0.5 * g * dv * (rho * rho).sum()
-    lz = dv * (pr * (x * J[2, :, 1] - y * J[1, :, 1]) - pi_ * (x * J[2, :, 0] - y * J[1, :, 0])).sum()
-    En = (kin + pot) / I + inter / I ** 2 - Om * lz / I                  # energy of the normalised state
-    mun = (kin + pot) / I + 2.0 * inter / I ** 2 - Om * lz / I
-    return dict(E=float(En), mu=float(mun), lz=float(lz / I), norm=float(I), psi=(pr + 1j * pi_) / math.sqrt(I))
+def state_numbers(want_psi=True):
+    """E, mu, Lz, norm of the network state on the training grid: Engine.observables (fp64 sums on the device); psi is fetched only
+    where the field itself is needed (vortex counting, density error)."""
+    o = eng.observables(xd, dv=dv)
+    out = dict(E=o["energy"], mu=o["mu"], lz=o["lz"], norm=o["norm"])
+    if want_psi:
+        J = eng.forward(xd).cpu().numpy().astype(np.float64)
+        out["psi"] = (J[:, 0] + 1j * J[:, 1]) / math.sqrt(o["norm"])
+    return out
 
 
 def windings(psi2d, hgrid):
@@ -157,6 +154,9 @@ cells = np.stack([m.ravel() for m in np.meshgrid(ax, ax, indexing="ij")], axis=1
 sets = [xd]
 for _ in range(a.sets - 1 if a.resample > 0 else 0):
     sets.append(torch.as_tensor((cells + rng.uniform(-0.5 * h, 0.5 * h, cells.shape)).astype(np.float32), device="cuda"))
+if a.monitor > 0:
+    eng.bind_monitor(xd, every=a.monitor, dv=dv, capacity=max(1, a.epochs // a.monitor + 1))
+    sets = sets[1:] if len(sets) > 1 else sets          # ... which the optimiser then never sees: training on the jittered sets only
 epoch_ctr = 0
 for frac, lr in ((0.35, tlr), (0.2, tlr * 0.3), (0.15, tlr * 0.1), (0.1, tlr * 0.03), (0.1, tlr * 0.01), (0.05, tlr * 0.003), (0.05, tlr * 0.001)):
     eng.set_lr(lr)
@@ -178,6 +178,13 @@ for frac, lr in ((0.35, tlr), (0.2, tlr * 0.3), (0.15, tlr * 0.1), (0.1, tlr * 0
         print(f"   lr {lr:.1e} loss {sc['loss']:.3e} pde {sc['pde']:.3e} mu {sc['mu']:.6f} E {sc['riesz']:.6f} int {sc['integral']:.6f} ({time.time() - t0:.0f} s)", flush=True)
     rows.append(dict(lr=lr, epochs=int(a.epochs * frac), loss=sc["loss"], pde=sc["pde"], mu=sc["mu"], norm=sc["integral"], energy=sc["riesz"]))
 wall = time.time() - t0
+monitor_rows = []
+if a.monitor > 0:
+    monitor_rows = [dict(step=r["step"], E=r["energy"], mu=r["mu"], mu_lap=r["mu_lap"], lz=r["lz"], norm=r["norm"], res_rms=r["res_rms"])
+                    for r in eng.read_monitor()]
+    eng.clear_monitor()
+    for r in monitor_rows[-5:]:
+        print(f"   monitor (regular grid) step {r['step']:.0f}: E {r['E']:.6f} mu {r['mu']:.6f} Lz {r['lz']:.4f} res {r['res_rms']:.3e}", flush=True)
 eng.bind_points(xd)
 s1 = state_numbers()
 v1 = windings(s1["psi"].reshape(n, n), h)
@@ -238,7 +245,7 @@ out = dict(case="cfg4_2d_rot", workload="cfg4_2d_6x128_rot", layers=layers, poin
            E_ref=ref["E"], mu_ref=ref["mu"], lz_ref=ref["lz"], vortices_ref=vref[0], solver_residual=ref["residual"],
            solver=f"oracle/gp_rotating_2d.py, {a.solver_n}^2 Fourier grid on [-12,12)^2, same seed",
            E_abs_err=abs(s1["E"] - ref["E"]), mu_abs_err=abs(s1["mu"] - ref["mu"]), density_rel_l2=rel_l2, final_pde_loss=sc["pde"],
-           basin=basin, density_rel_l2_best_rotation=rel_l2_rot, rotation_angle=theta_rot,
+           basin=basin, monitor=dict(every=a.monitor, grid="the regular training grid", records=monitor_rows), density_rel_l2_best_rotation=rel_l2_rot, rotation_angle=theta_rot,
            schedule=dict(lr=a.lr, train_lr=tlr, resample_every=a.resample, collocation_sets=len(sets), w_norm=a.w_norm, w_bc=a.w_bc, w_pde=a.w_pde, w_riesz=a.w_riesz, ladder="(0.35, 0.2, 0.15, 0.1, 0.1, 0.05, 0.05) of the epochs at lr x (1, .3, .1, .03, .01, .003, .001)"))
 path = a.out or os.path.join(ROOT, "gpurun_out", "accuracy_cfg4_2d_6x128_rot.json")
 os.makedirs(os.path.dirname(path), exist_ok=True)

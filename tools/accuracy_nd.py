@@ -185,15 +185,12 @@ if a.big_grid:
     rows.append(dict(gamma=cs["g"], epochs=a.big_epochs, mu=sc["mu"], loss=sc["loss"], pde=sc["pde"], norm=sc["integral"], lr=sc["lr"], riesz=sc["riesz"]))
 wall = time.time() - t0
 mu = rows[-1]["mu"]
-# mu of the NORMALISED state u / sqrt(int), from the three scalars of the last stage: with A = (kinetic + potential) / int and
-# B = g int(u^4) / int, the Rayleigh quotient is A + B and the variational energy of the normalised state A + B / (2 int); the
-# chemical potential of the normalised state is A + B / int.  (d mu / d int = B ~ 8 here: a norm that is off by 1e-4 moves the
-# raw quotient by 1e-3 although the state itself -- energy, density -- is right.)
-_int, _E = rows[-1]["norm"], rows[-1]["riesz"]
-mu_normalised = None
-if a.w_riesz != 0.0 and _int > 0.5:
-    _B = (mu - _E) / (1.0 - 0.5 / _int)
-    mu_normalised = (mu - _B) + _B / _int
+# mu of the NORMALISED state u / sqrt(int) on the grid bound last (the regular one): Engine.observables, fp64 sums on the device.  The raw
+# Rayleigh quotient above follows the norm with d mu / d int ~ 8 here: a norm that is off by 1e-4 moves it by 1e-3 although the state
+# itself -- energy, density -- is right.
+_int = rows[-1]["norm"]
+_obs = eng.observables()
+mu_normalised = _obs["mu"]
 # ---- density on a test grid vs the solver ----
 from oracle import gp_ground_state_nd as nd
 gr = truth["grids"][0]
@@ -217,7 +214,8 @@ out = dict(case=a.case, workload=cs["workload"], layers=cs["layers"], points=int
            schedule=dict(pretrain=a.pretrain, epochs=a.epochs, final=a.final, stages=a.stages, lr=a.lr, w_norm=a.w_norm, w_bc=a.w_bc,
                          w_riesz=a.w_riesz, w_norm_final=a.w_norm_final, resample=a.resample, sets=a.sets,
                          scheduler="constant lr per stage, fresh Adam per stage; last stage lr x (1, 0.3, 0.1, 0.03, 0.01, 0.003, 0.001)"),
-           energy=rows[-1]["riesz"], energy_ref=truth["energy"], big_grid=big)
+           energy=rows[-1]["riesz"], energy_ref=truth["energy"], big_grid=big,
+           observables={k: _obs[k] for k in ("norm", "kin", "pot", "inter", "energy", "mu", "mu_lap", "var_x", "peak_density", "res_rms")})
 path = a.out or os.path.join(ROOT, "gpurun_out", f"accuracy_{cs['workload']}.json")
 os.makedirs(os.path.dirname(path), exist_ok=True)
 json.dump(out, open(path, "w"), indent=1)
