@@ -68,6 +68,13 @@ class gpe_observables(C.Structure):
         return {n: (list(getattr(self, n)) if n in ("mean_x", "var_x") else getattr(self, n)) for n, _ in self._fields_}
 
 
+class gpe_sampler_spec(C.Structure):
+    """include/gpe_hip.h: gpe_sampler_spec -- the grid, clip box, seed, cell block and cadence of the device-side stratified sampler."""
+    _fields_ = [("shape", C.c_int64 * 3), ("lo", C.c_float * 3), ("hi", C.c_float * 3), ("clip_lo", C.c_float * 3),
+                ("clip_hi", C.c_float * 3), ("seed", C.c_uint64), ("first_cell", C.c_int64), ("n_local", C.c_int64),
+                ("draw0", C.c_int64), ("every", C.c_int64)]
+
+
 _vp, _i64, _int, _f = C.c_void_p, C.c_int64, C.c_int, C.c_float
 _P = C.POINTER
 
@@ -77,6 +84,7 @@ SYMBOLS = {
     "gpe_sizeof_config": (C.c_size_t, []),
     "gpe_sizeof_scalars": (C.c_size_t, []),
     "gpe_sizeof_observables": (C.c_size_t, []),
+    "gpe_sizeof_sampler_spec": (C.c_size_t, []),
     "gpe_exchange_dbl_count": (_i64, []),
     "gpe_use_external_exchange": (_int, [_vp, _vp, _i64, _vp, _i64]),
     "gpe_create": (_int, [_P(gpe_config), _int, _vp, _P(_vp)]),
@@ -99,6 +107,8 @@ SYMBOLS = {
     "gpe_set_adam_state": (_int, [_vp, _vp, _vp, C.c_size_t, _i64]),
     "gpe_reset_optimizer": (_int, [_vp, _f]),
     "gpe_bind_points": (_int, [_vp, _vp, _i64, _vp]),
+    "gpe_bind_sampler": (_int, [_vp, _P(gpe_sampler_spec)]),
+    "gpe_sampler_points": (_int, [_vp, _P(_vp), _P(_i64), _P(_i64)]),
     "gpe_bind_boundary": (_int, [_vp, _vp, _i64, _vp]),
     "gpe_bind_orth": (_int, [_vp, _int, _vp]),
     "gpe_bind_base": (_int, [_vp, _vp, _vp, _vp]),
@@ -165,7 +175,8 @@ def load():
     if lib.gpe_abi_version() != GPE_ABI_VERSION:
         raise ImportError(f"{path}: ABI version {lib.gpe_abi_version()} != {GPE_ABI_VERSION}")
     if lib.gpe_sizeof_config() != C.sizeof(gpe_config) or lib.gpe_sizeof_scalars() != C.sizeof(gpe_scalars) or \
-            lib.gpe_sizeof_observables() != C.sizeof(gpe_observables):
+            lib.gpe_sizeof_observables() != C.sizeof(gpe_observables) or \
+            lib.gpe_sizeof_sampler_spec() != C.sizeof(gpe_sampler_spec):
         raise ImportError(f"{path}: struct layout mismatch between include/gpe_hip.h and _capi.py")
     _lib = lib
     return lib

@@ -31,6 +31,7 @@ typedef enum { ncclFloat = 7, ncclDouble = 8 } ncclDataType_t;
 #include "gpe_common.h"
 #include "gpe_head.h"
 #include "gpe_observe.h"
+#include "gpe_sampler.h"
 #include "gpe_generic.h"
 #include "gpe_fused.h"
 #include "gpe_wide_api.h"
@@ -598,6 +599,13 @@ struct gpe_engine {
     int64_t mon_steps = 0, mon_records = 0;           // steps enqueued / records appended since the bind
     int mon_cap = 0;
     struct gpe_observables* mon_ring = nullptr;       // [mon_cap]
+    // device-side stratified sampler (gpe_bind_sampler): the engine owns the collocation points and redraws them in place
+    float* smp_x = nullptr;                           // [smp_n][dim]; ux points here while the sampler is bound
+    SamplerGrid smp_grid = {};
+    int64_t smp_n = 0, smp_first = 0, smp_every = 0;  // every == 0: no sampler
+    int64_t smp_draw0 = 0, smp_held = 0;              // draw at the bind / draw the buffer holds (as enqueued)
+    int64_t smp_steps = 0;                            // steps enqueued since the bind
+    bool capturing = false;                           // graph_build is recording: neither count the step nor redraw
     int phase = 0;                 // 0 idle, 1 after begin, 2 after backward
     std::string err;
     double* sums() { return dbl; }
@@ -1377,6 +1385,7 @@ int gpe_abi_version(void) { return GPE_ABI_VERSION; }
 size_t gpe_sizeof_config(void) { return sizeof(gpe_config); }
 size_t gpe_sizeof_scalars(void) { return sizeof(gpe_scalars); }
 size_t gpe_sizeof_observables(void) { return sizeof(struct gpe_observables); }
+size_t gpe_sizeof_sampler_spec(void) { return sizeof(gpe_sampler_spec); }
 int64_t gpe_exchange_dbl_count(void) { return S_COUNT + LS_COUNT + 4; }
 
 int gpe_use_external_exchange(gpe_engine* e, void* d_dbl, int64_t n_dbl, void* d_grad, int64_t n_grad) {
@@ -1798,7 +1807,7 @@ void gpe_destroy(gpe_engine* e) {
     free_batch(e->main); free_batch(e->bc); free_batch(e->sym); free_batch(e->aux); free_batch(e->mse); free_batch(e->mon);
     for (hipEvent_t ev : e->ev_pool) (void)hipEventDestroy(ev);
     if (e->ext_exchange) { e->grad = nullptr; e->dbl = nullptr; }
-    void* ps[] = {e->theta, e->am, e->av, e->grad, e->dbl, e->od, e->hist, e->last, (void*)e->orth_dev, e->Wpk, e->WpkT, e->gslab, e->gslab_bc, e->grad_bc, (void*)e->upd_snap, (void*)e->head_slots, (void*)e->upd_ticket, (void*)e->upd_snap_small, (void*)e->obs_buf, (void*)e->obs_out, (void*)e->mon_ring};
+    void* ps[] = {e->theta, e->am, e->av, e->grad, e->dbl, e->od, e->hist, e->last, (void*)e->orth_dev, e->Wpk, e->WpkT, e->gslab, e->gslab_bc, e->grad_bc, (void*)e->upd_snap, (void*)e->head_slots, (void*)e->upd_ticket, (void*)e->upd_snap_small, (void*)e->obs_buf, (void*)e->obs_out, (void*)e->mon_ring, (void*)e->smp_x};
     for (void* p : ps) if (p) (void)hipFree(p);
     delete e;
 }
@@ -1908,11 +1917,11 @@ static int rebuild_main(gpe_engine* e) {
     return GPE_OK;
 }
 
-int gpe_bind_points(gpe_engine* e, const float* d_x, int64_t n_local, const float* d_V) {
-    if (!e) return GPE_ERR_INVALID;
-    if (!d_x || n_local <= 0) FAIL(e, GPE_ERR_INVALID, "bind_points: need n_local > 0 points");
-    if (e->cfg.potential == GPE_POT_PRECOMPUTED && !d_V) FAIL(e, GPE_ERR_INVALID, "precomputed potential requested but d_V is NULL");
-    HIPCHK(e, hipStreamSynchronize(e->stream));
+static void sampler_clear(gpe_engine* e);
+static bool precomputed_base(const gpe_engine* e);
+
+// the bind itself, shared by gpe_bind_points (caller's points) and gpe_bind_sampler (the engine's own buffer)
+static int bind_points_impl(gpe_engine* e, const float* d_x, int64_t n_local, const float* d_V) {
     monitor_drop_if_on_bound_points(e);
     e->ux = d_x; e->uV = d_V; e->n_pde = n_local;
     int rc = rebuild_main(e);
@@ -1938,6 +1947,117 @@ int gpe_bind_points(gpe_engine* e, const float* d_x, int64_t n_local, const floa
     return GPE_OK;
 }
 
+int gpe_bind_points(gpe_engine* e, const float* d_x, int64_t n_local, const float* d_V) {
+    if (!e) return GPE_ERR_INVALID;
+    if (!d_x || n_local <= 0) FAIL(e, GPE_ERR_INVALID, "bind_points: need n_local > 0 points");
+    if (e->cfg.potential == GPE_POT_PRECOMPUTED && !d_V) FAIL(e, GPE_ERR_INVALID, "precomputed potential requested but d_V is NULL");
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    sampler_clear(e);                            // the caller's points take over
+    return bind_points_impl(e, d_x, n_local, d_V);
+}
+
+// ---- device-side stratified sampler ------------------------------------------------------------------------
+static void sampler_clear(gpe_engine* e) {       // the stream is idle (callers synchronise first)
+    if (e->smp_x) { (void)hipFree(e->smp_x); e->smp_x = nullptr; }
+    e->smp_n = 0; e->smp_every = 0; e->smp_steps = 0; e->smp_draw0 = 0; e->smp_held = 0; e->smp_first = 0;
+}
+
+// draw `draw` into the point buffer (and the [x ; -x] batch) on the engine's stream; nothing synchronises
+static int sampler_launch(gpe_engine* e, int64_t draw) {
+    float* xs = (e->cfg.w_sym != 0.f && e->sym.n == 2 * e->smp_n) ? e->sym.xown : nullptr;
+    hipLaunchKernelGGL(k_sampler_draw, dim3(cdiv(e->smp_n, SMP_THREADS)), dim3(SMP_THREADS), 0, e->stream, e->smp_grid, e->smp_first,
+                       e->smp_n, (uint64_t)draw, e->smp_x, xs);
+    HIPCHK(e, hipGetLastError());
+    e->smp_held = draw;
+    return GPE_OK;
+}
+
+// before the first kernel of a step: the set this step runs on.  A redraw leaves the engine as gpe_bind_points of the new set would
+// (the step starts with k_begin; Phys and the merged-boundary Pts depend on the point count and the pointers only, which stay) --
+// without that call's two synchronisations.
+static int sampler_before_step(gpe_engine* e) {
+    if (e->smp_every <= 0 || e->capturing) return GPE_OK;
+    const int64_t want = e->smp_draw0 + e->smp_steps / e->smp_every;
+    if (want == e->smp_held) return GPE_OK;
+    e->acc_clean = false;
+    return sampler_launch(e, want);
+}
+
+int gpe_bind_sampler(gpe_engine* e, const gpe_sampler_spec* sp) {
+    if (!e) return GPE_ERR_INVALID;
+    if (!sp) {                                   // clear: the buffer goes, so nothing stays bound
+        HIPCHK(e, hipStreamSynchronize(e->stream));
+        if (e->side) HIPCHK(e, hipStreamSynchronize(e->side));
+        if (e->smp_every <= 0) return GPE_OK;
+        monitor_drop_if_on_bound_points(e);
+        graph_drop(e);
+        sampler_clear(e);
+        e->ux = nullptr; e->uV = nullptr; e->n_pde = 0;
+        free_batch(e->main); free_batch(e->sym);
+        if (e->uxb && e->nb_user > 0) { int rc = setup_batch(e, e->bc, e->uxb, e->nb_user, 1, 0, false, nullptr); if (rc) return rc; }
+        e->nb_merged = 0;
+        e->acc_clean = false;
+        return GPE_OK;
+    }
+    const int dim = e->nd.dim;
+    if (e->cfg.potential == GPE_POT_PRECOMPUTED) FAIL(e, GPE_ERR_INVALID, "bind_sampler: a precomputed potential lives on fixed points");
+    if (precomputed_base(e)) FAIL(e, GPE_ERR_INVALID, "bind_sampler: a precomputed base lives on fixed points");
+    for (int k = 0; k < GPE_MAX_ORTH; ++k)
+        if (e->orth_host[k]) FAIL(e, GPE_ERR_INVALID, "bind_sampler: orthogonality array %d is bound, and lives on fixed points", k);
+    if (sp->every <= 0) FAIL(e, GPE_ERR_INVALID, "bind_sampler: every = %lld, need > 0", (long long)sp->every);
+    double cells = 1.0;
+    for (int k = 0; k < 3; ++k) {
+        if ((sp->shape[k] > 0) != (k < dim))
+            FAIL(e, GPE_ERR_INVALID, "bind_sampler: shape must use exactly the network's %d input axes (shape[%d] = %lld)", dim, k, (long long)sp->shape[k]);
+        if (k >= dim) continue;
+        if (sp->shape[k] > (1 << 24)) FAIL(e, GPE_ERR_INVALID, "bind_sampler: shape[%d] = %lld, at most 2^24 cells per axis", k, (long long)sp->shape[k]);
+        if (!(sp->hi[k] > sp->lo[k])) FAIL(e, GPE_ERR_INVALID, "bind_sampler: hi <= lo on axis %d", k);
+        if (!(sp->clip_hi[k] >= sp->clip_lo[k])) FAIL(e, GPE_ERR_INVALID, "bind_sampler: clip_hi < clip_lo on axis %d", k);
+        cells *= (double)sp->shape[k];
+    }
+    if (sp->first_cell < 0 || sp->n_local <= 0 || (double)sp->first_cell + (double)sp->n_local > cells)
+        FAIL(e, GPE_ERR_INVALID, "bind_sampler: cells [%lld, %lld + %lld) outside the grid's %.0f", (long long)sp->first_cell, (long long)sp->first_cell, (long long)sp->n_local, cells);
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    if (e->side) HIPCHK(e, hipStreamSynchronize(e->side));
+    if (e->smp_n != sp->n_local || !e->smp_x) {      // same size: the buffer (and a captured graph's pointers) stay
+        float* p = nullptr;
+        if (hipMalloc((void**)&p, (size_t)sp->n_local * dim * sizeof(float) + 256) != hipSuccess) {
+            (void)hipGetLastError();
+            FAIL(e, GPE_ERR_NOMEM, "bind_sampler: no memory for %lld points", (long long)sp->n_local);
+        }
+        sampler_clear(e);
+        e->smp_x = p;
+    }
+    SamplerGrid& g = e->smp_grid;
+    memset(&g, 0, sizeof g);
+    g.dim = dim; g.key0 = (uint32_t)sp->seed; g.key1 = (uint32_t)(sp->seed >> 32);
+    for (int k = 0; k < dim; ++k) {
+        g.shape[k] = sp->shape[k]; g.lo[k] = sp->lo[k]; g.clip_lo[k] = sp->clip_lo[k]; g.clip_hi[k] = sp->clip_hi[k];
+        g.h[k] = (float)(((double)sp->hi[k] - (double)sp->lo[k]) / (double)sp->shape[k]);
+    }
+    e->smp_n = sp->n_local; e->smp_first = sp->first_cell; e->smp_every = sp->every; e->smp_draw0 = sp->draw0; e->smp_steps = 0;
+    e->smp_held = sp->draw0;
+    if (e->mse_target) { e->mse_target = nullptr; free_batch(e->mse); }      // a pre-training target lived on the points that just went
+    int rc = bind_points_impl(e, e->smp_x, e->smp_n, nullptr);      // allocates the symmetry batch; its copy kernel reads a buffer ...
+    if (!rc) rc = sampler_launch(e, sp->draw0);                   // ... this launch fills, together with [x ; -x]
+    if (!rc && hipStreamSynchronize(e->stream) != hipSuccess) { e->err = "bind_sampler: synchronise failed"; rc = GPE_ERR_HIP; }
+    if (rc) {                                    // never leave a half-bound sampler behind
+        sampler_clear(e);
+        e->ux = nullptr; e->n_pde = 0; free_batch(e->main); free_batch(e->sym);
+    }
+    return rc;
+}
+
+int gpe_sampler_points(gpe_engine* e, const float** d_x, int64_t* n, int64_t* draw) {
+    if (!e) return GPE_ERR_INVALID;
+    if (e->smp_every <= 0) FAIL(e, GPE_ERR_STATE, "sampler_points: no sampler bound");
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    if (d_x) *d_x = e->smp_x;
+    if (n) *n = e->smp_n;
+    if (draw) *draw = e->smp_held;
+    return GPE_OK;
+}
+
 int gpe_bind_boundary(gpe_engine* e, const float* d_xb, int64_t n_b, const float* d_target) {
     if (!e) return GPE_ERR_INVALID;
     if (!d_xb || n_b <= 0) { e->uxb = nullptr; e->nb_user = 0; e->bc_target = nullptr; }
@@ -1956,6 +2076,7 @@ int gpe_bind_boundary(gpe_engine* e, const float* d_xb, int64_t n_b, const float
 
 int gpe_bind_orth(gpe_engine* e, int k, const float* d_psi) {
     if (!e || k < 0 || k >= GPE_MAX_ORTH) return GPE_ERR_INVALID;
+    if (d_psi && e->smp_every > 0) FAIL(e, GPE_ERR_STATE, "bind_orth: a sampler is bound, an orthogonality array would go stale at its next redraw");
     e->orth_host[k] = d_psi;
     HIPCHK(e, hipMemcpyAsync((void*)e->orth_dev, e->orth_host, sizeof e->orth_host, hipMemcpyHostToDevice, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));
@@ -2187,6 +2308,7 @@ int gpe_step_begin(gpe_engine* e) {
     int rc;
     e->fh_now = false; e->seedf_now = false; e->fu_done = false; e->fu_parts = false;      // per-step flags: a step that failed half-way must not leave them behind
     e->phase = 0;
+    if (e->smp_every > 0 && (rc = sampler_before_step(e))) return rc;
     if ((rc = launch_begin(e))) return rc;
     if ((rc = bc_fork(e, true))) return rc;
     const bool fh = head_in_forward(e);
@@ -2203,6 +2325,7 @@ int gpe_step_begin(gpe_engine* e) {
     }
     if (rc) { e->fh_now = false; return rc; }
     e->phase = 1;
+    if (e->smp_every > 0 && !e->capturing) e->smp_steps++;
     return GPE_OK;
 }
 
@@ -2324,6 +2447,7 @@ int gpe_step_update(gpe_engine* e) {
 int gpe_bind_target(gpe_engine* e, const float* d_target) {
     if (!e) return GPE_ERR_INVALID;
     if (e->main.n <= 0) FAIL(e, GPE_ERR_STATE, "bind_target before bind_points");
+    if (e->smp_every > 0) FAIL(e, GPE_ERR_STATE, "bind_target: a sampler is bound, a target array would go stale at its next redraw");
     e->mse_target = d_target;
     if (!d_target) { free_batch(e->mse); return GPE_OK; }
     return setup_batch(e, e->mse, e->ux, e->n_pde, 1, 0, false, nullptr);
@@ -2331,6 +2455,7 @@ int gpe_bind_target(gpe_engine* e, const float* d_target) {
 
 int gpe_mse_begin(gpe_engine* e) {
     if (!e) return GPE_ERR_INVALID;
+    if (e->smp_every > 0) FAIL(e, GPE_ERR_STATE, "mse step while a sampler is bound: the target lives on fixed points");
     if (!e->mse_target || e->mse.n <= 0) FAIL(e, GPE_ERR_STATE, "mse step before bind_target");
     int rc;
     e->fh_now = false; e->seedf_now = false;
@@ -2675,9 +2800,10 @@ static int graph_build(gpe_engine* e) {
     e->stream = e->cap_stream;
     e->packed_dirty = true;                       // the captured step always starts with k_begin
     e->acc_clean = false;
+    e->capturing = true;                          // a redraw is never recorded: a replay runs on whatever set the buffer holds
     hipGraph_t g = nullptr;
     int rc = GPE_OK;
-    if (hipStreamBeginCapture(e->cap_stream, hipStreamCaptureModeThreadLocal) != hipSuccess) { e->stream = s0; return GPE_ERR_HIP; }
+    if (hipStreamBeginCapture(e->cap_stream, hipStreamCaptureModeThreadLocal) != hipSuccess) { e->stream = s0; e->capturing = false; return GPE_ERR_HIP; }
     // graph_steps consecutive steps per graph: ONE hipGraphLaunch then enqueues all their kernels -- at the reference's batch sizes the
     // host's ~7 us per launch is as long as the kernels themselves (a one-step graph costs more per replay than it saves)
     for (int sidx = 0; sidx < e->graph_steps && !rc; ++sidx) {
@@ -2690,6 +2816,7 @@ static int graph_build(gpe_engine* e) {
     }
     hipError_t st = hipStreamEndCapture(e->cap_stream, &g);
     e->stream = s0;
+    e->capturing = false;
     e->phase = 0;
     e->packed_dirty = true;                       // nothing ran during capture
     e->acc_clean = false;
@@ -2710,9 +2837,16 @@ int gpe_run(gpe_engine* e, int64_t n_steps) {
         if (e->graph_exec) {
             int64_t done = 0;
             while (done + e->graph_steps <= n_steps) {
-                // a replay must not run past a monitor step: up to there with plain launches when fewer than a graph's steps are left to it
-                const int64_t room = e->mon_every > 0 ? e->mon_every - e->mon_steps % e->mon_every : e->graph_steps;
+                // a replay must not run past a monitor step, nor across a redraw of the sampler: up to there with plain launches when
+                // fewer than a graph's steps are left to it
+                int64_t room = e->mon_every > 0 ? e->mon_every - e->mon_steps % e->mon_every : e->graph_steps;
+                if (e->smp_every > 0) room = std::min(room, e->smp_every - e->smp_steps % e->smp_every);
                 if (room >= e->graph_steps) {
+                    if (e->smp_every > 0) {       // the redraw a replay may start with is enqueued here, outside the graph
+                        int rc = sampler_before_step(e);
+                        if (rc) return rc;
+                        e->smp_steps += e->graph_steps;
+                    }
                     HIPCHK(e, hipGraphLaunch(e->graph_exec, e->stream));
                     after_update(e);
                     e->phase = 0;

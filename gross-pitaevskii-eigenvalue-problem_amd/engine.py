@@ -119,6 +119,13 @@ class GPEConfig:
         return 1 + 2 * self.dim
 
 
+class _DeviceArrayView:
+    """A float32 device buffer the engine owns, described by the CUDA array interface so that torch can read it in place."""
+
+    def __init__(self, ptr: int, shape):
+        self.__cuda_array_interface__ = dict(shape=tuple(shape), typestr="<f4", data=(int(ptr), False), version=2, strides=None)
+
+
 def _check_dev_f32(t: torch.Tensor, name: str):
     if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
         raise ValueError(f"{name} must be a contiguous float32 tensor on the GPU")
@@ -321,6 +328,47 @@ class Engine:
         self._chk(self.lib.gpe_bind_points(self._h, C.c_void_p(x.data_ptr()), x.shape[0],
                                            C.c_void_p(Vt.data_ptr()) if Vt is not None else None))
         self.n_local = int(x.shape[0])
+
+    def bind_sampler(self, lo, hi, shape, every: int, seed: int = 0, first_cell: int = 0, n=None, draw0: int = 0, clip=None):
+        """Device-side stratified sampler: the engine owns the collocation batch -- one uniformly placed point per cell of the grid of
+        `shape` cells over [lo, hi], cells first_cell .. first_cell + n - 1 (n None: all of them) -- and redraws it in place every
+        `every` steps on its own stream (no host synchronisation, a captured graph stays valid).  clip = (clip_lo, clip_hi) keeps the
+        points inside a box narrower than the cells (default (lo, hi)).  sampler.stratified_points(lo, hi, shape, seed, draw, ...)
+        rebuilds any set on the CPU, bit for bit."""
+        from . import sampler
+        shp = [int(v) for v in np.atleast_1d(np.asarray(shape)).ravel()]
+        d = len(shp)
+        if not 1 <= d <= capi.GPE_MAX_DIM:
+            raise ValueError(f"shape: 1 to {capi.GPE_MAX_DIM} axes")
+        lo32, hi32 = sampler._per_axis(lo, d, "lo"), sampler._per_axis(hi, d, "hi")
+        clo, chi = (lo32, hi32) if clip is None else (sampler._per_axis(clip[0], d, "clip[0]"), sampler._per_axis(clip[1], d, "clip[1]"))
+        sp = capi.gpe_sampler_spec()          # what the engine cannot honour it refuses itself (GPE_ERR_INVALID): nothing is judged here
+        for k in range(d):
+            sp.shape[k] = shp[k]
+            sp.lo[k], sp.hi[k], sp.clip_lo[k], sp.clip_hi[k] = float(lo32[k]), float(hi32[k]), float(clo[k]), float(chi[k])
+        total = 1
+        for v in shp:
+            total *= v
+        sp.seed = int(seed) & (2 ** 64 - 1)
+        sp.first_cell = int(first_cell)
+        sp.n_local = total - int(first_cell) if n is None else int(n)
+        sp.draw0, sp.every = int(draw0), int(every)
+        self._chk(self.lib.gpe_bind_sampler(self._h, C.byref(sp)))
+        self._keep["x"], self._keep["V"] = None, None
+        self.n_local = int(sp.n_local)
+
+    def clear_sampler(self):
+        """Drop the sampler and its buffer: no points stay bound."""
+        self._chk(self.lib.gpe_bind_sampler(self._h, None))
+        self.n_local = 0
+
+    def sampler_points(self):
+        """(copy of the set the sampler holds now as a [n, dim] device tensor, its draw index); synchronises."""
+        p, n, d = C.c_void_p(), C.c_int64(), C.c_int64()
+        self._chk(self.lib.gpe_sampler_points(self._h, C.byref(p), C.byref(n), C.byref(d)))
+        view = _DeviceArrayView(p.value, (int(n.value), self.cfg.dim))      # the engine's buffer as a tensor, without owning it ...
+        out = torch.as_tensor(view, device=f"cuda:{self.device}").clone()    # ... and the copy the caller keeps
+        return out, int(d.value)
 
     def bind_boundary(self, xb, target=None):
         if xb is None:

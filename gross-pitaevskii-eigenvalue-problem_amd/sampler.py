@@ -1,0 +1,101 @@
+"""The engine's stratified collocation sets, restated in numpy (csrc/gpe_sampler.h, include/gpe_hip.h: gpe_bind_sampler).
+
+A set is a pure function of (seed, draw, cell): one uniformly placed point per cell of a regular grid, the random words from
+Philox4x32-10 with the cell and the draw as counter and the seed as key.  `stratified_points` gives, bit for bit, what
+`Engine.bind_sampler` holds on the device, so any training set of a run can be rebuilt on the CPU -- on any rank layout: cells are
+numbered row-major (last axis fastest, the order of ``np.meshgrid(..., indexing="ij")`` ravelled) and a rank's batch is a contiguous
+block of them.
+
+The coordinate arithmetic is pinned: u = float32(r >> 8) * 2^-24 (exact), t = float32(i) + u (one rounded fp32 add),
+x = lo + t * h (one rounded fp32 multiply, one rounded fp32 add -- never an fma), h = float32((double(hi) - double(lo)) / cells),
+then the clip box by comparisons.  numpy's float32 array arithmetic rounds after every operation, which is exactly that.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+PHILOX_M0, PHILOX_M1 = 0xD2511F53, 0xCD9E8D57
+PHILOX_W0, PHILOX_W1 = 0x9E3779B9, 0xBB67AE85
+_MASK = np.uint64(0xFFFFFFFF)
+_S32 = np.uint64(32)
+
+
+def philox4x32(counter, key, rounds: int = 10) -> np.ndarray:
+    """Philox4x32-10 (Salmon et al., SC'11).  counter [..., 4], key [..., 2] (uint32 words, broadcast against each other) -> the four
+    output words [..., 4] as uint32."""
+    c = np.asarray(counter, dtype=np.uint64) & _MASK
+    k = np.asarray(key, dtype=np.uint64) & _MASK
+    if c.shape[-1] != 4 or k.shape[-1] != 2:
+        raise ValueError("philox4x32: counter is [..., 4] words, key [..., 2]")
+    lead = np.broadcast_shapes(c.shape[:-1], k.shape[:-1])
+    c0, c1, c2, c3 = (np.broadcast_to(c[..., i], lead).copy() for i in range(4))
+    k0, k1 = (np.broadcast_to(k[..., i], lead).copy() for i in range(2))
+    m0, m1 = np.uint64(PHILOX_M0), np.uint64(PHILOX_M1)
+    w0, w1 = np.uint64(PHILOX_W0), np.uint64(PHILOX_W1)
+    for _ in range(rounds):
+        p0, p1 = m0 * c0, m1 * c2                       # 32 x 32 -> 64 bits: no overflow in uint64
+        c0, c1, c2, c3 = (p1 >> _S32) ^ c1 ^ k0, p1 & _MASK, (p0 >> _S32) ^ c3 ^ k1, p0 & _MASK
+        k0, k1 = (k0 + w0) & _MASK, (k1 + w1) & _MASK
+    return np.stack([c0, c1, c2, c3], axis=-1).astype(np.uint32)
+
+
+def _per_axis(v, d, name):
+    a = np.asarray(v, dtype=np.float32).ravel()
+    if a.size == 1:
+        a = np.repeat(a, d)
+    if a.size != d:
+        raise ValueError(f"{name}: one value or one per axis ({d})")
+    return a
+
+
+def grid_spec(lo, hi, shape, clip=None):
+    """(shape int64 [d], lo, hi, h, clip_lo, clip_hi as float32 [d]) -- the numbers the engine's kernel is given."""
+    shape = np.atleast_1d(np.asarray(shape, dtype=np.int64))
+    d = shape.size
+    if not 1 <= d <= 3 or np.any(shape <= 0) or np.any(shape > 1 << 24):
+        raise ValueError("shape: 1 to 3 axes of 1 .. 2^24 cells")
+    lo, hi = _per_axis(lo, d, "lo"), _per_axis(hi, d, "hi")
+    if np.any(hi <= lo):
+        raise ValueError("hi <= lo")
+    clo, chi = (lo, hi) if clip is None else (_per_axis(clip[0], d, "clip[0]"), _per_axis(clip[1], d, "clip[1]"))
+    if np.any(chi < clo):
+        raise ValueError("clip[1] < clip[0]")
+    h = ((hi.astype(np.float64) - lo.astype(np.float64)) / shape).astype(np.float32)
+    return shape, lo, hi, h, clo, chi
+
+
+def stratified_points(lo, hi, shape, seed, draw, first_cell: int = 0, n=None, clip=None) -> np.ndarray:
+    """Draw `draw` of the stratified set with seed `seed`: rows are cells first_cell .. first_cell + n - 1 (n None: all cells) of the
+    grid of `shape` cells over [lo, hi]; clip = (clip_lo, clip_hi), default (lo, hi).  float32 [n, d]."""
+    shape, lo, hi, h, clo, chi = grid_spec(lo, hi, shape, clip)
+    d = shape.size
+    total = int(np.prod([int(s) for s in shape]))
+    first_cell = int(first_cell)
+    n = total - first_cell if n is None else int(n)
+    if first_cell < 0 or n <= 0 or first_cell + n > total:
+        raise ValueError(f"cells [{first_cell}, {first_cell + n}) outside the grid's {total}")
+    seed, draw = int(seed) & (2 ** 64 - 1), int(draw) & (2 ** 64 - 1)
+    cell = np.arange(first_cell, first_cell + n, dtype=np.uint64)
+    ctr = np.empty((n, 4), dtype=np.uint64)
+    ctr[:, 0], ctr[:, 1] = cell & _MASK, cell >> _S32
+    ctr[:, 2], ctr[:, 3] = draw & 0xFFFFFFFF, draw >> 32
+    r = philox4x32(ctr, np.array([seed & 0xFFFFFFFF, seed >> 32], dtype=np.uint64))
+    idx = np.unravel_index(cell.astype(np.int64), tuple(int(s) for s in shape))          # row-major: last axis fastest
+    x = np.empty((n, d), dtype=np.float32)
+    for k in range(d):
+        u = (r[:, k] >> np.uint32(8)).astype(np.float32) * np.float32(2.0 ** -24)
+        t = idx[k].astype(np.float32) + u
+        xk = lo[k] + t * h[k]
+        xk = np.where(xk < clo[k], clo[k], xk)
+        xk = np.where(xk > chi[k], chi[k], xk)
+        x[:, k] = xk
+    return x
+
+
+def node_centred(half, n_nodes):
+    """(lo, hi, clip) whose cells are centred on the n_nodes nodes of the endpoint grid linspace(-half, half, n_nodes) per axis, with
+    the physical box as clip box: what tools/accuracy_nd.py and tools/accuracy_cfg4.py train on."""
+    half = np.atleast_1d(np.asarray(half, dtype=np.float64))
+    n_nodes = np.atleast_1d(np.asarray(n_nodes, dtype=np.int64))
+    hh = 2.0 * half / (n_nodes - 1)
+    return -half - hh / 2, half + hh / 2, (-half, half)

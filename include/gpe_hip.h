@@ -216,6 +216,41 @@ int gpe_bind_orth(gpe_engine* e, int k, const float* d_psi_k /* [n_local] or NUL
  * base: fold phi(x_b) into the boundary target. */
 int gpe_bind_base(gpe_engine* e, const float* d_phi, const float* d_phi1, const float* d_phi2);
 
+/* ---- device-side stratified collocation sampler --------------------------------------------------------------------------------
+ * One uniformly placed point per cell of a regular grid, re-drawn in place every `every` steps by a kernel on the engine's stream:
+ * no host synchronisation, no pointer change (a captured graph stays valid), and any set is a pure function of (seed, draw, cell).
+ * Replaces the host loop of tools/accuracy_nd.py:run_epochs (16 jittered numpy copies of the grid, uploaded and cycled through
+ * gpe_bind_points); the reference has no counterpart: it trains on one fixed grid.
+ *   grid   axis k has shape[k] cells over [lo[k], hi[k]], h[k] = float((double(hi[k]) - double(lo[k])) / shape[k]); axes beyond the
+ *          network's input dimension have shape 0.  Cells are numbered row-major, last axis fastest (np.meshgrid(indexing="ij")
+ *          ravelled); row j of the local batch is cell first_cell + j, so ranks holding contiguous blocks hold the world-1 set.
+ *   words  Philox4x32-10, counter (cell & 0xffffffff, cell >> 32, draw & 0xffffffff, draw >> 32), key (seed & 0xffffffff, seed >> 32),
+ *          one call per point, output word k for axis k.
+ *   point  u = float(r >> 8) * 2^-24;  t = float(i_k) + u;  x = lo[k] + t * h[k] (one rounded fp32 multiply, one rounded fp32 add,
+ *          never an fma);  x = min(max(x, clip_lo[k]), clip_hi[k]).  gpe_pinn/sampler.py restates this in numpy, bit for bit.
+ *   when   draw0 at the bind; enqueued steps s (counted on the host since the bind, as the monitor counts) with
+ *          m * every <= s < (m + 1) * every run on draw draw0 + m; the redraw is enqueued before the first kernel of step m * every. */
+typedef struct gpe_sampler_spec {
+    int64_t shape[3];
+    float lo[3], hi[3], clip_lo[3], clip_hi[3];
+    uint64_t seed;
+    int64_t first_cell, n_local, draw0, every;
+} gpe_sampler_spec;
+size_t gpe_sizeof_sampler_spec(void);   /* sizeof(gpe_sampler_spec) */
+/* Allocates the engine-owned point buffer [n_local, dim], draws draw0 into it and binds it as the collocation batch with no potential
+ * array (and the [x ; -x] symmetry batch when w_sym != 0, refreshed by every redraw).  Every step entry point honours the sampler:
+ * gpe_step, gpe_run (which cuts its graph replays at redraw steps), gpe_step_dp, gpe_run_dp and the three-phase gpe_step_begin.
+ * spec == NULL clears the sampler and leaves no points bound.  GPE_ERR_INVALID: GPE_POT_PRECOMPUTED or GPE_BASE_PRECOMPUTED (their arrays
+ * would be stale), an orthogonality array bound, every <= 0, hi <= lo or clip_hi < clip_lo on a used axis, first_cell + n_local beyond
+ * the product of shape, axes used other than the network's input dimension.  While a sampler is bound gpe_bind_orth with an array,
+ * gpe_bind_target and the gpe_mse_* entry points return GPE_ERR_STATE (their arrays live on fixed points); gpe_bind_points clears
+ * the sampler and the caller's points take over.
+ * Replaces: the host loop of tools/accuracy_nd.py:run_epochs (no reference counterpart). */
+int gpe_bind_sampler(gpe_engine* e, const gpe_sampler_spec* spec);
+/* synchronise; the engine-owned buffer d_x [n, dim], and the draw index of the set it holds now.  Any of the three may be NULL.
+ * Replaces: reading back the bound set in tools/accuracy_nd.py:run_epochs (the host there built it; no reference counterpart). */
+int gpe_sampler_points(gpe_engine* e, const float** d_x, int64_t* n, int64_t* draw);
+
 /* ---- forward-only entry points ---------------------------------------------------------------- */
 /* model.forward(x) (refine/...:121-125): d_out [n, out] row-major */
 int gpe_forward(gpe_engine* e, const float* d_x, int64_t n, float* d_out);

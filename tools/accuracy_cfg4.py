@@ -37,6 +37,8 @@ ap.add_argument("--w-pde", type=float, default=1.0)
 ap.add_argument("--train-lr", type=float, default=3e-4, help="learning rate of the training phase (0: --lr)")
 ap.add_argument("--resample", type=int, default=100, help="epochs between changes of the collocation set (0: the fixed grid throughout)")
 ap.add_argument("--sets", type=int, default=16, help="number of jittered collocation sets cycled through")
+ap.add_argument("--device-sampler", action="store_true", help="with --resample: the engine's own sampler (Engine.bind_sampler) draws a fresh stratified set on "
+                "the device every --resample epochs, instead of cycling through --sets sets built here")
 ap.add_argument("--no-basin", action="store_true", help="skip the second solver run (started from the trained network state)")
 ap.add_argument("--solver-n", type=int, default=192)
 ap.add_argument("--seed", type=int, default=0)
@@ -152,18 +154,25 @@ rows = []
 rng = np.random.default_rng(a.seed + 1)
 cells = np.stack([m.ravel() for m in np.meshgrid(ax, ax, indexing="ij")], axis=1)
 sets = [xd]
-for _ in range(a.sets - 1 if a.resample > 0 else 0):
+device_sampler = a.device_sampler and a.resample > 0
+for _ in range(a.sets - 1 if a.resample > 0 and not device_sampler else 0):
     sets.append(torch.as_tensor((cells + rng.uniform(-0.5 * h, 0.5 * h, cells.shape)).astype(np.float32), device="cuda"))
 if a.monitor > 0:
     eng.bind_monitor(xd, every=a.monitor, dv=dv, capacity=max(1, a.epochs // a.monitor + 1))
     sets = sets[1:] if len(sets) > 1 else sets          # ... which the optimiser then never sees: training on the jittered sets only
+if device_sampler:
+    # cells centred on the grid nodes (the quadrature weight stays the cell area), points kept inside the physical box; the regular grid
+    # stays the monitor's and is bound again below for the reported numbers
+    from gpe_pinn.sampler import node_centred
+    s_lo, s_hi, s_clip = node_centred([half, half], [n, n])
+    eng.bind_sampler(s_lo, s_hi, (n, n), every=a.resample, seed=a.seed + 1, clip=s_clip)
 epoch_ctr = 0
 for frac, lr in ((0.35, tlr), (0.2, tlr * 0.3), (0.15, tlr * 0.1), (0.1, tlr * 0.03), (0.1, tlr * 0.01), (0.05, tlr * 0.003), (0.05, tlr * 0.001)):
     eng.set_lr(lr)
     left = int(a.epochs * frac)
     while left > 0:
         k = min(left, 10000)
-        if a.resample > 0:
+        if a.resample > 0 and not device_sampler:
             done = 0
             while done < k:
                 eng.bind_points(sets[(epoch_ctr // a.resample) % len(sets)])
@@ -246,7 +255,8 @@ out = dict(case="cfg4_2d_rot", workload="cfg4_2d_6x128_rot", layers=layers, poin
            solver=f"oracle/gp_rotating_2d.py, {a.solver_n}^2 Fourier grid on [-12,12)^2, same seed",
            E_abs_err=abs(s1["E"] - ref["E"]), mu_abs_err=abs(s1["mu"] - ref["mu"]), density_rel_l2=rel_l2, final_pde_loss=sc["pde"],
            basin=basin, monitor=dict(every=a.monitor, grid="the regular training grid", records=monitor_rows), density_rel_l2_best_rotation=rel_l2_rot, rotation_angle=theta_rot,
-           schedule=dict(lr=a.lr, train_lr=tlr, resample_every=a.resample, collocation_sets=len(sets), w_norm=a.w_norm, w_bc=a.w_bc, w_pde=a.w_pde, w_riesz=a.w_riesz, ladder="(0.35, 0.2, 0.15, 0.1, 0.1, 0.05, 0.05) of the epochs at lr x (1, .3, .1, .03, .01, .003, .001)"))
+           schedule=dict(lr=a.lr, train_lr=tlr, resample_every=a.resample, collocation_sets=len(sets),
+                         sampler=("device" if device_sampler else "host_cycle") if a.resample > 0 else "fixed_grid", w_norm=a.w_norm, w_bc=a.w_bc, w_pde=a.w_pde, w_riesz=a.w_riesz, ladder="(0.35, 0.2, 0.15, 0.1, 0.1, 0.05, 0.05) of the epochs at lr x (1, .3, .1, .03, .01, .003, .001)"))
 path = a.out or os.path.join(ROOT, "gpurun_out", "accuracy_cfg4_2d_6x128_rot.json")
 os.makedirs(os.path.dirname(path), exist_ok=True)
 json.dump(out, open(path, "w"), indent=1)

@@ -39,6 +39,8 @@ ap.add_argument("--resample", type=int, default=0, help="epochs between changes 
                                                        "cell, quadrature weight = the cell volume (0: the fixed grid throughout).  On one fixed grid a long run fits the "
                                                        "residual AT the points and grows structure between them (cfg5 at 40^3: mu 13.018 on the grid, 26.2 on a finer one)")
 ap.add_argument("--sets", type=int, default=16, help="number of jittered collocation sets cycled through")
+ap.add_argument("--device-sampler", action="store_true", help="with --resample: the engine's own sampler (Engine.bind_sampler) draws a fresh stratified set on "
+                                                             "the device every --resample epochs, instead of cycling through --sets sets built here")
 ap.add_argument("--big-grid", default="", help="e.g. 64,128,64: after the schedule, continue on THIS grid (BASELINE's per-GPU size) for --big-epochs epochs "
                                                "at the low end of the learning-rate ladder, and evaluate mu there (same weights, fresh Adam)")
 ap.add_argument("--big-epochs", type=int, default=3000)
@@ -82,7 +84,8 @@ eng.bind_points(xd)
 eng.bind_boundary(torch.as_tensor(xb, device="cuda"))
 # stratified collocation sets (--resample): the grid point moved uniformly inside its cell; the first and last cells of an axis stay inside the box
 xsets = [xd]
-if a.resample > 0:
+device_sampler = a.device_sampler and a.resample > 0
+if a.resample > 0 and not device_sampler:
     rng = np.random.default_rng(1234 + a.seed)
     for _ in range(a.sets):
         J = X.astype(np.float64) + rng.uniform(-0.5 * h, 0.5 * h, X.shape)
@@ -92,7 +95,7 @@ _set_i = [0]
 
 def run_epochs(n_ep):
     """eng.run(n_ep), changing the collocation set every --resample epochs (bind_points is a pointer swap)"""
-    if a.resample <= 0:
+    if a.resample <= 0 or device_sampler:       # (the device sampler redraws inside eng.run, with no host synchronisation)
         eng.run(n_ep)
         return
     left = n_ep
@@ -118,6 +121,11 @@ for i in range(a.pretrain):
     elif i % 500 == 0:
         print(f"pretrain {i}: mse {sc['loss']:.3e}", flush=True)
 eng.bind_target(None)
+if device_sampler:
+    # cells centred on the grid nodes (so the quadrature weight stays the cell volume dv), points kept inside the physical box
+    from gpe_pinn.sampler import node_centred
+    s_lo, s_hi, s_clip = node_centred([half] * d, [n] * d)
+    eng.bind_sampler(s_lo, s_hi, (n,) * d, every=a.resample, seed=1234 + a.seed, clip=s_clip)
 # ---- gamma continuation ----
 gam = [cs["g"] * (k / a.stages) ** 2 for k in range(a.stages + 1)]            # quadratic ramp: small steps where the state changes fastest
 rows = []
@@ -213,6 +221,7 @@ out = dict(case=a.case, workload=cs["workload"], layers=cs["layers"], points=int
            density_rel_l2=float(np.sqrt(((dens - dref) ** 2).sum() / (dref ** 2).sum())),
            schedule=dict(pretrain=a.pretrain, epochs=a.epochs, final=a.final, stages=a.stages, lr=a.lr, w_norm=a.w_norm, w_bc=a.w_bc,
                          w_riesz=a.w_riesz, w_norm_final=a.w_norm_final, resample=a.resample, sets=a.sets,
+                         sampler=("device" if device_sampler else "host_cycle") if a.resample > 0 else "fixed_grid",
                          scheduler="constant lr per stage, fresh Adam per stage; last stage lr x (1, 0.3, 0.1, 0.03, 0.01, 0.003, 0.001)"),
            energy=rows[-1]["riesz"], energy_ref=truth["energy"], big_grid=big,
            observables={k: _obs[k] for k in ("norm", "kin", "pot", "inter", "energy", "mu", "mu_lap", "var_x", "peak_density", "res_rms")})
