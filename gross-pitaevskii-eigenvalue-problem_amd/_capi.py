@@ -111,6 +111,8 @@ SYMBOLS = {
     "gpe_sampler_points": (_int, [_vp, _P(_vp), _P(_i64), _P(_i64)]),
     "gpe_bind_boundary": (_int, [_vp, _vp, _i64, _vp]),
     "gpe_bind_orth": (_int, [_vp, _int, _vp]),
+    "gpe_bind_orth_state": (_int, [_vp, _int, _vp, C.c_size_t, _int, _f, _f]),
+    "gpe_orth_values": (_int, [_vp, _int, _P(_vp), _P(_i64)]),
     "gpe_bind_base": (_int, [_vp, _vp, _vp, _vp]),
     "gpe_forward": (_int, [_vp, _vp, _i64, _vp]),
     "gpe_forward_jets": (_int, [_vp, _vp, _i64, _vp]),

@@ -464,6 +464,20 @@ struct Batch {
     std::vector<void*> allocs;
 };
 
+// the parameter set a forward pass evaluates, with its packed copies (fused path): the trained one, or a frozen orthogonality state's
+struct FwdWeights { const float* theta; const float* Wpk; const float* WpkT; };
+
+// frozen reference state of an orthogonality slot (gpe_bind_orth_state): a parameter set of the engine's own network, in the engine's
+// (padded) layout, with its packed copies, and psi_k on the collocation set bound now -- orth_host[k] points at psi
+struct OrthState {
+    bool on = false;
+    float *theta = nullptr, *Wpk = nullptr, *WpkT = nullptr;
+    float* psi = nullptr;          // [n]
+    int64_t n = 0;
+    int base_mode = -1;
+    float perturb_scale = 1.f, amplitude = 1.f, base_norm = 1.f;
+};
+
 struct gpe_engine {
     gpe_config cfg;
     NetDesc nd;
@@ -554,6 +568,8 @@ struct gpe_engine {
     const float** orth_dev = nullptr;
     const float* orth_host[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // [4..6]: precomputed base
     Batch main, bc, sym, aux, mse;
+    OrthState ost[GPE_MAX_ORTH];   // frozen states: evaluated by the engine on every set it holds (orth_refill)
+    Batch orb;                     // ... through this value-only forward batch on the collocation points, sized at the binds
     const float* bc_target = nullptr;
     // what the caller bound: collocation points / potential, boundary points.  When the boundary batch is small it is MERGED:
     // appended to the collocation batch (main.pts.b) and handled by the same launches; e->bc stays empty then.
@@ -760,8 +776,8 @@ static bool head_fusable_tile(gpe_engine* e) {
 static bool head_fusable(gpe_engine* e) { return head_fusable_coop(e) || head_fusable_tile(e); }
 static bool head_in_forward(gpe_engine* e) { return e->fuse_head && e->fh_want && head_fusable(e); }
 template <int HH, int CC, int EE, int NO>
-static void launch_fcoop_no(gpe_engine* e, Batch& b, unsigned grid, size_t lds, int store) {
-#define CARGS e->nd, e->theta, e->Wpk, b.pts, b.stored, b.O, b.n, b.ld, store
+static void launch_fcoop_no(gpe_engine* e, Batch& b, unsigned grid, size_t lds, int store, const FwdWeights& W) {
+#define CARGS e->nd, W.theta, W.Wpk, b.pts, b.stored, b.O, b.n, b.ld, store
     if constexpr (HH <= 64 && NO == 1 && CC >= 3) {
         if (e->fh_now && &b == &e->main) {
             const HeadArgs ha{e->ph, e->base_norm, b.V, (const float* const*)e->orth_dev, e->bc_target, b.u, b.Hu, b.Ob, e->n_pde, b.ld, e->head_slots};
@@ -783,7 +799,7 @@ static void launch_fcoop_no(gpe_engine* e, Batch& b, unsigned grid, size_t lds, 
     }
 #undef CARGS
     const HeadArgs nohead{};
-#define CARGS e->nd, e->theta, e->Wpk, b.pts, b.stored, b.O, b.n, b.ld, store, nohead
+#define CARGS e->nd, W.theta, W.Wpk, b.pts, b.stored, b.O, b.n, b.ld, store, nohead
     if constexpr (HH <= 64 && NO == 1) {
         if (e->cfg.net_kind == GPE_NET_RESIDUAL) {        // one or two residual blocks (checked at gpe_create)
             if (e->nd.n_lin - 2 == 2) hipLaunchKernelGGL((f_forward_coop<HH, CC, EE, 1, 2, false, true>), dim3(grid), dim3(HH * 4), lds, e->stream, CARGS);
@@ -807,17 +823,17 @@ static void launch_fcoop_no(gpe_engine* e, Batch& b, unsigned grid, size_t lds, 
 #undef CARGS
 }
 template <int HH, int CC, int EE>
-static void launch_f_forward(gpe_engine* e, Batch& b, unsigned grid, int store) {
+static void launch_f_forward(gpe_engine* e, Batch& b, unsigned grid, int store, const FwdWeights& W) {
     if constexpr (HH <= 64 || (HH == 128 && CC <= 4)) {
         if (fwd_coop(e, b)) {
             const int NT = HH / 16;
             const size_t lds = fused_small_bytes(e) + ((size_t)2 * CC * NT * 256 + (size_t)NT * e->nd.n_out * CC * 16) * sizeof(float);
             const unsigned g = fused_grid(e, b.n, 1, HH == 128 ? 1 : 2);
 #ifdef GPE_FAST_BUILD
-            launch_fcoop_no<HH, CC, EE, 1>(e, b, g, lds, store);
+            launch_fcoop_no<HH, CC, EE, 1>(e, b, g, lds, store, W);
 #else
-            if (e->nd.n_out == 1) launch_fcoop_no<HH, CC, EE, 1>(e, b, g, lds, store);
-            else launch_fcoop_no<HH, CC, EE, 2>(e, b, g, lds, store);
+            if (e->nd.n_out == 1) launch_fcoop_no<HH, CC, EE, 1>(e, b, g, lds, store, W);
+            else launch_fcoop_no<HH, CC, EE, 2>(e, b, g, lds, store, W);
 #endif
             return;
         }
@@ -826,7 +842,7 @@ static void launch_f_forward(gpe_engine* e, Batch& b, unsigned grid, int store) 
     const int fshare = (e->fwd_share > 0 && grid == (unsigned)(2 * e->num_cu) && (b.n + 15) / 16 >= 4 * e->share_min_tiles * (int64_t)grid) ? e->fwd_share : 0;
     const HeadArgs nohead{};
     if constexpr (HH > 64) {
-        F_LAUNCH(f_forward, HH, CC, EE, false, grid, 256, fused_fwd_lds(e, false), e->nd, e->theta, e->Wpk, b.pts, b.stored, b.O, b.n, b.ld, store, fshare, nohead);
+        F_LAUNCH(f_forward, HH, CC, EE, false, grid, 256, fused_fwd_lds(e, false), e->nd, W.theta, W.Wpk, b.pts, b.stored, b.O, b.n, b.ld, store, fshare, nohead);
         return;
     }
     if constexpr (HH <= 64) {
@@ -835,7 +851,7 @@ static void launch_f_forward(gpe_engine* e, Batch& b, unsigned grid, int store) 
             const size_t w6 = (size_t)(e->nd.n_lin - 2) * HH * HH * 6;
             const bool wl = 2 * (fused_small_bytes(e) + w6) <= (size_t)160 * 1024;
             const size_t lds6 = fused_small_bytes(e) + (wl ? w6 : 0);
-#define B6ARGS e->nd, e->theta, e->WpkT, b.pts, b.stored, b.O, b.n, b.ld, store
+#define B6ARGS e->nd, W.theta, W.WpkT, b.pts, b.stored, b.O, b.n, b.ld, store
 #ifdef GPE_FAST_BUILD
             if (wl) hipLaunchKernelGGL((f_forward_b6<HH, CC, EE, 1, true>), dim3(grid), dim3(256), lds6, e->stream, B6ARGS);
             else hipLaunchKernelGGL((f_forward_b6<HH, CC, EE, 1, false>), dim3(grid), dim3(256), lds6, e->stream, B6ARGS);
@@ -856,18 +872,18 @@ static void launch_f_forward(gpe_engine* e, Batch& b, unsigned grid, int store) 
         if (e->fh_now && &b == &e->main && e->nd.n_out == 1) {     // whole step, large batch: the head rides in this kernel
             const HeadArgs ha{e->ph, e->base_norm, b.V, (const float* const*)e->orth_dev, e->bc_target, b.u, b.Hu, b.Ob, e->n_pde, b.ld, e->head_slots};
             if (e->fwd_wlds && staged_batch(e, b))
-                hipLaunchKernelGGL((f_forward<HH, CC, EE, 1, true, true>), dim3(grid), dim3(256), fused_fwd_lds(e, true), e->stream, e->nd, e->theta, e->Wpk,
+                hipLaunchKernelGGL((f_forward<HH, CC, EE, 1, true, true>), dim3(grid), dim3(256), fused_fwd_lds(e, true), e->stream, e->nd, W.theta, W.Wpk,
                                    b.pts, b.stored, b.O, b.n, b.ld, store, fshare, ha);
             else
-                hipLaunchKernelGGL((f_forward<HH, CC, EE, 1, false, true>), dim3(grid), dim3(256), fused_fwd_lds(e, false), e->stream, e->nd, e->theta, e->Wpk,
+                hipLaunchKernelGGL((f_forward<HH, CC, EE, 1, false, true>), dim3(grid), dim3(256), fused_fwd_lds(e, false), e->stream, e->nd, W.theta, W.Wpk,
                                    b.pts, b.stored, b.O, b.n, b.ld, store, fshare, ha);
             return;
         }
     }
     if (e->fwd_wlds && staged_batch(e, b))
-        F_LAUNCH(f_forward, HH, CC, EE, true, grid, 256, fused_fwd_lds(e, true), e->nd, e->theta, e->Wpk, b.pts, b.stored, b.O, b.n, b.ld, store, fshare, nohead);
+        F_LAUNCH(f_forward, HH, CC, EE, true, grid, 256, fused_fwd_lds(e, true), e->nd, W.theta, W.Wpk, b.pts, b.stored, b.O, b.n, b.ld, store, fshare, nohead);
     else
-        F_LAUNCH(f_forward, HH, CC, EE, false, grid, 256, fused_fwd_lds(e, false), e->nd, e->theta, e->Wpk, b.pts, b.stored, b.O, b.n, b.ld, store, fshare, nohead);
+        F_LAUNCH(f_forward, HH, CC, EE, false, grid, 256, fused_fwd_lds(e, false), e->nd, W.theta, W.Wpk, b.pts, b.stored, b.O, b.n, b.ld, store, fshare, nohead);
 }
 // reverse-kernel variant for one batch: 3 = cooperative (a workgroup per tile, a wave per 16-feature slice),
 // 2 = weight gradients in registers (1 wave/SIMD),
@@ -1099,16 +1115,20 @@ static WideCall wide_call(gpe_engine* e, Batch& b) {
     return a;
 }
 
-static int mlp_forward(gpe_engine* e, Batch& b, bool store) {
+// frozen: the parameter set of a frozen orthogonality state instead of the trained one (its packed copies never go stale)
+static int mlp_forward(gpe_engine* e, Batch& b, bool store, const FwdWeights* frozen = nullptr) {
     if (b.n <= 0) return GPE_OK;
     const bool mark = e->prof && (&b == &e->main);
+    const FwdWeights W = frozen ? *frozen : FwdWeights{e->theta, e->Wpk, e->WpkT};
     if (e->path == GPE_PATH_FUSED) {
-        int rc = ensure_packed(e);
+        int rc = frozen ? GPE_OK : ensure_packed(e);
         if (rc) return rc;
         unsigned grid = fused_grid(e, b.n, 4, e->fwd_wg_per_cu);
         if (mark) prof_mark(e, 0, true);
         if (e->wide_fwd) {
-            const int wr = wide_forward(wide_call(e, b), store ? 1 : 0);
+            WideCall wc = wide_call(e, b);
+            wc.theta = W.theta; wc.Wpk = W.Wpk; wc.WpkT = W.WpkT;
+            const int wr = wide_forward(wc, store ? 1 : 0);
             if (wr < 0) FAIL(e, GPE_ERR_INVALID, "wide kernel set: channels (%d,%d) / n_out %d not compiled", b.C, b.E, e->nd.n_out);
             if (wr) FAIL(e, GPE_ERR_HIP, "w_forward launch: %s", hipGetErrorString((hipError_t)wr));
             if (mark) prof_mark(e, 0, false);
@@ -1116,20 +1136,20 @@ static int mlp_forward(gpe_engine* e, Batch& b, bool store) {
         }
 #ifdef GPE_FAST_BUILD
         if (e->H != 64 || e->nd.n_out != 1) FAIL(e, GPE_ERR_INVALID, "fast build: only H = 64, n_out = 1 compiled");
-        DISPATCH_FWD(b, launch_f_forward<64, CC, EE>(e, b, grid, store ? 1 : 0));
+        DISPATCH_FWD(b, launch_f_forward<64, CC, EE>(e, b, grid, store ? 1 : 0, W));
 #else
         if (e->H == 128) {      // wide layers: one wave per SIMD, C <= 5 (checked at create)
             grid = fused_grid(e, b.n, 4, 1);
             switch (b.C * 10 + b.E) {     // wide layers: dim <= 2 (checked at create)
-                case 10: launch_f_forward<128, 1, 0>(e, b, grid, store ? 1 : 0); break;
-                case 31: launch_f_forward<128, 3, 1>(e, b, grid, store ? 1 : 0); break;
-                case 41: launch_f_forward<128, 4, 1>(e, b, grid, store ? 1 : 0); break;
-                case 52: launch_f_forward<128, 5, 2>(e, b, grid, store ? 1 : 0); break;
+                case 10: launch_f_forward<128, 1, 0>(e, b, grid, store ? 1 : 0, W); break;
+                case 31: launch_f_forward<128, 3, 1>(e, b, grid, store ? 1 : 0, W); break;
+                case 41: launch_f_forward<128, 4, 1>(e, b, grid, store ? 1 : 0, W); break;
+                case 52: launch_f_forward<128, 5, 2>(e, b, grid, store ? 1 : 0, W); break;
                 default: FAIL(e, GPE_ERR_INVALID, "bad channel pair (%d,%d) for H = 128", b.C, b.E);
             }
         }
-        else if (e->H == 64) { DISPATCH_FWD(b, launch_f_forward<64, CC, EE>(e, b, grid, store ? 1 : 0)); }
-        else            { DISPATCH_FWD(b, launch_f_forward<32, CC, EE>(e, b, grid, store ? 1 : 0)); }
+        else if (e->H == 64) { DISPATCH_FWD(b, launch_f_forward<64, CC, EE>(e, b, grid, store ? 1 : 0, W)); }
+        else            { DISPATCH_FWD(b, launch_f_forward<32, CC, EE>(e, b, grid, store ? 1 : 0, W)); }
 #endif
         if (mark) prof_mark(e, 0, false);
     } else {
@@ -1140,20 +1160,20 @@ static int mlp_forward(gpe_engine* e, Batch& b, bool store) {
             const float* Sskip = nd.skip[lin] >= 0 ? b.S[nd.skip[lin]] : nullptr;     // residual block: the VALU kernel adds the block input
             if (!Sskip && lin > 0 && nd.width[lin] % 64 == 0 && nd.width[lin + 1] % 256 == 0 && e->gen_mfma && e->gen_mfma2) {
                 dim3 grid(cdiv(b.n, 16), nd.width[lin + 1] / 256);      // a block = one point tile x 256 outputs, jets shared through LDS
-                DISPATCH_FWD(b, hipLaunchKernelGGL((g_fwd_layer_mfma2<CC, EE>), grid, dim3(256), 0, e->stream, nd, lin, e->theta,
+                DISPATCH_FWD(b, hipLaunchKernelGGL((g_fwd_layer_mfma2<CC, EE>), grid, dim3(256), 0, e->stream, nd, lin, W.theta,
                                                     Sprev, Out, b.n, b.ld));
             } else if (lin > 0 && nd.width[lin] % 64 == 0 && nd.width[lin + 1] % 64 == 0 && e->gen_mfma &&
                        (!Sskip || nd.width[nd.skip[lin] + 1] == nd.width[lin + 1])) {   // wide map: matrix cores (round 4: residual blocks too)
                 dim3 grid(cdiv(cdiv(b.n, 16), 4), nd.width[lin + 1] / 64);
-                DISPATCH_FWD(b, hipLaunchKernelGGL((g_fwd_layer_mfma<CC, EE>), grid, dim3(256), 0, e->stream, nd, lin, e->theta,
+                DISPATCH_FWD(b, hipLaunchKernelGGL((g_fwd_layer_mfma<CC, EE>), grid, dim3(256), 0, e->stream, nd, lin, W.theta,
                                                     Sprev, Out, b.n, b.ld, Sskip));
             } else if (nd.width[lin + 1] >= 64) {      // wide layer: 16 output features per thread
                 dim3 grid(cdiv(b.n, 256), cdiv(nd.width[lin + 1], G_FBW));
-                DISPATCH_FWD(b, hipLaunchKernelGGL((g_fwd_layer<CC, EE, G_FBW>), grid, dim3(256), 0, e->stream, nd, lin, e->theta,
+                DISPATCH_FWD(b, hipLaunchKernelGGL((g_fwd_layer<CC, EE, G_FBW>), grid, dim3(256), 0, e->stream, nd, lin, W.theta,
                                                     b.pts, Sprev, Out, b.n, b.ld, Sskip));
             } else {
                 dim3 grid(cdiv(b.n, 256), cdiv(nd.width[lin + 1], G_FB));
-                DISPATCH_FWD(b, hipLaunchKernelGGL((g_fwd_layer<CC, EE, G_FB>), grid, dim3(256), 0, e->stream, nd, lin, e->theta,
+                DISPATCH_FWD(b, hipLaunchKernelGGL((g_fwd_layer<CC, EE, G_FB>), grid, dim3(256), 0, e->stream, nd, lin, W.theta,
                                                     b.pts, Sprev, Out, b.n, b.ld, Sskip));
             }
         }
@@ -1794,6 +1814,11 @@ int gpe_create(const gpe_config* cfg, int device, void* hip_stream, gpe_engine**
 static void graph_drop(gpe_engine* e);
 int gpe_comm_destroy(gpe_engine* e);
 
+static void orth_state_free(OrthState& s) {      // the stream is idle, or hipFree waits for it
+    for (float* p : {s.theta, s.Wpk, s.WpkT, s.psi}) if (p) (void)hipFree(p);
+    s = OrthState();
+}
+
 void gpe_destroy(gpe_engine* e) {
     if (!e) return;
     (void)hipSetDevice(e->device);
@@ -1804,7 +1829,8 @@ void gpe_destroy(gpe_engine* e) {
     if (e->cap_stream) (void)hipStreamDestroy(e->cap_stream);
     if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
     if (e->ev_join) (void)hipEventDestroy(e->ev_join);
-    free_batch(e->main); free_batch(e->bc); free_batch(e->sym); free_batch(e->aux); free_batch(e->mse); free_batch(e->mon);
+    free_batch(e->main); free_batch(e->bc); free_batch(e->sym); free_batch(e->aux); free_batch(e->mse); free_batch(e->mon); free_batch(e->orb);
+    for (int k = 0; k < GPE_MAX_ORTH; ++k) orth_state_free(e->ost[k]);
     for (hipEvent_t ev : e->ev_pool) (void)hipEventDestroy(ev);
     if (e->ext_exchange) { e->grad = nullptr; e->dbl = nullptr; }
     void* ps[] = {e->theta, e->am, e->av, e->grad, e->dbl, e->od, e->hist, e->last, (void*)e->orth_dev, e->Wpk, e->WpkT, e->gslab, e->gslab_bc, e->grad_bc, (void*)e->upd_snap, (void*)e->head_slots, (void*)e->upd_ticket, (void*)e->upd_snap_small, (void*)e->obs_buf, (void*)e->obs_out, (void*)e->mon_ring, (void*)e->smp_x};
@@ -1820,10 +1846,10 @@ int gpe_synchronize(gpe_engine* e) {
 }
 
 // caller's flat vector (P_user entries, hidden widths as given) <-> the engine's (P entries, padded widths)
-static int flat_to_device(gpe_engine* e, float* d_dst, const float* h_user) {
+static int flat_to_device(gpe_engine* e, float* d_dst, const float* h_user, bool params = false) {
     if (e->umap.empty()) { HIPCHK(e, hipMemcpyAsync(d_dst, h_user, (size_t)e->P * 4, hipMemcpyHostToDevice, e->stream)); return GPE_OK; }
     std::vector<float> tmp((size_t)e->P, 0.f);
-    if (d_dst == e->theta) for (int i : e->pad_bias) tmp[i] = -40.f;         // (parameters only: the Adam moments of the padding are 0)
+    if (params) for (int i : e->pad_bias) tmp[i] = -40.f;         // (parameters only: the Adam moments of the padding are 0)
     for (int i = 0; i < e->P_user; ++i) tmp[e->umap[i]] = h_user[i];
     HIPCHK(e, hipMemcpyAsync(d_dst, tmp.data(), (size_t)e->P * 4, hipMemcpyHostToDevice, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));              // tmp dies with this frame
@@ -1841,7 +1867,7 @@ static int flat_from_device(gpe_engine* e, const float* d_src, float* h_user) {
 int gpe_set_params(gpe_engine* e, const float* h, size_t n) {
     if (!e || !h) return GPE_ERR_INVALID;
     if ((int64_t)n != e->P_user) FAIL(e, GPE_ERR_INVALID, "set_params: got %zu floats, model has %d", n, e->P_user);
-    int rc = flat_to_device(e, e->theta, h);
+    int rc = flat_to_device(e, e->theta, h, /*params=*/true);
     if (rc) return rc;
     HIPCHK(e, hipStreamSynchronize(e->stream));
     e->packed_dirty = true;
@@ -1919,6 +1945,8 @@ static int rebuild_main(gpe_engine* e) {
 
 static void sampler_clear(gpe_engine* e);
 static bool precomputed_base(const gpe_engine* e);
+static int orth_resize(gpe_engine* e);
+static int orth_refill(gpe_engine* e);
 
 // the bind itself, shared by gpe_bind_points (caller's points) and gpe_bind_sampler (the engine's own buffer)
 static int bind_points_impl(gpe_engine* e, const float* d_x, int64_t n_local, const float* d_V) {
@@ -1941,8 +1969,10 @@ static int bind_points_impl(gpe_engine* e, const float* d_x, int64_t n_local, co
                            e->sym.xown, n_local, e->nd.dim);
         HIPCHK(e, hipGetLastError());
     }
+    if ((rc = orth_resize(e))) return rc;
     fill_phys(e);
     e->acc_clean = false;
+    if (e->smp_every <= 0 && (rc = orth_refill(e))) return rc;      // (a sampler's set does not exist yet: sampler_launch fills behind its draw)
     HIPCHK(e, hipStreamSynchronize(e->stream));
     return GPE_OK;
 }
@@ -1969,7 +1999,7 @@ static int sampler_launch(gpe_engine* e, int64_t draw) {
                        e->smp_n, (uint64_t)draw, e->smp_x, xs);
     HIPCHK(e, hipGetLastError());
     e->smp_held = draw;
-    return GPE_OK;
+    return orth_refill(e);                       // frozen orthogonality states: psi_k of the new set, before the step's first kernel
 }
 
 // before the first kernel of a step: the set this step runs on.  A redraw leaves the engine as gpe_bind_points of the new set would
@@ -2002,8 +2032,8 @@ int gpe_bind_sampler(gpe_engine* e, const gpe_sampler_spec* sp) {
     const int dim = e->nd.dim;
     if (e->cfg.potential == GPE_POT_PRECOMPUTED) FAIL(e, GPE_ERR_INVALID, "bind_sampler: a precomputed potential lives on fixed points");
     if (precomputed_base(e)) FAIL(e, GPE_ERR_INVALID, "bind_sampler: a precomputed base lives on fixed points");
-    for (int k = 0; k < GPE_MAX_ORTH; ++k)
-        if (e->orth_host[k]) FAIL(e, GPE_ERR_INVALID, "bind_sampler: orthogonality array %d is bound, and lives on fixed points", k);
+    for (int k = 0; k < GPE_MAX_ORTH; ++k)       // (a frozen state is re-evaluated behind every redraw: only caller arrays are refused)
+        if (e->orth_host[k] && !e->ost[k].on) FAIL(e, GPE_ERR_INVALID, "bind_sampler: orthogonality array %d is bound, and lives on fixed points", k);
     if (sp->every <= 0) FAIL(e, GPE_ERR_INVALID, "bind_sampler: every = %lld, need > 0", (long long)sp->every);
     double cells = 1.0;
     for (int k = 0; k < 3; ++k) {
@@ -2074,13 +2104,127 @@ int gpe_bind_boundary(gpe_engine* e, const float* d_xb, int64_t n_b, const float
     return GPE_OK;
 }
 
-int gpe_bind_orth(gpe_engine* e, int k, const float* d_psi) {
-    if (!e || k < 0 || k >= GPE_MAX_ORTH) return GPE_ERR_INVALID;
-    if (d_psi && e->smp_every > 0) FAIL(e, GPE_ERR_STATE, "bind_orth: a sampler is bound, an orthogonality array would go stale at its next redraw");
-    e->orth_host[k] = d_psi;
+// ---- orthogonality slots: a caller's array on the bound points, or a frozen state the engine evaluates itself ---------------------
+static int orth_publish(gpe_engine* e) {         // orth_host -> the device copy the head / seed kernels read; n_orth
     HIPCHK(e, hipMemcpyAsync((void*)e->orth_dev, e->orth_host, sizeof e->orth_host, hipMemcpyHostToDevice, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));
     fill_phys(e);
+    return GPE_OK;
+}
+
+int gpe_bind_orth(gpe_engine* e, int k, const float* d_psi) {
+    if (!e || k < 0 || k >= GPE_MAX_ORTH) return GPE_ERR_INVALID;
+    if (d_psi && e->smp_every > 0) FAIL(e, GPE_ERR_STATE, "bind_orth: a sampler is bound, an orthogonality array would go stale at its next redraw");
+    if (e->ost[k].on) {                          // the array (or NULL) replaces a frozen state
+        HIPCHK(e, hipStreamSynchronize(e->stream));
+        orth_state_free(e->ost[k]);
+    }
+    e->orth_host[k] = d_psi;
+    return orth_publish(e);
+}
+
+// the value-only forward batch of the refills and every frozen state's psi buffer, sized for the bound collocation set; a buffer is
+// reallocated only when the point count changed.  The stream is idle (the binds synchronise first).
+static int orth_resize(gpe_engine* e) {
+    bool any = false;
+    for (int k = 0; k < GPE_MAX_ORTH; ++k) any = any || e->ost[k].on;
+    if (!any) { if (e->orb.O) free_batch(e->orb); return GPE_OK; }
+    if (!e->ux || e->n_pde <= 0) return GPE_OK;
+    int rc = setup_batch(e, e->orb, e->ux, e->n_pde, 1, 0, false, nullptr, /*with_store=*/false);
+    if (rc) return rc;
+    bool moved = false;
+    for (int k = 0; k < GPE_MAX_ORTH; ++k) {
+        OrthState& s = e->ost[k];
+        if (!s.on || s.n == e->n_pde) continue;
+        float* p = nullptr;
+        if (hipMalloc((void**)&p, (size_t)e->n_pde * sizeof(float) + 256) != hipSuccess) {
+            (void)hipGetLastError();
+            orth_state_free(s);                   // never leave a buffer of the old size in a slot the head kernels read
+            e->orth_host[k] = nullptr;
+            (void)orth_publish(e);
+            FAIL(e, GPE_ERR_NOMEM, "orthogonality state %d: no memory for %lld values (the slot was cleared)", k, (long long)e->n_pde);
+        }
+        (void)hipFree(s.psi);
+        s.psi = p; s.n = e->n_pde;
+        e->orth_host[k] = p;
+        moved = true;
+    }
+    return moved ? orth_publish(e) : GPE_OK;
+}
+
+// psi_k of every frozen state on the collocation set bound now: the value-only forward pass on the frozen parameters (the kernel set
+// gpe_forward runs), then k_orth_fill.  Enqueued on the engine's stream; nothing synchronises; never recorded into a graph (the binds
+// and sampler_launch are its only callers, and a capture neither binds nor redraws).
+static int orth_refill(gpe_engine* e) {
+    if (!e->ux || e->n_pde <= 0) return GPE_OK;
+    for (int k = 0; k < GPE_MAX_ORTH; ++k) {
+        const OrthState& s = e->ost[k];
+        if (!s.on) continue;
+        if (s.n != e->n_pde || e->orb.n != e->n_pde) FAIL(e, GPE_ERR_STATE, "orthogonality state %d: buffers not sized for the bound set", k);
+        e->orb.pts = Pts{e->ux, nullptr, e->n_pde};
+        const FwdWeights w{s.theta, s.Wpk, s.WpkT};
+        int rc = mlp_forward(e, e->orb, false, &w);
+        if (rc) return rc;
+        Phys ph = e->ph;
+        ph.base_mode = s.base_mode; ph.perturb_scale = s.perturb_scale;
+        hipLaunchKernelGGL(k_orth_fill, dim3(cdiv(e->n_pde, 256)), dim3(256), 0, e->stream, ph, s.base_norm, e->ux, (const float*)e->orb.O,
+                           s.amplitude, s.psi, e->n_pde);
+        HIPCHK(e, hipGetLastError());
+    }
+    return GPE_OK;
+}
+
+int gpe_bind_orth_state(gpe_engine* e, int k, const float* h_flat, size_t n, int base_mode, float perturb_scale, float amplitude) {
+    if (!e) return GPE_ERR_INVALID;
+    if (k < 0 || k >= GPE_MAX_ORTH) FAIL(e, GPE_ERR_INVALID, "bind_orth_state: slot %d, need 0..%d", k, GPE_MAX_ORTH - 1);
+    if (!h_flat) return gpe_bind_orth(e, k, nullptr);
+    if (e->cfg.complex_psi || e->nd.n_out != 1) FAIL(e, GPE_ERR_INVALID, "bind_orth_state: frozen states need real psi (out=1)");
+    if ((int64_t)n != e->P_user) FAIL(e, GPE_ERR_INVALID, "bind_orth_state: got %zu floats, model has %d", n, e->P_user);
+    if (base_mode >= 0 && (e->cfg.base_kind == GPE_BASE_PRECOMPUTED || e->nd.dim > 1))
+        FAIL(e, GPE_ERR_INVALID, "bind_orth_state: a base needs dim=1 and an analytic base kind (a precomputed base lives on fixed points)");
+    if (!isfinite(perturb_scale) || !isfinite(amplitude)) FAIL(e, GPE_ERR_INVALID, "bind_orth_state: perturb_scale / amplitude not finite");
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    if (e->side) HIPCHK(e, hipStreamSynchronize(e->side));
+    // build the new state aside; the slot changes only once everything is in place
+    OrthState s;
+    const bool have_pts = e->ux && e->n_pde > 0;
+    const size_t wn = e->path == GPE_PATH_FUSED ? (size_t)(e->nd.n_lin - 2) * e->H * e->H : 0;
+    bool ok = hipMalloc((void**)&s.theta, (size_t)e->P * 4 + 256) == hipSuccess &&
+              hipMalloc((void**)&s.psi, (size_t)(have_pts ? e->n_pde : 0) * sizeof(float) + 256) == hipSuccess;
+    if (ok && wn) ok = hipMalloc((void**)&s.Wpk, wn * 4 + 256) == hipSuccess && hipMalloc((void**)&s.WpkT, wn * (4 + 6 + 6) + 256) == hipSuccess;
+    if (!ok) { (void)hipGetLastError(); orth_state_free(s); FAIL(e, GPE_ERR_NOMEM, "bind_orth_state: no memory for the frozen state"); }
+    int rc = flat_to_device(e, s.theta, h_flat, /*params=*/true);
+    if (!rc && hipStreamSynchronize(e->stream) != hipSuccess) { e->err = "bind_orth_state: upload failed"; rc = GPE_ERR_HIP; }
+    if (!rc && wn) {                             // the same packing as the trained parameters (k_pack_weights / k_begin)
+        hipLaunchKernelGGL(k_pack_weights, dim3(cdiv((int64_t)wn, 256)), dim3(256), 0, e->stream, e->nd, e->H, (const float*)s.theta, s.Wpk, s.WpkT);
+        if (hipGetLastError() != hipSuccess) { e->err = "bind_orth_state: k_pack_weights launch failed"; rc = GPE_ERR_HIP; }
+    }
+    if (!rc && have_pts) rc = setup_batch(e, e->orb, e->ux, e->n_pde, 1, 0, false, nullptr, /*with_store=*/false);
+    if (rc) { (void)hipStreamSynchronize(e->stream); orth_state_free(s); return rc; }
+    s.on = true; s.n = have_pts ? e->n_pde : 0;
+    s.base_mode = base_mode; s.perturb_scale = perturb_scale; s.amplitude = amplitude;
+    if (base_mode >= 0) {                        // Hermite normalisation, as fill_phys forms the engine's
+        double f = 1.0;
+        for (int i = 2; i <= base_mode; ++i) f *= i;
+        s.base_norm = (float)pow(pow(2.0, base_mode) * f * sqrt(M_PI), -0.5);
+    }
+    orth_state_free(e->ost[k]);                  // (a caller array in the slot is simply replaced)
+    e->ost[k] = s;
+    e->orth_host[k] = s.psi;
+    if ((rc = orth_publish(e))) return rc;
+    if ((rc = orth_refill(e))) return rc;
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    return GPE_OK;
+}
+
+int gpe_orth_values(gpe_engine* e, int k, const float** d_psi, int64_t* n) {
+    if (!e) return GPE_ERR_INVALID;
+    if (k < 0 || k >= GPE_MAX_ORTH) FAIL(e, GPE_ERR_INVALID, "orth_values: slot %d, need 0..%d", k, GPE_MAX_ORTH - 1);
+    if (!e->ost[k].on) FAIL(e, GPE_ERR_STATE, "orth_values: slot %d holds no frozen state", k);
+    if (!e->ux || e->n_pde <= 0 || e->ost[k].n != e->n_pde) FAIL(e, GPE_ERR_STATE, "orth_values: no points bound");
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    if (d_psi) *d_psi = e->ost[k].psi;
+    if (n) *n = e->n_pde;
     return GPE_OK;
 }
 

@@ -537,6 +537,22 @@ __global__ __launch_bounds__(256) void k_eval_u(Phys ph, float base_norm, const 
     double t = block_sum_256(s, red);
     if (threadIdx.x == 0) atomicAdd(acc, t);
 }
+// frozen orthogonality state (gpe_bind_orth_state): psi_k = amplitude * (env * s_k * NN_theta_k + phi_k) from the value-only output O of
+// the forward pass on the frozen parameters -- k_eval_u's arithmetic for the point with the STATE's perturb_scale / base_mode (ph is the
+// engine's Phys with those two replaced), then one rounded multiply by the amplitude.  Real psi (n_out = 1); no reduction, no atomics.
+__global__ __launch_bounds__(256) void k_orth_fill(Phys ph, float base_norm, const float* __restrict__ x, const float* __restrict__ O,
+                                                   float amplitude, float* __restrict__ psi, int64_t N) {
+    const int64_t m = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (m >= N) return;
+    float v = ph.perturb_scale * O[m];
+    if (ph.envelope == GPE_ENV_SIN) { float f, f1, f2; envelope_at(ph, x[m * ph.dim], f, f1, f2); v *= f; }
+    if (ph.base_mode >= 0) {
+        float phi, p1, p2;
+        base_at(ph, x[m * ph.dim], base_norm, phi, p1, p2);
+        v += phi;
+    }
+    psi[m] = v * amplitude;
+}
 __global__ void k_eval_finish(const float* __restrict__ u, const double* __restrict__ acc, float dx, int abs_flag,
                               float* __restrict__ u_out, float* __restrict__ dens, int64_t N, int64_t ld, int n_out) {
     int64_t m = (int64_t)blockIdx.x * 256 + threadIdx.x;

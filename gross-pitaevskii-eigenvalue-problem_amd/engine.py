@@ -391,6 +391,31 @@ class Engine:
         self._keep[f"orth{k}"] = t
         self._chk(self.lib.gpe_bind_orth(self._h, int(k), C.c_void_p(t.data_ptr()) if t is not None else None))
 
+    def bind_orth_state(self, k: int, params, base_mode: int = -1, perturb_scale: float = 1.0, amplitude: float = 1.0):
+        """Frozen reference state in orthogonality slot k: psi_k = amplitude * (env * perturb_scale * NN_params + phi_base_mode), kept and
+        evaluated by the engine on every collocation set it holds -- at the binds and behind every redraw of the sampler -- so that
+        an excited state can be trained on sampler-drawn sets.  params: a flat parameter vector of this engine's network, or another
+        Engine of the same network, whose get_params() and cfg.base_mode / cfg.perturb_scale are taken (the two keywords are then
+        ignored).  None clears the slot."""
+        if params is None:
+            self._chk(self.lib.gpe_bind_orth_state(self._h, int(k), None, 0, -1, 1.0, 1.0))
+            self._keep.pop(f"orth{k}", None)
+            return
+        if isinstance(params, Engine):
+            base_mode, perturb_scale = params.cfg.base_mode, params.cfg.perturb_scale
+            params = params.get_params()
+        a = np.ascontiguousarray(np.asarray(params, dtype=np.float32).ravel())
+        self._chk(self.lib.gpe_bind_orth_state(self._h, int(k), a.ctypes.data_as(C.c_void_p), a.size, int(base_mode),
+                                               float(perturb_scale), float(amplitude)))
+        self._keep.pop(f"orth{k}", None)            # the engine's own buffer replaced a caller array
+
+    def orth_values(self, k: int) -> torch.Tensor:
+        """Copy of the engine-owned psi_k [n_local] of the frozen state in slot k on the set bound now; synchronises."""
+        p, n = C.c_void_p(), C.c_int64()
+        self._chk(self.lib.gpe_orth_values(self._h, int(k), C.byref(p), C.byref(n)))
+        view = _DeviceArrayView(p.value, (int(n.value),))
+        return torch.as_tensor(view, device=f"cuda:{self.device}").clone()
+
     # ---- forward-only -----------------------------------------------------------------------------------------
     def forward(self, x) -> torch.Tensor:
         x = self._to_dev(x, "x")

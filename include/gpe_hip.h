@@ -211,7 +211,23 @@ int gpe_reset_optimizer(gpe_engine* e, float lr);                    /* new Adam
  * Buffers stay owned by the caller and must outlive their use. */
 int gpe_bind_points(gpe_engine* e, const float* d_x, int64_t n_local, const float* d_V);
 int gpe_bind_boundary(gpe_engine* e, const float* d_xb, int64_t n_b, const float* d_target /* [n_b,out] or NULL = 0 */);
-int gpe_bind_orth(gpe_engine* e, int k, const float* d_psi_k /* [n_local] or NULL to clear */);
+int gpe_bind_orth(gpe_engine* e, int k, const float* d_psi_k /* [n_local] or NULL to clear (a caller array or a frozen state) */);
+/* Frozen reference state in orthogonality slot k (0 .. GPE_MAX_ORTH-1): a parameter set of the engine's OWN network (layers,
+ * activation, net_kind; caller's layout as gpe_set_params, n == gpe_param_count) that the engine keeps on the device and evaluates
+ * itself:  psi_k(x) = amplitude * ( env(x) * perturb_scale * NN_theta_k(x) + phi_{base_mode}(x) )
+ * base_mode < 0: no base.  Base kind / envelope are the engine's.  h_flat == NULL clears the slot.  A slot holds a caller array
+ * (gpe_bind_orth) or a frozen state; binding one kind replaces the other.  psi_k lives in an engine-owned buffer [n_local] that the
+ * head / seed kernels read like a caller's array; it is filled on the engine's stream -- here (if points are bound), at every
+ * gpe_bind_points / gpe_bind_sampler, and directly behind every redraw of the sampler -- by the forward pass behind gpe_forward run
+ * on the frozen parameters (same kernel set, width padding and weight packing as the trained ones) and one elementwise kernel.
+ * Never part of a captured graph.  Later gpe_set_params / gpe_set_perturb_scale / gpe_set_gamma / gpe_reset_optimizer do not touch it.
+ * Every step entry point honours it (gpe_step, gpe_run, the three phases, gpe_step_dp / gpe_run_dp: each rank fills its own rows).
+ * GPE_ERR_INVALID: complex psi or out != 1, n != gpe_param_count, k out of range, base_mode >= 0 with GPE_BASE_PRECOMPUTED or dim > 1,
+ * perturb_scale / amplitude not finite.  A bind that fails leaves the slot as it was.
+ * Replaces: the host-side evaluate-and-upload a caller of gpe_bind_orth needs per point set (no reference counterpart). */
+int gpe_bind_orth_state(gpe_engine* e, int k, const float* h_flat, size_t n, int base_mode, float perturb_scale, float amplitude);
+/* synchronise; the engine-owned array psi_k [n] on the collocation set bound now.  GPE_ERR_STATE: slot k holds no frozen state, or no points bound. */
+int gpe_orth_values(gpe_engine* e, int k, const float** d_psi, int64_t* n);
 /* GPE_BASE_PRECOMPUTED: phi, phi', phi'' of the base on the bound points, each [n_local].  The boundary term then uses no
  * base: fold phi(x_b) into the boundary target. */
 int gpe_bind_base(gpe_engine* e, const float* d_phi, const float* d_phi1, const float* d_phi2);
@@ -241,7 +257,7 @@ size_t gpe_sizeof_sampler_spec(void);   /* sizeof(gpe_sampler_spec) */
  * array (and the [x ; -x] symmetry batch when w_sym != 0, refreshed by every redraw).  Every step entry point honours the sampler:
  * gpe_step, gpe_run (which cuts its graph replays at redraw steps), gpe_step_dp, gpe_run_dp and the three-phase gpe_step_begin.
  * spec == NULL clears the sampler and leaves no points bound.  GPE_ERR_INVALID: GPE_POT_PRECOMPUTED or GPE_BASE_PRECOMPUTED (their arrays
- * would be stale), an orthogonality array bound, every <= 0, hi <= lo or clip_hi < clip_lo on a used axis, first_cell + n_local beyond
+ * would be stale), a caller's orthogonality array bound (frozen states of gpe_bind_orth_state are fine), every <= 0, hi <= lo or clip_hi < clip_lo on a used axis, first_cell + n_local beyond
  * the product of shape, axes used other than the network's input dimension.  While a sampler is bound gpe_bind_orth with an array,
  * gpe_bind_target and the gpe_mse_* entry points return GPE_ERR_STATE (their arrays live on fixed points); gpe_bind_points clears
  * the sampler and the caller's points take over.
