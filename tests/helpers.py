@@ -152,3 +152,34 @@ def problem_from_class2d(fx, n_global=0) -> go.Problem:
     return go.Problem(layers=[int(v) for v in fx["layers"]], activation=0, kinetic_coeff=1.0, potential=go.POT_PRECOMPUTED, gamma=float(fx["g"]), p=3,
                       abs_power=True, w_pde=1.0, w_bc=10.0, w_norm=0.0, w_riesz=1.0, riesz_kind=go.RIESZ_SUM, lambda_kind=go.LAMBDA_ENERGY,
                       w_reg_f=1.0, reg_f_eps=1e-2, w_reg_lam=1.0, reg_lam_eps=1e-6, dx=1.0, n_global=n_global)
+
+
+# ---- data-parallel cuts with the edges in them (tests/test_gpu_dp_matrix.py, tests/test_dp_cuts_cpu.py) ------------------------------
+# leading block sizes per world; the last rank takes the rest.  1-point shards, shards one below, at and one above the 16-point tile,
+# and (5 boundary points in d > 1, 2 in 1D; merged into the collocation launch when nb * 8 <= n_pde) ranks with the boundary batch
+# merged next to ranks where it runs on its own
+DP_CUT_HEADS = {3: (1, 17), 8: (1, 15, 16, 17, 64, 1, 200)}
+
+
+def dp_cuts(world, N):
+    """[(lo, hi)] of the `world` contiguous blocks of 0..N: W = 3 -> sizes (1, 17, N - 18); W = 8 -> (1, 15, 16, 17, 64, 1, 200, N - 314)"""
+    head = DP_CUT_HEADS[world]
+    sizes = list(head) + [N - sum(head)]
+    assert sizes[-1] >= 1, (world, N)
+    edges = np.concatenate([[0], np.cumsum(sizes)])
+    return [(int(edges[r]), int(edges[r + 1])) for r in range(world)]
+
+
+def param_blocks(layers, net_kind=go.NET_MLP):
+    """[(name, flat indices)] of every weight matrix and bias, from go.unflatten of an index vector"""
+    idx = go.unflatten(np.arange(go.param_count(layers, net_kind)), layers, net_kind)
+    out = []
+    for j, (W, b) in enumerate(idx):
+        out += [(f"W{j}", W.ravel()), (f"b{j}", b.ravel())]
+    return out
+
+
+def block_rel_errs(g, ref, blocks):
+    """{block name: max|g - ref| over the block / max|ref| over the block}"""
+    g = np.asarray(g, np.float64); ref = np.asarray(ref, np.float64)
+    return {nm: float(np.abs(g[ix] - ref[ix]).max() / (np.abs(ref[ix]).max() + 1e-300)) for nm, ix in blocks}

@@ -1,7 +1,7 @@
-"""world_size = 2 on ONE MI355X: two processes, each with its own HIP engine on cuda:0 and half of the collocation points,
-exchange the two step buffers with torch.distributed (gloo backend: NCCL/RCCL refuses two ranks on one device; the
+"""world_size = 2 and 8 on ONE MI355X: one process per rank, each with its own HIP engine on cuda:0 and its block of the collocation
+points, exchange the two step buffers with torch.distributed (gloo backend: NCCL/RCCL refuses two ranks on one device; the
 data-parallel protocol and the engine's three-phase API are exactly what bench.py runs over RCCL).  The result must equal
-the single-engine step on all points."""
+the single-engine step on all points, and the fp64 oracle's at the tolerances of test_step_matches_oracle."""
 import os
 import socket
 
@@ -33,12 +33,14 @@ def _case():
 
 
 def _worker(rank, world, port, steps, out):
+    from datetime import timedelta
     import torch.distributed as dist
     import gpe_pinn
     from gpe_pinn.dp import shard_points
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+    # (a rank that dies ends its peers within the timeout instead of leaving them in all_reduce until the pytest limit)
+    dist.init_process_group("gloo", rank=rank, world_size=world, timeout=timedelta(seconds=120))
     torch.cuda.set_device(0)
     kw, x, xb, flat = _case()
     eng = gpe_pinn.Engine(gpe_pinn.GPEConfig(**kw, world_size=world), device=0)
@@ -46,20 +48,26 @@ def _worker(rank, world, port, steps, out):
     eng.bind_points(torch.as_tensor(shard_points(x, rank, world), device="cuda:0"))
     eng.bind_boundary(torch.as_tensor(xb, device="cuda:0"))
     trace = []
-    for _ in range(steps):
+    for k in range(steps):
         trace.append(eng.step_distributed(sync=True))
+        if k == 0:
+            grad1, flat1 = eng.get_grad(), eng.get_params()
     if rank == 0:
         np.savez(out, flat=eng.get_params(), loss=[t["loss"] for t in trace], mu=[t["mu"] for t in trace],
-                 gn=[t["grad_norm"] for t in trace])
+                 gn=[t["grad_norm"] for t in trace], bc=[t["bc"] for t in trace], pde=[t["pde"] for t in trace],
+                 norm=[t["norm"] for t in trace], grad1=grad1, flat1=flat1)
     dist.barrier()
     dist.destroy_process_group()
 
 
 @pytest.mark.timeout(600)
-def test_two_ranks_one_gpu_equal_single_engine(tmp_path):
+@pytest.mark.parametrize("world", [2, 8])
+def test_two_ranks_one_gpu_equal_single_engine(tmp_path, world):
     import torch.multiprocessing as mp
     import gpe_pinn
-    steps, world = 3, 2
+    from oracle import gpe_oracle as go
+    from tests import helpers as H
+    steps = 3
     out = str(tmp_path / "dp_gpu.npz")
     mp.get_context("spawn")
     mp.spawn(_worker, args=(world, _free_port(), steps, out), nprocs=world, join=True)
@@ -74,6 +82,22 @@ def test_two_ranks_one_gpu_equal_single_engine(tmp_path):
     np.testing.assert_allclose(got["mu"], [t["mu"] for t in ref], rtol=2e-6)
     np.testing.assert_allclose(got["gn"], [t["grad_norm"] for t in ref], rtol=2e-5)
     assert np.abs(got["flat"] - eng.get_params()).max() < 2e-5
+    # ... and the fp64 oracle on all points: first step at the bounds of test_step_matches_oracle, the losses of all steps at the
+    # trajectory bound of tools/fuzz_parity.py
+    pb = go.Problem(layers=kw["layers"], gamma=kw["gamma"], dx=kw["dx"], n_global=kw["n_global"])
+    x64, xb64, f64 = x.astype(np.float64), xb.astype(np.float64), flat.astype(np.float64)
+    osc, ograd, _ = go.full_loss_and_grad(pb, f64, x64, xb64)
+    for k, tol in (("mu", 2e-5), ("loss", 1e-4), ("pde", 1e-4), ("bc", 1e-4), ("norm", 2e-4)):
+        assert abs(got[k][0] - osc[k]) <= tol * max(abs(osc[k]), 1e-6), (k, got[k][0], osc[k])
+    assert abs(got["gn"][0] - np.linalg.norm(ograd)) < 1e-4 * np.linalg.norm(ograd)
+    assert H.rel_err(got["grad1"], ograd) < 5e-5
+    worst = H.block_rel_errs(got["grad1"], ograd, H.param_blocks(pb.layers))
+    assert max(worst.values()) < 5e-5, worst
+    new, _, _ = go.optimizer_step(go.OptState(lr0=kw["lr"]), flat, ograd, osc["loss"])
+    d = np.abs(got["flat1"] - new)
+    assert np.quantile(d, 0.99) < 2e-5 and d.max() < 2.1e-3
+    _, tr = go.train_steps(pb, go.OptState(lr0=kw["lr"]), f64, x64, steps, xb64, dtype=np.float64)
+    assert max(abs(a - t["loss"]) / abs(t["loss"]) / (1 + k) for k, (a, t) in enumerate(zip(got["loss"], tr))) < 1e-3
 
 
 def _worker_native(rank, world, port, steps, out, stale):

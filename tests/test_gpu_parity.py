@@ -1103,26 +1103,52 @@ def test_padded_hidden_widths_train_like_the_network_as_given():
 
 
 # ---- native exchange: the engine's own RCCL communicator (world 1 on the one-GPU box: the same code path as N ranks) -----------
-@pytest.mark.parametrize("extra", [{}, dict(kinetic_coeff=1.0, pot_scale=1.0, w_norm=0.0, w_riesz=0.05, riesz_kind=go.RIESZ_SUM,
-                                            lambda_kind=go.LAMBDA_ENERGY, w_reg_f=1.0, w_reg_lam=1.0)], ids=["north_star_loss", "2d_class_loss"])
-@pytest.mark.parametrize("path", ["generic", "fused"])
-def test_native_rccl_step_equals_plain_step(path, extra):
-    kw = dict(layers=[2, 64, 64, 64, 1], gamma=50.0, dx=0.01, **extra)
-    x, flat, x_bc = _inputs(kw, 3000)
+_CLASS_LOSS = dict(kinetic_coeff=1.0, pot_scale=1.0, w_norm=0.0, w_riesz=0.05, riesz_kind=go.RIESZ_SUM, lambda_kind=go.LAMBDA_ENERGY, w_reg_f=1.0,
+                   w_reg_lam=1.0)
+# the bucket-per-map exchange overlapped with the reverse pass exists on the generic set only: residual blocks, the H = 256 energy-functional
+# lambda, complex psi with the variational energy and a single hidden layer step through it too, each also against the fp64 oracle
+NATIVE_CASES = ["1d_residual_64x2blocks", "3d_energy_lambda_p5_256x2", "2d_complex_rot_variational", "1d_single_hidden"]
+
+
+@pytest.mark.parametrize("path,extra,case", [("generic", {}, None), ("fused", {}, None), ("generic", _CLASS_LOSS, None), ("fused", _CLASS_LOSS, None)]
+                         + [("generic", None, c) for c in NATIVE_CASES],
+                         ids=["generic-north_star_loss", "fused-north_star_loss", "generic-2d_class_loss", "fused-2d_class_loss"]
+                         + [f"generic-{c}" for c in NATIVE_CASES])
+def test_native_rccl_step_equals_plain_step(path, extra, case):
+    if case is None:
+        kw = dict(layers=[2, 64, 64, 64, 1], gamma=50.0, dx=0.01, **extra)
+        x, flat, x_bc = _inputs(kw, 3000)
+    else:
+        kw, N, _ = CASES[case]
+        x, flat, x_bc = _inputs(kw, N, scale=_scale(kw))
     pb = go.Problem(**kw)
     a = make_engine(pb, flat, x, x_bc, path=PATHS[path])
     b = make_engine(pb, flat, x, x_bc, path=PATHS[path])
+    assert b.active_path == PATHS[path]
     b.comm_init(0, 1)
     assert b.comm_info()["world"] == 1 and a.comm_info()["world"] == 0
-    for _ in range(3):
+    for k in range(3):
         a.step()
         b.step_dp()
+        if k == 0 and case is not None:                # the first step over the communicator against the fp64 oracle (test_step_matches_oracle's bounds)
+            osc, ograd, _ = go.full_loss_and_grad(pb, flat.astype(np.float64), x.astype(np.float64), x_bc.astype(np.float64))
+            sc, grad = b.read_scalars(), b.get_grad()
+            for key, tol in (("mu", 2e-5), ("loss", 1e-4), ("pde", 1e-4), ("bc", 1e-4), ("norm", 2e-4), ("sym", 1e-4), ("riesz", 1e-4), ("reg", 1e-4)):
+                assert abs(sc[key] - osc[key]) <= tol * max(abs(osc[key]), 1e-6), (key, sc[key], osc[key])
+            assert H.rel_err(grad, ograd) < 5e-5
+            worst = H.block_rel_errs(grad, ograd, H.param_blocks(pb.layers, pb.net_kind))
+            assert max(worst.values()) < 5e-5, worst
+            assert abs(sc["grad_norm"] - np.linalg.norm(ograd)) < 1e-4 * np.linalg.norm(ograd)
+            new, _, _ = go.optimizer_step(go.OptState(lr0=1e-3), flat, ograd, osc["loss"])
+            d = np.abs(b.get_params() - new)
+            assert np.quantile(d, 0.99) < 2e-5 and d.max() < 2.1e-3
     sa, sb = a.read_scalars(), b.read_scalars()
     assert abs(sa["loss"] - sb["loss"]) <= 1e-6 * abs(sa["loss"]) and abs(sa["mu"] - sb["mu"]) <= 1e-6 * abs(sa["mu"])
     assert np.abs(a.get_params() - b.get_params()).max() < 1e-6
     n = b.comm_info()["collectives"]
     # fused: sums + one gradient message per step; generic: sums + one bucket per linear map + the tail
-    assert n == (3 * 2 if path == "fused" else 3 * (1 + (len(kw["layers"]) - 1) + 1)), n
+    n_maps = len(go.expand_layers(kw["layers"], kw.get("net_kind", go.NET_MLP))[0]) - 1
+    assert n == (3 * 2 if path == "fused" else 3 * (1 + n_maps + 1)), n
     with pytest.raises(gpe_pinn.GPEError):
         a.step_dp()                                   # no communicator: loud
     a.close(); b.close()
@@ -1355,5 +1381,9 @@ def test_randomised_parity_sweep():
     import os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "tools", "fuzz_parity.py"), "120", "3", "7"], capture_output=True, text=True, timeout=600, cwd=root)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-1500:]
+    # ... and 40 more, five steps each, also stepped data-parallel at world 3 on random uneven cuts with a 1-point shard (the tool's thresholds)
+    r = subprocess.run([sys.executable, os.path.join(root, "tools", "fuzz_parity.py"), "40", "5", "7", "1", "dp", "3"], capture_output=True, text=True,
+                       timeout=600, cwd=root)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-1500:]
 

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Randomised parity sweep: engine (kernel set as gpe_create picks it: fused / wide / padded / residual / generic) against the fp64 oracle on
 random problem descriptions -- dimensions, hidden widths (native, odd, ragged), depth, activation, residual blocks, loss terms (Riesz forms,
-energy-functional lambda, regularisers, symmetry), batch sizes down to one point.  usage: python tools/fuzz_parity.py [cases] [seed] [smallest N] [steps]"""
+energy-functional lambda, regularisers, symmetry), batch sizes down to one point.
+usage: python tools/fuzz_parity.py [cases] [seed] [smallest N] [steps] [dp [world]]"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -15,8 +16,24 @@ cases = int(sys.argv[1]) if len(sys.argv) > 1 else 100
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 0)
 min_n = int(sys.argv[3]) if len(sys.argv) > 3 else 1
 n_steps = int(sys.argv[4]) if len(sys.argv) > 4 else 1          # > 1: also follow the fp64 oracle's optimiser for that many steps (loss per step)
-dp_mode = len(sys.argv) > 5 and sys.argv[5] == "dp"             # also: the step of TWO engines on the two halves of the points (world_size = 2, exchange
-                                                                # buffers summed by hand as the all-reduces would) against the single engine's
+dp_mode = len(sys.argv) > 5 and sys.argv[5] == "dp"             # also: the step of `world` engines on contiguous blocks of the points (exchange buffers
+dp_world = int(sys.argv[6]) if len(sys.argv) > 6 else 2         # summed by hand in float64 in rank order, as the all-reduces would) against the single engine's
+
+
+def dp_cuts(N, world, cut_rng):
+    """`world` contiguous blocks of 0..N at random uneven positions, one of them a single point when N >= world + 1 (a generator of its
+    own: the problem descriptions of a seed do not depend on the mode)"""
+    if N >= world + 1:
+        inner = np.sort(cut_rng.choice(np.arange(1, N - 1), size=world - 2, replace=False)) if world > 2 else np.zeros(0, int)
+        sizes = np.diff(np.concatenate([[0], inner, [N - 1]])).tolist()          # world - 1 blocks of N - 1 points ...
+        sizes.insert(int(cut_rng.integers(0, world)), 1)                        # ... and the 1-point shard at a random rank
+    else:
+        sizes = [1] * N
+    edges = np.concatenate([[0], np.cumsum(sizes)])
+    assert len(sizes) == world and edges[-1] == N and min(sizes) >= 1
+    return [(int(edges[r]), int(edges[r + 1])) for r in range(world)]
+
+
 bad = 0
 t0 = time.time()
 for it in range(cases):
@@ -103,29 +120,30 @@ for it in range(cases):
             traj = max(abs(a - t["loss"]) / max(abs(t["loss"]), 1e-30) / (1 + k) for k, (a, t) in enumerate(zip(losses, tr)))
         eng.close()
         dpe = 0.0
-        if dp_mode and N >= 2:
+        if dp_mode and N >= dp_world:
             import dataclasses
             pbn = dataclasses.replace(pb, n_global=N)
-            lo = N // 2
             engs = []
-            for xs in (x[:lo], x[lo:]):
-                e2 = gpe_pinn.Engine(cfg_from_problem(pbn, world_size=2))
-                e2.set_params(flat); e2.bind_points(torch.as_tensor(xs, device="cuda")); e2.bind_boundary(torch.as_tensor(xb, device="cuda"))
+            for lo, hi in dp_cuts(N, dp_world, np.random.default_rng([int(sys.argv[2]), it])):
+                e2 = gpe_pinn.Engine(cfg_from_problem(pbn, world_size=dp_world))
+                e2.set_params(flat); e2.bind_points(torch.as_tensor(x[lo:hi], device="cuda")); e2.bind_boundary(torch.as_tensor(xb, device="cuda"))
                 engs.append(e2)
             for e2 in engs: e2.step_begin()
-            tot = engs[0].exchange_sums + engs[1].exchange_sums
+            tot = torch.zeros_like(engs[0].exchange_sums)
+            for e2 in engs: tot += e2.exchange_sums
             for e2 in engs:
                 e2.exchange_sums.copy_(tot); e2.step_backward()
-            gt = engs[0].exchange_grad + engs[1].exchange_grad
+            gt = torch.zeros_like(engs[0].exchange_grad, dtype=torch.float64)
+            for e2 in engs: gt += e2.exchange_grad.to(torch.float64)
             for e2 in engs:
-                e2.exchange_grad.copy_(gt); e2.step_update()
+                e2.exchange_grad.copy_(gt.to(torch.float32)); e2.step_update()
             s2 = engs[0].read_scalars()
             dpe = max(abs(s2["loss"] - sc["loss"]) / max(abs(sc["loss"]), 1e-30), abs(s2["mu"] - sc["mu"]) / max(abs(sc["mu"]), 1e-6),
                       H.rel_err(engs[0].get_grad(), g) / 5.0)
-            same = np.array_equal(engs[0].get_params(), engs[1].get_params())
+            same = all(np.array_equal(engs[0].get_params(), e2.get_params()) for e2 in engs[1:])
             for e2 in engs: e2.close()
             if not same: dpe = float("inf")
-        traj = max(traj, 50.0 * dpe)          # (reported in the same column: the two-rank step within 2e-5 of the single engine's, replicas bit-identical)
+        traj = max(traj, 50.0 * dpe)          # (reported in the same column: the data-parallel step within 2e-5 of the single engine's, replicas bit-identical)
         f = 10.0 if N < 4 else 1.0
         el = abs(sc["loss"] - osc["loss"]) / max(abs(osc["loss"]), 1e-30)
         em = abs(sc["mu"] - osc["mu"]) / max(abs(osc["mu"]), 1e-6)
