@@ -478,6 +478,29 @@ struct OrthState {
     float perturb_scale = 1.f, amplitude = 1.f, base_norm = 1.f;
 };
 
+// what the caller of a step's phases promises about how it enqueues them
+struct StepOpts {
+    bool head_may_fuse = false;    // nobody reads the step sums between the passes: the head may ride in the forward kernel
+    bool update_may_fuse = false;  // reduction and update are enqueued back to back: the update may ride in the slab reduction
+    bool capturing = false;        // graph_build is recording: neither count the step nor redraw
+};
+// what the phases of one step hand to the next; e->st = StepState{} is the only reset
+struct StepState {
+    int phase = 0;                 // 0 idle, 1 after begin, 2 after backward, 3 after mse begin
+    bool bc_inflight = false;      // the boundary batch was forked: its gradient (grad_bc) waits for the reverse pass that closes the step
+    int head_slots = 0;            // the forward pass left this many per-workgroup head triples in head_slots (= its workgroups); 0: k_head_pde ran
+    bool update_done = false;      // the update already ran inside the slab reduction
+    bool update_parts = false;     // the slab reduction left partial norms + snapshot for the multi-workgroup update
+};
+// one reverse pass (mlp_backward)
+struct BwdOpts {
+    bool close = false;            // the last reverse pass of the step: join the boundary batch, add its gradient, write the exchange tail
+    bool assign = true;            // the first one: the gradient is assigned, not accumulated
+    bool seeds_in_kernel = false;  // small batch: the pipelined kernel forms the seeds itself (k_seed_pde was not launched)
+    bool update_may_fuse = false;  // StepOpts::update_may_fuse
+    bool bucketed = false;         // data-parallel step, generic set: finished layers go to the exchange stream
+};
+
 struct gpe_engine {
     gpe_config cfg;
     NetDesc nd;
@@ -505,7 +528,6 @@ struct gpe_engine {
     OptDev* od = nullptr;
     bool update_cache = true;      // single-workgroup update: register-cached elements + scatter packing (GPE_UPDATE_CACHE=0: the two-pass form)
     bool fuse_seed = true;         // small batches: the pipelined reverse kernel forms the seeds itself (GPE_FUSE_SEED=0: k_seed_pde)
-    bool seedf_now = false;        // ... for the reverse pass being enqueued
     int64_t fuse_seed_max = 65536; // ... up to this many points (beyond, the redundant seed arithmetic of the four waves costs more than the launch)
     int share_min_tiles = 16;      // ... for batches of at least this many tiles per workgroup (per wave in the forward kernel)
     int fwd_share = 640;           // f_forward: the same for its waves (GPE_FWD_SHARE; measured flat between 608 and 672: NS step 2.703 -> 2.688 ms)
@@ -513,18 +535,12 @@ struct gpe_engine {
                                    // NS reverse kernel 1.741 ms even, 1.727 / 1.719 / 1.715 / 1.730 / 1.741 ms at 544 / 576 / 592 / 608 / 640)
     bool fuse_head = true;         // ... and the cooperative forward kernel runs the head (GPE_FUSE_HEAD=0: k_head_pde): whole steps only,
     int64_t fuse_head_max = 6144;  // up to this many points (measured: 43.2 vs 46.5 us at 4 000, equal at 6 000, 64.3 vs 62.9 us at 8 192)
-    bool fh_want = false;          // gpe_step / graph capture in progress: nobody reads the step sums between the passes
-    bool fh_now = false;           // the forward pass of this step left per-workgroup head sums in head_slots
-    int fh_nslots = 0;             // ... this many triples (= workgroups of that forward launch)
     int64_t fuse_head_tile_min = 32769;   // f_forward (per-wave tiles) runs the head from this many points on (GPE_FUSE_HEAD_TILE_MIN)
     double* head_slots = nullptr;  // [HEAD_SLOTS][4]
     bool fuse_update = false;      // small P, whole steps: the last-arriving workgroup of the slab reduction runs the update (k_reduce_update; opt-in GPE_FUSE_UPDATE=1)
-    bool fu_want = false;          // gpe_step / graph capture in progress: reduction and update are enqueued back to back
-    bool fu_done = false;          // this step's update already ran inside the slab reduction
     unsigned* upd_ticket = nullptr;
     bool split_update = false;     // small P, whole steps: slab reduction in the update's partition + k_update<true> on UPD_G workgroups (opt-in GPE_SPLIT_UPDATE=1)
     UpdSnap* upd_snap_small = nullptr;
-    bool fu_parts = false;         // this step's slab reduction left partial norms + snapshot for the multi-workgroup update
     UpdSnap* upd_snap = nullptr;   // multi-workgroup update (P >= UPD_MULTI_MIN): partial norms + snapshot of sums / optimiser state
     gpe_scalars *hist = nullptr, *last = nullptr;
     int cap = 65536;
@@ -552,7 +568,6 @@ struct gpe_engine {
     hipStream_t side = nullptr;                   // boundary batch runs here, concurrently with the collocation batch
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     float *gslab_bc = nullptr, *grad_bc = nullptr;
-    bool bc_inflight = false;
     // gpe_run replays one captured step (hipGraph) while every by-value launch argument is unchanged
     bool use_graph = false;
     int graph_steps = 8;           // steps captured per graph (GPE_GRAPH_STEPS)
@@ -601,7 +616,6 @@ struct gpe_engine {
     double* dbl_prev = nullptr;                       // sums of the step whose gradient is in flight
     hipEvent_t ev_g[2] = {nullptr, nullptr};
     int64_t async_t = 0;
-    bool dp_bucket = false;                           // set by gpe_step_dp: the generic reverse pass hands finished layers to the comm stream
     int64_t dp_collectives = 0;                       // all-reduces issued since gpe_comm_init (bench / tests)
     bool dp_inline = true;                            // synchronous step on the fused / wide sets: collectives on the compute stream (GPE_DP_INLINE=0: exchange stream)
     // ---- observables (gpe_observe.h) ----
@@ -621,12 +635,28 @@ struct gpe_engine {
     int64_t smp_n = 0, smp_first = 0, smp_every = 0;  // every == 0: no sampler
     int64_t smp_draw0 = 0, smp_held = 0;              // draw at the bind / draw the buffer holds (as enqueued)
     int64_t smp_steps = 0;                            // steps enqueued since the bind
-    bool capturing = false;                           // graph_build is recording: neither count the step nor redraw
-    int phase = 0;                 // 0 idle, 1 after begin, 2 after backward
+    StepState st;
     std::string err;
     double* sums() { return dbl; }
     double* lsums() { return dbl + S_COUNT; }
     double* dsc() { return dbl + S_COUNT + LS_COUNT; }
+};
+
+// Every launcher enqueues on e->stream and writes the gradient through e->grad / e->gslab.  The boundary batch (side stream, grad_bc),
+// the stale-gradient step (alternating buffer) and the graph capture (capture stream) send them elsewhere for a while: only through
+// this guard, which puts the engine's own back on every way out.
+struct Redirect {
+    gpe_engine* e; hipStream_t stream; float *grad, *gslab;
+    Redirect(gpe_engine* e_, hipStream_t s, float* g, float* sl) : e(e_), stream(e->stream), grad(e->grad), gslab(e->gslab) { e->stream = s; e->grad = g; e->gslab = sl; }
+    ~Redirect() { e->stream = stream; e->grad = grad; e->gslab = gslab; }
+    Redirect(const Redirect&) = delete;
+};
+// The per-step record lives from one phase to the next only: a sequence clears it on every way out -- a step that failed half-way
+// must not leave anything behind -- except where it hands the record on to the next phase (keep).
+struct StepScope {
+    gpe_engine* e; bool kept = false;
+    ~StepScope() { if (!kept) e->st = StepState{}; }
+    int keep() { kept = true; return GPE_OK; }
 };
 
 static void free_batch(Batch& b) {
@@ -648,8 +678,6 @@ static int setup_batch(gpe_engine* e, Batch& b, const float* x, int64_t n, int C
                        bool with_store = true) {
     if (b.n == n && b.C == C && b.E == E && b.O) { b.pts = Pts{x, nullptr, n}; b.V = V; return GPE_OK; }
     HIPCHK(e, hipStreamSynchronize(e->stream));
-    float* keep_xown = nullptr;
-    (void)keep_xown;
     free_batch(b);
     b.pts = Pts{x, nullptr, n}; b.V = V; b.n = n; b.C = C; b.E = E;
     b.ld = round_up(n, 64);
@@ -756,8 +784,6 @@ static bool seed_in_reverse(gpe_engine* e);
 static bool plain_terms(const gpe_engine* e) {
     return e->cfg.w_riesz == 0.f && e->cfg.lambda_kind == GPE_LAMBDA_RAYLEIGH && e->cfg.w_reg_f == 0.f && e->cfg.w_reg_lam == 0.f;
 }
-// whole steps (gpe_step / gpe_run) of the small-batch class whose reverse kernel forms the seeds: the cooperative forward kernel runs
-// the head too, k_head_pde is not launched and the step sums are added in a fixed order
 // problem class whose head the forward kernels can run (head_point_real): real psi, no orthogonality / Riesz / symmetry terms
 static bool head_class(gpe_engine* e) {
     return e->fuse_head && e->head_slots && e->path == GPE_PATH_FUSED && !e->wide && e->H <= 64 && e->nd.n_out == 1 && !e->cfg.complex_psi &&
@@ -774,12 +800,12 @@ static bool head_fusable_tile(gpe_engine* e) {
     return head_class(e) && !fwd_coop(e, e->main) && !e->fwd_b6 && e->main.n >= e->fuse_head_tile_min && fused_grid(e, e->main.n, 4, e->fwd_wg_per_cu) <= HEAD_SLOTS;
 }
 static bool head_fusable(gpe_engine* e) { return head_fusable_coop(e) || head_fusable_tile(e); }
-static bool head_in_forward(gpe_engine* e) { return e->fuse_head && e->fh_want && head_fusable(e); }
+// head: the kernel runs the head too and leaves one triple per workgroup in head_slots (the step's forward pass of the main batch only)
 template <int HH, int CC, int EE, int NO>
-static void launch_fcoop_no(gpe_engine* e, Batch& b, unsigned grid, size_t lds, int store, const FwdWeights& W) {
+static void launch_fcoop_no(gpe_engine* e, Batch& b, unsigned grid, size_t lds, int store, const FwdWeights& W, bool head) {
 #define CARGS e->nd, W.theta, W.Wpk, b.pts, b.stored, b.O, b.n, b.ld, store
     if constexpr (HH <= 64 && NO == 1 && CC >= 3) {
-        if (e->fh_now && &b == &e->main) {
+        if (head) {
             const HeadArgs ha{e->ph, e->base_norm, b.V, (const float* const*)e->orth_dev, e->bc_target, b.u, b.Hu, b.Ob, e->n_pde, b.ld, e->head_slots};
             const size_t ldsh = lds + (size_t)CC * 16 * sizeof(float);
             if (e->cfg.net_kind == GPE_NET_RESIDUAL) {
@@ -823,17 +849,17 @@ static void launch_fcoop_no(gpe_engine* e, Batch& b, unsigned grid, size_t lds, 
 #undef CARGS
 }
 template <int HH, int CC, int EE>
-static void launch_f_forward(gpe_engine* e, Batch& b, unsigned grid, int store, const FwdWeights& W) {
+static void launch_f_forward(gpe_engine* e, Batch& b, unsigned grid, int store, const FwdWeights& W, bool head) {
     if constexpr (HH <= 64 || (HH == 128 && CC <= 4)) {
         if (fwd_coop(e, b)) {
             const int NT = HH / 16;
             const size_t lds = fused_small_bytes(e) + ((size_t)2 * CC * NT * 256 + (size_t)NT * e->nd.n_out * CC * 16) * sizeof(float);
             const unsigned g = fused_grid(e, b.n, 1, HH == 128 ? 1 : 2);
 #ifdef GPE_FAST_BUILD
-            launch_fcoop_no<HH, CC, EE, 1>(e, b, g, lds, store, W);
+            launch_fcoop_no<HH, CC, EE, 1>(e, b, g, lds, store, W, head);
 #else
-            if (e->nd.n_out == 1) launch_fcoop_no<HH, CC, EE, 1>(e, b, g, lds, store, W);
-            else launch_fcoop_no<HH, CC, EE, 2>(e, b, g, lds, store, W);
+            if (e->nd.n_out == 1) launch_fcoop_no<HH, CC, EE, 1>(e, b, g, lds, store, W, head);
+            else launch_fcoop_no<HH, CC, EE, 2>(e, b, g, lds, store, W, head);
 #endif
             return;
         }
@@ -869,7 +895,7 @@ static void launch_f_forward(gpe_engine* e, Batch& b, unsigned grid, int store, 
         }
     }
     if constexpr (HH <= 64 && CC >= 3) {
-        if (e->fh_now && &b == &e->main && e->nd.n_out == 1) {     // whole step, large batch: the head rides in this kernel
+        if (head && e->nd.n_out == 1) {     // whole step, large batch: the head rides in this kernel
             const HeadArgs ha{e->ph, e->base_norm, b.V, (const float* const*)e->orth_dev, e->bc_target, b.u, b.Hu, b.Ob, e->n_pde, b.ld, e->head_slots};
             if (e->fwd_wlds && staged_batch(e, b))
                 hipLaunchKernelGGL((f_forward<HH, CC, EE, 1, true, true>), dim3(grid), dim3(256), fused_fwd_lds(e, true), e->stream, e->nd, W.theta, W.Wpk,
@@ -955,8 +981,9 @@ static void set_pipe_lds(int bytes) {
 static bool coop_b6(const gpe_engine* e) {
     return e->bwd_b6 && e->H <= 64 && e->nd.n_lin - 2 <= 3 && e->cfg.net_kind == GPE_NET_MLP;
 }
+// seeds: the pipelined kernel forms the seeds itself from these (mlp_backward's seeds_in_kernel); nullptr: they are in b.Ob already
 template <int HH, int CC, int EE, int NO>
-static void launch_coop_no(gpe_engine* e, Batch& b, unsigned grid, size_t lds) {
+static void launch_coop_no(gpe_engine* e, Batch& b, unsigned grid, size_t lds, const SeedArgs* seeds) {
 #define CARGS e->nd, e->theta, e->WpkT, b.pts, b.stored, b.Ob, e->gslab, b.n, b.ld, e->Ppad
     if constexpr (HH <= 64) {
         if (coop_b6(e)) {
@@ -969,10 +996,8 @@ static void launch_coop_no(gpe_engine* e, Batch& b, unsigned grid, size_t lds) {
         }
         if constexpr (!(HH == 64 && CC == 5)) if (use_pipe(e, CC)) {       // (H = 64 in 3D: two workgroups' exchange buffers exceed the LDS)
             if constexpr (NO == 1 && CC >= 3) {
-                if (e->seedf_now && &b == &e->main) {       // small batch: the kernel forms the seeds itself (k_seed_pde was not launched)
-                    const SeedArgs sa{e->ph, b.V, b.u, b.Hu, (const double*)e->sums(), e->dsc(), e->n_pde,
-                                      e->fh_now ? (const double*)e->head_slots : nullptr, e->fh_now ? e->fh_nslots : 0,
-                                      e->sums(), e->lsums(), 0};
+                if (seeds) {       // small batch: the kernel forms the seeds itself (k_seed_pde was not launched)
+                    const SeedArgs& sa = *seeds;
                     switch (e->nd.n_lin - 2) {
                         case 1: hipLaunchKernelGGL((f_backward_pipe<HH, CC, EE, 1, 1, true>), dim3(grid), dim3(HH * 4), lds, e->stream, CARGS, sa); break;
                         case 2: hipLaunchKernelGGL((f_backward_pipe<HH, CC, EE, 1, 2, true>), dim3(grid), dim3(HH * 4), lds, e->stream, CARGS, sa); break;
@@ -1015,25 +1040,23 @@ static void launch_coop_no(gpe_engine* e, Batch& b, unsigned grid, size_t lds) {
 #undef CARGS
 }
 template <int HH, int CC, int EE>
-static void launch_f_backward_coop(gpe_engine* e, Batch& b, unsigned grid, size_t lds) {
-    {
+static void launch_f_backward_coop(gpe_engine* e, Batch& b, unsigned grid, size_t lds, const SeedArgs* seeds) {
 #ifdef GPE_FAST_BUILD
-        launch_coop_no<HH, CC, EE, 1>(e, b, grid, lds);
+    launch_coop_no<HH, CC, EE, 1>(e, b, grid, lds, seeds);
 #else
-        if (e->nd.n_out == 1) launch_coop_no<HH, CC, EE, 1>(e, b, grid, lds);
-        else launch_coop_no<HH, CC, EE, 2>(e, b, grid, lds);
+    if (e->nd.n_out == 1) launch_coop_no<HH, CC, EE, 1>(e, b, grid, lds, seeds);
+    else launch_coop_no<HH, CC, EE, 2>(e, b, grid, lds, seeds);
 #endif
-    }
 }
 template <int HH, int CC, int EE>
-static void launch_f_backward(gpe_engine* e, Batch& b, unsigned grid, size_t lds) {
+static void launch_f_backward(gpe_engine* e, Batch& b, unsigned grid, size_t lds, const SeedArgs* seeds) {
     if constexpr (HH > 64) {
         B_LAUNCH(HH, CC, EE, false, 0, grid, 256, lds, e->nd, e->theta, e->WpkT, b.pts, b.stored, b.Ob, e->gslab, b.n, b.ld, e->Ppad, e->nslab_g);
         return;
     } else {
 #define BARGS e->nd, e->theta, e->WpkT, b.pts, b.stored, b.Ob, e->gslab, b.n, b.ld, e->Ppad, e->nslab_g
     const int kind = bwd_kind(e, b);
-    if (kind == 3) launch_f_backward_coop<HH, CC, EE>(e, b, grid, lds);
+    if (kind == 3) launch_f_backward_coop<HH, CC, EE>(e, b, grid, lds, seeds);
     else if (kind == 2) {
         switch (e->nd.n_lin - 2) {
             case 1: B_LAUNCH(HH, CC, EE, true, 1, grid, 256, lds, BARGS); break;
@@ -1116,7 +1139,8 @@ static WideCall wide_call(gpe_engine* e, Batch& b) {
 }
 
 // frozen: the parameter set of a frozen orthogonality state instead of the trained one (its packed copies never go stale)
-static int mlp_forward(gpe_engine* e, Batch& b, bool store, const FwdWeights* frozen = nullptr) {
+// head_slots > 0: the head rides in this pass, whose workgroups (that many) each leave a triple in e->head_slots (step_begin only)
+static int mlp_forward(gpe_engine* e, Batch& b, bool store, const FwdWeights* frozen = nullptr, int head_slots = 0) {
     if (b.n <= 0) return GPE_OK;
     const bool mark = e->prof && (&b == &e->main);
     const FwdWeights W = frozen ? *frozen : FwdWeights{e->theta, e->Wpk, e->WpkT};
@@ -1136,20 +1160,20 @@ static int mlp_forward(gpe_engine* e, Batch& b, bool store, const FwdWeights* fr
         }
 #ifdef GPE_FAST_BUILD
         if (e->H != 64 || e->nd.n_out != 1) FAIL(e, GPE_ERR_INVALID, "fast build: only H = 64, n_out = 1 compiled");
-        DISPATCH_FWD(b, launch_f_forward<64, CC, EE>(e, b, grid, store ? 1 : 0, W));
+        DISPATCH_FWD(b, launch_f_forward<64, CC, EE>(e, b, grid, store ? 1 : 0, W, head_slots > 0));
 #else
         if (e->H == 128) {      // wide layers: one wave per SIMD, C <= 5 (checked at create)
             grid = fused_grid(e, b.n, 4, 1);
             switch (b.C * 10 + b.E) {     // wide layers: dim <= 2 (checked at create)
-                case 10: launch_f_forward<128, 1, 0>(e, b, grid, store ? 1 : 0, W); break;
-                case 31: launch_f_forward<128, 3, 1>(e, b, grid, store ? 1 : 0, W); break;
-                case 41: launch_f_forward<128, 4, 1>(e, b, grid, store ? 1 : 0, W); break;
-                case 52: launch_f_forward<128, 5, 2>(e, b, grid, store ? 1 : 0, W); break;
+                case 10: launch_f_forward<128, 1, 0>(e, b, grid, store ? 1 : 0, W, head_slots > 0); break;
+                case 31: launch_f_forward<128, 3, 1>(e, b, grid, store ? 1 : 0, W, head_slots > 0); break;
+                case 41: launch_f_forward<128, 4, 1>(e, b, grid, store ? 1 : 0, W, head_slots > 0); break;
+                case 52: launch_f_forward<128, 5, 2>(e, b, grid, store ? 1 : 0, W, head_slots > 0); break;
                 default: FAIL(e, GPE_ERR_INVALID, "bad channel pair (%d,%d) for H = 128", b.C, b.E);
             }
         }
-        else if (e->H == 64) { DISPATCH_FWD(b, launch_f_forward<64, CC, EE>(e, b, grid, store ? 1 : 0, W)); }
-        else            { DISPATCH_FWD(b, launch_f_forward<32, CC, EE>(e, b, grid, store ? 1 : 0, W)); }
+        else if (e->H == 64) { DISPATCH_FWD(b, launch_f_forward<64, CC, EE>(e, b, grid, store ? 1 : 0, W, head_slots > 0)); }
+        else            { DISPATCH_FWD(b, launch_f_forward<32, CC, EE>(e, b, grid, store ? 1 : 0, W, head_slots > 0)); }
 #endif
         if (mark) prof_mark(e, 0, false);
     } else {
@@ -1186,11 +1210,16 @@ static int bc_join(gpe_engine* e);
 static double bc_count(gpe_engine* e);
 static int launch_tail(gpe_engine* e, bool add_bc);
 static int dp_allreduce_after(gpe_engine* e, void* buf, size_t count, ncclDataType_t dt, hipEvent_t ev);
-// Gradient of one batch into e->grad: assigned (first reverse pass of the step) or accumulated.  close: this is the last reverse pass of the step -- join the boundary batch's side stream, add its
+// Gradient of one batch into e->grad: assigned (first reverse pass of the step) or accumulated.  o.close: this is the last reverse pass of the step -- join the boundary batch's side stream, add its
 // gradient and write the exchange tail (folded into the slab reduction on the fused path)
-static int mlp_backward(gpe_engine* e, Batch& b, bool close = false, bool assign = true) {
+static int mlp_backward(gpe_engine* e, Batch& b, const BwdOpts& o) {
+    const bool close = o.close, assign = o.assign;
     if (b.n <= 0) return close ? launch_tail(e, true) : GPE_OK;
     if (e->path == GPE_PATH_FUSED) {
+        // the seeds the kernel forms add the head triples this step's forward pass left, if it ran the head
+        const SeedArgs sa{e->ph, b.V, b.u, b.Hu, (const double*)e->sums(), e->dsc(), e->n_pde, e->st.head_slots ? (const double*)e->head_slots : nullptr,
+                          e->st.head_slots, e->sums(), e->lsums(), 0};
+        const SeedArgs* seeds = o.seeds_in_kernel ? &sa : nullptr;
         const int kind = bwd_kind(e, b);
         unsigned grid = kind == 3 ? fused_grid(e, b.n, 1, e->coop_wg_per_cu)
                                   : (kind == 2 ? fused_grid(e, b.n, 4, 1) : fused_grid(e, b.n, 4, 2));
@@ -1207,15 +1236,15 @@ static int mlp_backward(gpe_engine* e, Batch& b, bool close = false, bool assign
         } else {
 #ifdef GPE_FAST_BUILD
         if (e->H != 64 || e->nd.n_out != 1) FAIL(e, GPE_ERR_INVALID, "fast build: only H = 64, n_out = 1 compiled");
-        DISPATCH_TRAIN(b, launch_f_backward<64, CC, EE>(e, b, grid, lds));
+        DISPATCH_TRAIN(b, launch_f_backward<64, CC, EE>(e, b, grid, lds, seeds));
 #else
         if (e->H == 128 && kind == 3) {
             grid = fused_grid(e, b.n, 1, 1);
             nred = (int)grid;
             switch (b.C * 10 + b.E) {
-                case 10: launch_f_backward_coop<128, 1, 0>(e, b, grid, lds); break;
-                case 31: launch_f_backward_coop<128, 3, 1>(e, b, grid, lds); break;
-                case 41: launch_f_backward_coop<128, 4, 1>(e, b, grid, lds); break;
+                case 10: launch_f_backward_coop<128, 1, 0>(e, b, grid, lds, seeds); break;
+                case 31: launch_f_backward_coop<128, 3, 1>(e, b, grid, lds, seeds); break;
+                case 41: launch_f_backward_coop<128, 4, 1>(e, b, grid, lds, seeds); break;
                 default: FAIL(e, GPE_ERR_INVALID, "bad channel pair (%d,%d) for H = 128", b.C, b.E);
             }
         }
@@ -1224,14 +1253,14 @@ static int mlp_backward(gpe_engine* e, Batch& b, bool close = false, bool assign
             nred = e->nslab_g;
             HIPCHK(e, hipMemsetAsync(e->gslab, 0, (size_t)e->nslab_g * e->Ppad * sizeof(float), e->stream));
             switch (b.C * 10 + b.E) {
-                case 10: launch_f_backward<128, 1, 0>(e, b, grid, lds); break;
-                case 31: launch_f_backward<128, 3, 1>(e, b, grid, lds); break;
-                case 41: launch_f_backward<128, 4, 1>(e, b, grid, lds); break;
+                case 10: launch_f_backward<128, 1, 0>(e, b, grid, lds, seeds); break;
+                case 31: launch_f_backward<128, 3, 1>(e, b, grid, lds, seeds); break;
+                case 41: launch_f_backward<128, 4, 1>(e, b, grid, lds, seeds); break;
                 default: FAIL(e, GPE_ERR_INVALID, "bad channel pair (%d,%d) for H = 128", b.C, b.E);
             }
         }
-        else if (e->H == 64) { DISPATCH_TRAIN(b, launch_f_backward<64, CC, EE>(e, b, grid, lds)); }
-        else            { DISPATCH_TRAIN(b, launch_f_backward<32, CC, EE>(e, b, grid, lds)); }
+        else if (e->H == 64) { DISPATCH_TRAIN(b, launch_f_backward<64, CC, EE>(e, b, grid, lds, seeds)); }
+        else            { DISPATCH_TRAIN(b, launch_f_backward<32, CC, EE>(e, b, grid, lds, seeds)); }
 #endif
         }
         if (mark) prof_mark(e, 1, false);
@@ -1240,21 +1269,21 @@ static int mlp_backward(gpe_engine* e, Batch& b, bool close = false, bool assign
         if (close) {
             int rc = bc_join(e);
             if (rc) return rc;
-            if (e->bc_inflight) add = e->grad_bc;
-            e->bc_inflight = false;
+            if (e->st.bc_inflight) add = e->grad_bc;
+            e->st.bc_inflight = false;
         }
-        if (close && assign && e->fu_want && e->fuse_update && e->upd_ticket && !e->upd_snap && e->update_cache && e->P <= 13 * 1024 && !e->comm) {
+        if (close && assign && o.update_may_fuse && e->fuse_update && e->upd_ticket && !e->upd_snap && e->update_cache && e->P <= 13 * 1024 && !e->comm) {
             const int n_pack = (e->nd.n_lin - 2) * e->H * e->H;
             hipLaunchKernelGGL(k_reduce_update, dim3(cdiv(e->P, 64)), dim3(1024), 0, e->stream, e->gslab, nred, e->Ppad, e->P, e->grad, add,
                                (const double*)e->dsc(), e->upd_ticket, e->theta, e->am, e->av, (const double*)e->sums(), (const double*)e->lsums(),
                                e->ph, e->oc, e->od, e->hist, e->cap, e->last, bc_count(e), e->nd, e->H, e->Wpk, e->WpkT, n_pack, e->dbl,
                                (int)(S_COUNT + LS_COUNT + 4), ((e->fwd_b6 || e->bwd_b6 || e->H > 64) ? 1 : 2));
-            e->fu_done = true;
-        } else if (close && assign && e->fu_want && e->split_update && e->upd_snap_small && !e->upd_snap && !e->comm && !e->ext_exchange &&
+            e->st.update_done = true;
+        } else if (close && assign && o.update_may_fuse && e->split_update && e->upd_snap_small && !e->upd_snap && !e->comm && !e->ext_exchange &&
                    !e->fwd_b6 && !e->bwd_b6 && e->H <= 64) {
             hipLaunchKernelGGL(k_grad_reduce_part, dim3(UPD_G), dim3(1024), 0, e->stream, e->gslab, nred, e->Ppad, e->P, e->grad, add,
                                (const double*)e->dsc(), (const double*)e->sums(), (const double*)e->lsums(), (const OptDev*)e->od, e->upd_snap_small);
-            e->fu_parts = true;
+            e->st.update_parts = true;
         } else
         hipLaunchKernelGGL(k_grad_reduce, dim3(cdiv(e->P, 64)), dim3(1024), 0, e->stream, e->gslab, nred, e->Ppad,
                            e->P, e->grad, add, close ? (const double*)e->dsc() : (const double*)nullptr, assign ? 1 : 0);
@@ -1303,7 +1332,7 @@ static int mlp_backward(gpe_engine* e, Batch& b, bool close = false, bool assign
                 DISPATCH_TRAIN(b, hipLaunchKernelGGL((g_bwd_weight<CC, EE, 1, G_KB>), gw, dim3(256), 0, e->stream, nd, lin, b.pts, Sprev,
                                                     Zb, e->grad, b.n, b.ld));
             }
-            if (e->dp_bucket && close) {
+            if (o.bucketed && close) {
                 // data-parallel step: this map's gradient slice (weights + bias, contiguous) is final -> all-reduce it on the
                 // exchange stream behind the remaining reverse pass (output map first)
                 int rcb = dp_allreduce_after(e, e->grad + nd.offW[lin], (size_t)K * Ho + Ho, ncclFloat, e->ev_bucket[lin]);
@@ -2005,8 +2034,8 @@ static int sampler_launch(gpe_engine* e, int64_t draw) {
 // before the first kernel of a step: the set this step runs on.  A redraw leaves the engine as gpe_bind_points of the new set would
 // (the step starts with k_begin; Phys and the merged-boundary Pts depend on the point count and the pointers only, which stay) --
 // without that call's two synchronisations.
-static int sampler_before_step(gpe_engine* e) {
-    if (e->smp_every <= 0 || e->capturing) return GPE_OK;
+static int sampler_before_step(gpe_engine* e, bool capturing) {
+    if (e->smp_every <= 0 || capturing) return GPE_OK;
     const int64_t want = e->smp_draw0 + e->smp_steps / e->smp_every;
     if (want == e->smp_held) return GPE_OK;
     e->acc_clean = false;
@@ -2431,35 +2460,34 @@ static int launch_head_pde(gpe_engine* e) {
     HIPCHK(e, hipGetLastError());
     return GPE_OK;
 }
-static int launch_seed_pde(gpe_engine* e, float* d_resid, int want_seeds) {
+// head_slots: the forward pass left that many head triples (StepState::head_slots), which this kernel adds into the sums; 0: k_head_pde did
+static int launch_seed_pde(gpe_engine* e, float* d_resid, int want_seeds, int head_slots) {
     Batch& b = e->main;
     dim3 g(head_grid(e, e->n_pde));
     DISPATCH_TRAIN(b, hipLaunchKernelGGL((k_seed_pde<CC, EE>), g, dim3(e->head_threads), 0, e->stream, e->ph, b.pts, b.V,
                                         (const float* const*)e->orth_dev, b.u, b.Hu, b.ux, e->sums(), b.Ob, d_resid, e->dsc(),
-                                        e->n_pde, b.ld, want_seeds, e->fh_now ? (const double*)e->head_slots : (const double*)nullptr,
-                                        e->fh_now ? e->fh_nslots : 0, e->sums(), e->lsums()));      // collocation rows only; boundary rows were seeded by the head kernel
+                                        e->n_pde, b.ld, want_seeds, head_slots ? (const double*)e->head_slots : (const double*)nullptr,
+                                        head_slots, e->sums(), e->lsums()));      // collocation rows only; boundary rows were seeded by the head kernel
     HIPCHK(e, hipGetLastError());
     return GPE_OK;
 }
 
 static int bc_fork(gpe_engine* e, bool with_backward);
-
-int gpe_step_begin(gpe_engine* e) {
-    if (!e) return GPE_ERR_INVALID;
+static int step_begin(gpe_engine* e, StepOpts o) {
     if (e->main.n <= 0) FAIL(e, GPE_ERR_STATE, "step before bind_points");
     if (e->cfg.base_mode >= 0 && e->cfg.base_kind == GPE_BASE_PRECOMPUTED && !e->orth_host[4])
         FAIL(e, GPE_ERR_STATE, "precomputed base requested but gpe_bind_base was not called");
     int rc;
-    e->fh_now = false; e->seedf_now = false; e->fu_done = false; e->fu_parts = false;      // per-step flags: a step that failed half-way must not leave them behind
-    e->phase = 0;
-    if (e->smp_every > 0 && (rc = sampler_before_step(e))) return rc;
+    e->st = StepState{};
+    StepScope seq{e};
+    if ((rc = sampler_before_step(e, o.capturing))) return rc;
     if ((rc = launch_begin(e))) return rc;
     if ((rc = bc_fork(e, true))) return rc;
-    const bool fh = head_in_forward(e);
-    if (fh) e->fh_nslots = (int)(head_fusable_coop(e) ? fused_grid(e, e->main.n, 1, 2) : fused_grid(e, e->main.n, 4, e->fwd_wg_per_cu));
-    e->fh_now = fh;
-    rc = mlp_forward(e, e->main, true);
-    if (!rc && !fh) rc = launch_head_pde(e);
+    // the head rides in the forward kernel, one triple per workgroup of that launch
+    const int slots = !(o.head_may_fuse && head_fusable(e)) ? 0
+                    : (int)(head_fusable_coop(e) ? fused_grid(e, e->main.n, 1, 2) : fused_grid(e, e->main.n, 4, e->fwd_wg_per_cu));
+    rc = mlp_forward(e, e->main, true, nullptr, slots);
+    if (!rc && !slots) rc = launch_head_pde(e);
     if (!rc && e->cfg.w_sym != 0.f) {
         if (!(rc = mlp_forward(e, e->sym, true))) {
             hipLaunchKernelGGL(k_head_sym, dim3(cdiv(e->n_pde, 256)), dim3(256), 0, e->stream, e->ph, e->sym.O, e->sums(),
@@ -2467,79 +2495,72 @@ int gpe_step_begin(gpe_engine* e) {
             if (hipGetLastError() != hipSuccess) { e->err = "k_head_sym launch failed"; rc = GPE_ERR_HIP; }
         }
     }
-    if (rc) { e->fh_now = false; return rc; }
-    e->phase = 1;
-    if (e->smp_every > 0 && !e->capturing) e->smp_steps++;
-    return GPE_OK;
+    if (rc) return rc;
+    e->st.phase = 1; e->st.head_slots = slots;
+    if (e->smp_every > 0 && !o.capturing) e->smp_steps++;
+    return seq.keep();
 }
+int gpe_step_begin(gpe_engine* e) { return e ? step_begin(e, StepOpts{}) : GPE_ERR_INVALID; }
 
 // Boundary batch (refine/harmonic_pinn_simulation.py:197-210): forward, loss + seeds, reverse.  It does not depend on mu, so it
 // is forked onto the side stream at the start of the step and overlaps the collocation batch; its gradient lands in grad_bc
 // and k_tail adds it after the join.
 static int bc_fork(gpe_engine* e, bool with_backward) {
-    e->bc_inflight = false;
+    e->st.bc_inflight = false;
     if (e->bc.n <= 0 || e->cfg.w_bc == 0.f) return GPE_OK;
     int rc = ensure_packed(e);
     if (rc) return rc;
-    hipStream_t s0 = e->stream;
-    float *g0 = e->grad, *sl0 = e->gslab;
     if (e->side) {
-        HIPCHK(e, hipEventRecord(e->ev_fork, s0));
+        HIPCHK(e, hipEventRecord(e->ev_fork, e->stream));
         HIPCHK(e, hipStreamWaitEvent(e->side, e->ev_fork, 0));
-        e->stream = e->side;
     }
-    e->grad = e->grad_bc;
-    if (e->gslab_bc) e->gslab = e->gslab_bc;
-    auto body = [&]() -> int {
-        int r;
-        if ((r = mlp_forward(e, e->bc, true))) return r;
+    {
+        Redirect to_side(e, e->side ? e->side : e->stream, e->grad_bc, e->gslab_bc ? e->gslab_bc : e->gslab);
+        if ((rc = mlp_forward(e, e->bc, true))) return rc;
         hipLaunchKernelGGL(k_head_seed_bc, dim3(cdiv(e->bc.n, 256)), dim3(256), 0, e->stream, e->ph, e->base_norm, e->bc.pts.a,
                            e->bc_target, e->bc.O, e->bc.Ob, e->lsums(), e->bc.n, e->bc.ld);
         HIPCHK(e, hipGetLastError());
-        if (with_backward && (r = mlp_backward(e, e->bc))) return r;
-        return GPE_OK;
-    };
-    rc = body();
-    e->stream = s0; e->grad = g0; e->gslab = sl0;
-    if (rc) return rc;
+        if (with_backward && (rc = mlp_backward(e, e->bc, BwdOpts{}))) return rc;
+    }
     if (e->side) HIPCHK(e, hipEventRecord(e->ev_join, e->side));
-    e->bc_inflight = true;
+    e->st.bc_inflight = true;
     return GPE_OK;
 }
 static int bc_join(gpe_engine* e) {
-    if (e->bc_inflight && e->side) HIPCHK(e, hipStreamWaitEvent(e->stream, e->ev_join, 0));
+    if (e->st.bc_inflight && e->side) HIPCHK(e, hipStreamWaitEvent(e->stream, e->ev_join, 0));
     return GPE_OK;
 }
 static int launch_tail(gpe_engine* e, bool add_bc) {
-    const float* add = (add_bc && e->bc_inflight) ? e->grad_bc : nullptr;
+    const float* add = (add_bc && e->st.bc_inflight) ? e->grad_bc : nullptr;
     hipLaunchKernelGGL(k_tail, dim3(add ? cdiv(e->P, 256) : 1), dim3(256), 0, e->stream, e->grad, add, e->P, e->dsc());
     HIPCHK(e, hipGetLastError());
-    e->bc_inflight = false;
+    e->st.bc_inflight = false;
     return GPE_OK;
 }
 
-int gpe_step_backward(gpe_engine* e) {
-    if (!e) return GPE_ERR_INVALID;
-    if (e->phase != 1) FAIL(e, GPE_ERR_STATE, "step_backward without step_begin");
-    int rc;
+// bucketed: the synchronous data-parallel step all-reduces every finished layer of the generic set behind the remaining reverse pass
+static int step_backward(gpe_engine* e, StepOpts o, bool bucketed = false) {
+    if (e->st.phase != 1) FAIL(e, GPE_ERR_STATE, "step_backward without step_begin");
+    StepScope seq{e};
+    int rc = GPE_OK;
     const bool with_sym = e->cfg.w_sym != 0.f;
     // small batches of the common problem class (real psi, no orthogonality / Riesz / symmetry terms) on the pipelined reverse
     // kernel: the seeds are formed inside it
-    e->seedf_now = seed_in_reverse(e);
-    if (!e->seedf_now && (rc = launch_seed_pde(e, nullptr, 1))) return rc;
-    rc = mlp_backward(e, e->main, /*close=*/!with_sym);
-    e->seedf_now = false;
-    e->fh_now = false;
+    const BwdOpts bo{/*close=*/!with_sym, /*assign=*/true, seed_in_reverse(e), o.update_may_fuse, bucketed};
+    if (!bo.seeds_in_kernel && (rc = launch_seed_pde(e, nullptr, 1, e->st.head_slots))) return rc;
+    rc = mlp_backward(e, e->main, bo);
+    e->st.head_slots = 0;
     if (rc) return rc;
     if (with_sym) {
         hipLaunchKernelGGL(k_seed_sym, dim3(cdiv(e->n_pde, 256)), dim3(256), 0, e->stream, e->ph, e->sym.O, e->sym.Ob,
                            e->n_pde, e->sym.ld);
         HIPCHK(e, hipGetLastError());
-        if ((rc = mlp_backward(e, e->sym, /*close=*/true, /*assign=*/false))) return rc;
+        if ((rc = mlp_backward(e, e->sym, BwdOpts{/*close=*/true, /*assign=*/false}))) return rc;
     }
-    e->phase = 2;
-    return GPE_OK;
+    e->st.phase = 2;
+    return seq.keep();
 }
+int gpe_step_backward(gpe_engine* e) { return e ? step_backward(e, StepOpts{}) : GPE_ERR_INVALID; }
 
 static void after_update(gpe_engine* e) {          // host-side mirror of what k_update left behind
     e->acc_clean = true;
@@ -2564,12 +2585,11 @@ static double bc_count(gpe_engine* e) {
     return (nb > 0 && e->cfg.w_bc != 0.f) ? (double)nb * e->nd.n_out : 0.0;
 }
 
-int gpe_step_update(gpe_engine* e) {
-    if (!e) return GPE_ERR_INVALID;
-    if (e->phase != 2) FAIL(e, GPE_ERR_STATE, "step_update without step_backward");
-    if (e->fu_done) { e->fu_done = false; after_update(e); e->phase = 0; return GPE_OK; }      // the slab reduction's last workgroup ran it
-    if (e->fu_parts) {          // the slab reduction left partial norms + snapshot: the update on UPD_G workgroups, new weights scattered into the packed copies
-        e->fu_parts = false;
+static int step_update(gpe_engine* e) {
+    if (e->st.phase != 2) FAIL(e, GPE_ERR_STATE, "step_update without step_backward");
+    StepScope seq{e};               // the step ends here
+    if (e->st.update_done) { after_update(e); return GPE_OK; }      // the slab reduction's last workgroup ran it
+    if (e->st.update_parts) {          // the slab reduction left partial norms + snapshot: the update on UPD_G workgroups, new weights scattered into the packed copies
         const int n_pack = (e->nd.n_lin - 2) * e->H * e->H;
         hipLaunchKernelGGL(k_update<true>, dim3(UPD_G), dim3(1024), 0, e->stream, e->P, e->theta, e->am, e->av, (const float*)e->grad,
                            (const double*)e->sums(), (const double*)e->lsums(), e->ph, e->oc, e->od, e->hist, e->cap, e->last, bc_count(e), 1, 0,
@@ -2577,15 +2597,14 @@ int gpe_step_update(gpe_engine* e) {
                            (const UpdSnap*)e->upd_snap_small, 2);
         HIPCHK(e, hipGetLastError());
         after_update(e);
-        e->phase = 0;
         return GPE_OK;
     }
     launch_update(e, e->grad, e->sums(), e->lsums(), bc_count(e), 1, 0, nullptr);
     HIPCHK(e, hipGetLastError());
     after_update(e);
-    e->phase = 0;
     return GPE_OK;
 }
+int gpe_step_update(gpe_engine* e) { return e ? step_update(e) : GPE_ERR_INVALID; }
 
 // ---- pre-training on an analytic target (refine/harmonic_pinn_simulation.py:650-701) ---------------------------------
 int gpe_bind_target(gpe_engine* e, const float* d_target) {
@@ -2602,25 +2621,26 @@ int gpe_mse_begin(gpe_engine* e) {
     if (e->smp_every > 0) FAIL(e, GPE_ERR_STATE, "mse step while a sampler is bound: the target lives on fixed points");
     if (!e->mse_target || e->mse.n <= 0) FAIL(e, GPE_ERR_STATE, "mse step before bind_target");
     int rc;
-    e->fh_now = false; e->seedf_now = false;
+    e->st = StepState{};
+    StepScope seq{e};
     e->mse.pts = Pts{e->ux, nullptr, e->n_pde};
     if ((rc = launch_begin(e))) return rc;
     if ((rc = mlp_forward(e, e->mse, true))) return rc;
     hipLaunchKernelGGL(k_seed_mse, dim3(head_grid(e, e->mse.n, 256)), dim3(256), 0, e->stream, e->ph, e->mse.pts.a, e->mse_target,
                        e->mse.O, e->mse.Ob, e->dsc() + 2, e->mse.n, e->mse.ld);
     HIPCHK(e, hipGetLastError());
-    if ((rc = mlp_backward(e, e->mse, /*close=*/true))) return rc;
-    e->phase = 3;
-    return GPE_OK;
+    if ((rc = mlp_backward(e, e->mse, BwdOpts{/*close=*/true}))) return rc;
+    e->st.phase = 3;
+    return seq.keep();
 }
 
 static int mse_finish(gpe_engine* e, int do_update) {
-    if (e->phase != 3) FAIL(e, GPE_ERR_STATE, "mse update without mse begin");
+    if (e->st.phase != 3) FAIL(e, GPE_ERR_STATE, "mse update without mse begin");
+    StepScope seq{e};
     // sums[S_DEN] must be non-zero for the (unused) Rayleigh quotient of the shared update kernel
     launch_update(e, e->grad, e->sums(), e->lsums(), 0.0, do_update, 1, nullptr);
     HIPCHK(e, hipGetLastError());
     after_update(e);
-    e->phase = 0;
     return GPE_OK;
 }
 
@@ -2755,14 +2775,12 @@ static int dp_join(gpe_engine* e) {       // the compute stream continues after 
 // kernel may run the head (the N = 1 kernels: no k_head_pde); its per-workgroup triples are added by one small launch into the sums
 // the first all-reduce exchanges, and the reverse phase then reads the GLOBAL sums like after k_head_pde.
 static int dp_begin(gpe_engine* e) {
-    e->fh_want = true;
-    int rc = gpe_step_begin(e);
-    e->fh_want = false;
+    int rc = step_begin(e, StepOpts{/*head_may_fuse=*/true});
     if (rc) return rc;
-    if (e->fh_now) {
-        hipLaunchKernelGGL(k_slots_to_sums, dim3(1), dim3(64), 0, e->stream, (const double*)e->head_slots, e->fh_nslots, e->sums(), e->lsums());
+    if (e->st.head_slots) {
+        hipLaunchKernelGGL(k_slots_to_sums, dim3(1), dim3(64), 0, e->stream, (const double*)e->head_slots, e->st.head_slots, e->sums(), e->lsums());
         HIPCHK(e, hipGetLastError());
-        e->fh_now = false;                          // consumers take the (all-reduced) sums, not the local slots
+        e->st.head_slots = 0;                       // consumers take the (all-reduced) sums, not the local slots
     }
     return GPE_OK;
 }
@@ -2777,27 +2795,22 @@ static int step_dp_async(gpe_engine* e) {
     int rc;
     const int cur = (int)(e->async_t & 1), prv = cur ^ 1;
     float* gcur = (e->async_t & 1) ? e->grad_alt : e->grad;       // the two gradient buffers alternate
-    float* const g_home = e->grad;
-    e->grad = gcur;                                   // this step's buffer: zeroed by k_begin (generic set), written by the reverse pass;
-                                                      // the other one holds g_{t-1} until this step's update has applied it
     e->acc_clean = e->acc_clean && e->path == GPE_PATH_FUSED;
-    rc = dp_begin(e);
-    if (!rc) rc = dp_allreduce_after(e, e->sums(), S_COUNT, ncclDouble, e->ev_x0);
-    if (!rc) rc = dp_join(e);
-    if (!rc) rc = gpe_step_backward(e);
-    if (!rc) {
-        hipError_t st;
-        if ((st = hipEventRecord(e->ev_x0, e->stream)) != hipSuccess || (st = hipStreamWaitEvent(e->comm_stream, e->ev_x0, 0)) != hipSuccess) {
-            e->grad = g_home;
-            FAIL(e, GPE_ERR_HIP, "stale-gradient exchange: %s", hipGetErrorString(st));
-        }
-        ncclResult_t nr = e->rccl.AllReduce(gcur, gcur, (size_t)e->P + GT_COUNT, ncclFloat, ncclSum, e->comm, e->comm_stream);
-        if (nr != ncclSuccess) { e->grad = g_home; FAIL(e, GPE_ERR_HIP, "ncclAllReduce: %s", e->rccl.GetErrorString(nr)); }
+    StepScope seq{e};
+    {
+        // this step's buffer: zeroed by k_begin (generic set), written by the reverse pass; the other one holds g_{t-1} until this
+        // step's update has applied it
+        Redirect to_cur(e, e->stream, gcur, e->gslab);
+        if ((rc = dp_begin(e))) return rc;
+        if ((rc = dp_allreduce_after(e, e->sums(), S_COUNT, ncclDouble, e->ev_x0))) return rc;
+        if ((rc = dp_join(e))) return rc;
+        if ((rc = step_backward(e, StepOpts{}))) return rc;
+        HIPCHK(e, hipEventRecord(e->ev_x0, e->stream));
+        HIPCHK(e, hipStreamWaitEvent(e->comm_stream, e->ev_x0, 0));
+        RCCLCHK(e, e->rccl.AllReduce(gcur, gcur, (size_t)e->P + GT_COUNT, ncclFloat, ncclSum, e->comm, e->comm_stream));
         e->dp_collectives++;
         (void)hipEventRecord(e->ev_g[cur], e->comm_stream);
     }
-    e->grad = g_home;
-    if (rc) return rc;
     float* gprev = (prv == 1) ? e->grad_alt : e->grad;
     const int apply = e->async_t > 0;
     HIPCHK(e, hipStreamWaitEvent(e->stream, e->ev_g[apply ? prv : cur], 0));     // step 0 only records: it reads its own (reduced) tail
@@ -2805,7 +2818,6 @@ static int step_dp_async(gpe_engine* e) {
                   apply ? (const double*)(e->dbl_prev + S_COUNT) : (const double*)e->lsums(), bc_count(e), apply, 0, e->dbl_prev);
     HIPCHK(e, hipGetLastError());
     after_update(e);
-    e->phase = 0;
     e->async_t++;
     return GPE_OK;
 }
@@ -2832,9 +2844,10 @@ int gpe_step_dp(gpe_engine* e) {
     if (!e->comm) FAIL(e, GPE_ERR_STATE, "gpe_step_dp before gpe_comm_init");
     if (e->async_grad) return step_dp_async(e);
     int rc;
+    StepScope seq{e};
     if ((rc = dp_begin(e))) return rc;
     // layer buckets need every map's gradient to be final when its weight kernel ends: no second batch adding to it later
-    const bool bucketed = e->path == GPE_PATH_GENERIC && e->cfg.w_sym == 0.f && !e->bc_inflight;
+    const bool bucketed = e->path == GPE_PATH_GENERIC && e->cfg.w_sym == 0.f && !e->st.bc_inflight;
     // Fused / wide kernel sets: the next kernel needs each all-reduce's result at once and nothing else is enqueued meanwhile, so the
     // collective goes onto the COMPUTE stream itself -- no event hop to the exchange stream and back (each cross-stream dependency
     // costs several microseconds on this runtime: 4 hops were most of the 35-40 us a world-1 step lost against the plain step,
@@ -2844,16 +2857,13 @@ int gpe_step_dp(gpe_engine* e) {
     if (inl) rc = dp_allreduce_inline(e, e->sums(), S_COUNT, ncclDouble);
     else if (!(rc = dp_allreduce_after(e, e->sums(), S_COUNT, ncclDouble, e->ev_x0))) rc = dp_join(e);
     if (rc) return rc;
-    e->dp_bucket = bucketed;
-    rc = gpe_step_backward(e);
-    e->dp_bucket = false;
-    if (rc) return rc;
+    if ((rc = step_backward(e, StepOpts{}, bucketed))) return rc;
     if (bucketed) rc = dp_allreduce_after(e, e->grad + e->P, GT_COUNT, ncclFloat, e->ev_x0);      // exchange tail (sum r^2)
     else if (inl) rc = dp_allreduce_inline(e, e->grad, (size_t)e->P + GT_COUNT, ncclFloat);
     else rc = dp_allreduce_after(e, e->grad, (size_t)e->P + GT_COUNT, ncclFloat, e->ev_x0);
     if (rc) return rc;
     if (!inl && (rc = dp_join(e))) return rc;
-    return gpe_step_update(e);
+    return step_update(e);
 }
 
 int gpe_run_dp(gpe_engine* e, int64_t n_steps) {
@@ -2896,18 +2906,19 @@ int gpe_read_history(gpe_engine* e, int64_t first, int64_t count, gpe_scalars* o
     return GPE_OK;
 }
 
+// One whole step: begin, backward and update enqueued back to back (callers pass head_may_fuse and update_may_fuse: the head may ride
+// in the forward kernel, the update in the slab reduction).  A phase that fails clears the per-step record itself.
+static int whole_step(gpe_engine* e, StepOpts o) {
+    int rc = step_begin(e, o);
+    if (!rc) rc = step_backward(e, o);
+    if (!rc) rc = step_update(e);
+    return rc;
+}
+
 int gpe_step(gpe_engine* e, gpe_scalars* out) {
     int rc;
     if (!e) return GPE_ERR_INVALID;
-    e->fh_want = true;                            // begin and backward are enqueued back to back: the head may ride in the forward kernel
-    rc = gpe_step_begin(e);
-    e->fh_want = false;
-    if (rc) return rc;
-    e->fu_want = true;                            // ... and backward and update: the update may ride in the slab reduction
-    rc = gpe_step_backward(e);
-    e->fu_want = false;
-    if (rc) { e->fu_done = false; e->fu_parts = false; return rc; }
-    if ((rc = gpe_step_update(e))) return rc;
+    if ((rc = whole_step(e, StepOpts{/*head_may_fuse=*/true, /*update_may_fuse=*/true}))) return rc;
     if ((rc = monitor_after_steps(e, 1))) return rc;
     if (out) return gpe_read_scalars(e, out);
     return GPE_OK;
@@ -2940,28 +2951,17 @@ static int graph_build(gpe_engine* e) {
     graph_drop(e);
     if (!e->cap_stream && hipStreamCreateWithFlags(&e->cap_stream, hipStreamNonBlocking) != hipSuccess) return GPE_ERR_HIP;
     std::vector<char> key = graph_key_of(e);
-    hipStream_t s0 = e->stream;
-    e->stream = e->cap_stream;
     e->packed_dirty = true;                       // the captured step always starts with k_begin
     e->acc_clean = false;
-    e->capturing = true;                          // a redraw is never recorded: a replay runs on whatever set the buffer holds
     hipGraph_t g = nullptr;
     int rc = GPE_OK;
-    if (hipStreamBeginCapture(e->cap_stream, hipStreamCaptureModeThreadLocal) != hipSuccess) { e->stream = s0; e->capturing = false; return GPE_ERR_HIP; }
+    Redirect to_capture(e, e->cap_stream, e->grad, e->gslab);       // (nothing below enqueues on the caller's stream)
+    if (hipStreamBeginCapture(e->cap_stream, hipStreamCaptureModeThreadLocal) != hipSuccess) return GPE_ERR_HIP;
     // graph_steps consecutive steps per graph: ONE hipGraphLaunch then enqueues all their kernels -- at the reference's batch sizes the
     // host's ~7 us per launch is as long as the kernels themselves (a one-step graph costs more per replay than it saves)
-    for (int sidx = 0; sidx < e->graph_steps && !rc; ++sidx) {
-        e->fh_want = true;
-        rc = gpe_step_begin(e);
-        e->fh_want = false;
-        if (!rc) { e->fu_want = true; rc = gpe_step_backward(e); e->fu_want = false; }
-        if (!rc) rc = gpe_step_update(e);
-        e->fu_done = false; e->fu_parts = false;
-    }
+    // (a redraw is never recorded: a replay runs on whatever set the buffer holds)
+    for (int sidx = 0; sidx < e->graph_steps && !rc; ++sidx) rc = whole_step(e, StepOpts{/*head_may_fuse=*/true, /*update_may_fuse=*/true, /*capturing=*/true});
     hipError_t st = hipStreamEndCapture(e->cap_stream, &g);
-    e->stream = s0;
-    e->capturing = false;
-    e->phase = 0;
     e->packed_dirty = true;                       // nothing ran during capture
     e->acc_clean = false;
     if (rc || st != hipSuccess || !g) { if (g) (void)hipGraphDestroy(g); (void)hipGetLastError(); return rc ? rc : GPE_ERR_HIP; }
@@ -2987,13 +2987,13 @@ int gpe_run(gpe_engine* e, int64_t n_steps) {
                 if (e->smp_every > 0) room = std::min(room, e->smp_every - e->smp_steps % e->smp_every);
                 if (room >= e->graph_steps) {
                     if (e->smp_every > 0) {       // the redraw a replay may start with is enqueued here, outside the graph
-                        int rc = sampler_before_step(e);
+                        int rc = sampler_before_step(e, /*capturing=*/false);
                         if (rc) return rc;
                         e->smp_steps += e->graph_steps;
                     }
                     HIPCHK(e, hipGraphLaunch(e->graph_exec, e->stream));
                     after_update(e);
-                    e->phase = 0;
+                    e->st = StepState{};
                     done += e->graph_steps;
                     int rc = monitor_after_steps(e, e->graph_steps);
                     if (rc) return rc;
@@ -3022,7 +3022,8 @@ int gpe_residual(gpe_engine* e, gpe_scalars* out, float* d_psi, float* d_resid) 
     if (!e || !out) return GPE_ERR_INVALID;
     if (e->main.n <= 0) FAIL(e, GPE_ERR_STATE, "residual before bind_points");
     int rc;
-    e->fh_now = false; e->seedf_now = false;      // forward-only evaluation: k_head_pde forms the sums, never the slots of an earlier step
+    e->st = StepState{};                          // forward-only evaluation: k_head_pde forms the sums, never the slots of an earlier step
+    StepScope seq{e};
     if ((rc = launch_begin(e, /*force=*/true))) return rc;      // no reverse pass here: the gradient buffer must read zero
     if ((rc = mlp_forward(e, e->main, false))) return rc;
     if ((rc = launch_head_pde(e))) return rc;
@@ -3031,7 +3032,7 @@ int gpe_residual(gpe_engine* e, gpe_scalars* out, float* d_psi, float* d_resid) 
         hipLaunchKernelGGL(k_head_sym, dim3(cdiv(e->n_pde, 256)), dim3(256), 0, e->stream, e->ph, e->sym.O, e->sums(),
                            e->n_pde, e->sym.ld);
     }
-    if ((rc = launch_seed_pde(e, d_resid, 0))) return rc;
+    if ((rc = launch_seed_pde(e, d_resid, 0, /*head_slots=*/0))) return rc;
     if ((rc = bc_fork(e, false))) return rc;
     if ((rc = bc_join(e))) return rc;
     if (d_psi) hipLaunchKernelGGL(k_copy_psi, dim3(cdiv(e->n_pde, 256)), dim3(256), 0, e->stream, e->main.u, d_psi, e->n_pde,
@@ -3040,7 +3041,6 @@ int gpe_residual(gpe_engine* e, gpe_scalars* out, float* d_psi, float* d_resid) 
     launch_update(e, e->grad, e->sums(), e->lsums(), bc_count(e), 0, 0, nullptr);
     HIPCHK(e, hipGetLastError());
     after_update(e);
-    e->phase = 0;
     HIPCHK(e, hipMemcpyAsync(out, e->last, sizeof *out, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));
     return GPE_OK;
