@@ -27,6 +27,7 @@ ENV_NONE, ENV_SIN = 0, 1
 RIESZ_PAPER, RIESZ_SUM, RIESZ_VARIATIONAL = 0, 1, 2
 NET_MLP, NET_RESIDUAL = 0, 1
 LAMBDA_RAYLEIGH, LAMBDA_ENERGY = 0, 1
+KEEP_NONE, KEEP_RES_RMS, KEEP_ENERGY = 0, 1, 2
 
 
 class gpe_config(C.Structure):
@@ -121,6 +122,9 @@ SYMBOLS = {
     "gpe_observables": (_int, [_vp, _vp, _i64, _vp, _f, _P(gpe_observables)]),
     "gpe_bind_monitor": (_int, [_vp, _vp, _i64, _vp, _f, _i64, C.c_int32]),
     "gpe_read_monitor": (_int, [_vp, _i64, _i64, _P(gpe_observables), _P(_i64)]),
+    "gpe_bind_keeper": (_int, [_vp, _int, C.c_double, _i64]),
+    "gpe_keeper_read": (_int, [_vp, _vp, C.c_size_t, _P(gpe_observables), _P(_i64), _P(_i64), _P(_i64), _P(_int)]),
+    "gpe_keeper_restore": (_int, [_vp]),
     "gpe_step_begin": (_int, [_vp]),
     "gpe_step_backward": (_int, [_vp]),
     "gpe_step_update": (_int, [_vp]),

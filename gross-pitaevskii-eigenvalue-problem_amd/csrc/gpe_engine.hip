@@ -629,6 +629,12 @@ struct gpe_engine {
     int64_t mon_steps = 0, mon_records = 0;           // steps enqueued / records appended since the bind
     int mon_cap = 0;
     struct gpe_observables* mon_ring = nullptr;       // [mon_cap]
+    // keeper (gpe_bind_keeper): the best parameters by one field of the monitor's records; both buffers allocated at the bind
+    int keep_metric = GPE_KEEP_NONE;                  // GPE_KEEP_NONE: no keeper
+    double keep_min_delta = 0.0;
+    int64_t keep_patience = 0;
+    float* theta_best = nullptr;                      // [P], the engine's own padded layout
+    KeepDev* keep_dev = nullptr;
     // device-side stratified sampler (gpe_bind_sampler): the engine owns the collocation points and redraws them in place
     float* smp_x = nullptr;                           // [smp_n][dim]; ux points here while the sampler is bound
     SamplerGrid smp_grid = {};
@@ -1862,7 +1868,7 @@ void gpe_destroy(gpe_engine* e) {
     for (int k = 0; k < GPE_MAX_ORTH; ++k) orth_state_free(e->ost[k]);
     for (hipEvent_t ev : e->ev_pool) (void)hipEventDestroy(ev);
     if (e->ext_exchange) { e->grad = nullptr; e->dbl = nullptr; }
-    void* ps[] = {e->theta, e->am, e->av, e->grad, e->dbl, e->od, e->hist, e->last, (void*)e->orth_dev, e->Wpk, e->WpkT, e->gslab, e->gslab_bc, e->grad_bc, (void*)e->upd_snap, (void*)e->head_slots, (void*)e->upd_ticket, (void*)e->upd_snap_small, (void*)e->obs_buf, (void*)e->obs_out, (void*)e->mon_ring, (void*)e->smp_x};
+    void* ps[] = {e->theta, e->am, e->av, e->grad, e->dbl, e->od, e->hist, e->last, (void*)e->orth_dev, e->Wpk, e->WpkT, e->gslab, e->gslab_bc, e->grad_bc, (void*)e->upd_snap, (void*)e->head_slots, (void*)e->upd_ticket, (void*)e->upd_snap_small, (void*)e->obs_buf, (void*)e->obs_out, (void*)e->mon_ring, (void*)e->smp_x, (void*)e->theta_best, (void*)e->keep_dev};
     for (void* p : ps) if (p) (void)hipFree(p);
     delete e;
 }
@@ -2373,7 +2379,33 @@ int gpe_observables(gpe_engine* e, const float* d_x, int64_t n, const float* d_V
     return GPE_OK;
 }
 
+// ---- keeper: model selection and a patience stop driven by the monitor (gpe_observe.h: k_keep_decide, k_keep_copy) -----------------------
+static void keeper_clear(gpe_engine* e) {             // the stream is idle, or hipFree waits for it
+    e->keep_metric = GPE_KEEP_NONE; e->keep_min_delta = 0.0; e->keep_patience = 0;
+    if (e->theta_best) { (void)hipFree(e->theta_best); e->theta_best = nullptr; }
+    if (e->keep_dev) { (void)hipFree(e->keep_dev); e->keep_dev = nullptr; }
+}
+// "nothing kept": best = +inf, every counter and flag zero
+static int keeper_reset(gpe_engine* e, KeepDev* kd) {
+    KeepDev h;
+    memset(&h, 0, sizeof h);
+    h.best = INFINITY;
+    HIPCHK(e, hipMemcpyAsync(kd, &h, sizeof h, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    return GPE_OK;
+}
+static int keeper_field(int metric) {                 // index of the chosen double in struct gpe_observables
+    return (int)((metric == GPE_KEEP_ENERGY ? offsetof(struct gpe_observables, energy) : offsetof(struct gpe_observables, res_rms)) / sizeof(double));
+}
+static int keeper_state(gpe_engine* e, const char* who, KeepDev* h) {      // synchronises
+    if (e->keep_metric == GPE_KEEP_NONE) FAIL(e, GPE_ERR_STATE, "%s: no keeper bound (gpe_bind_keeper)", who);
+    HIPCHK(e, hipMemcpyAsync(h, e->keep_dev, sizeof *h, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    return GPE_OK;
+}
+
 static void monitor_clear(gpe_engine* e) {
+    keeper_clear(e);                                  // its metric exists on the monitor's points only
     e->mon_every = 0; e->mon_steps = 0; e->mon_records = 0;
     e->mon_x = nullptr; e->mon_V = nullptr; e->mon_n = 0;
     free_batch(e->mon);
@@ -2411,6 +2443,77 @@ int gpe_bind_monitor(gpe_engine* e, const float* d_x, int64_t n, const float* d_
     HIPCHK(e, hipStreamSynchronize(e->stream));
     e->mon_x = d_x; e->mon_V = d_V; e->mon_n = n; e->mon_dv = dv; e->mon_every = every;
     e->mon_steps = 0; e->mon_records = 0;
+    // an armed keeper stays armed and starts again from "nothing kept": its metric is comparable on one point set only
+    if (e->keep_metric != GPE_KEEP_NONE) return keeper_reset(e, e->keep_dev);
+    return GPE_OK;
+}
+
+int gpe_bind_keeper(gpe_engine* e, int metric, double min_delta, int64_t patience) {
+    if (!e) return GPE_ERR_INVALID;
+    if (metric == GPE_KEEP_NONE) {
+        HIPCHK(e, hipStreamSynchronize(e->stream));
+        keeper_clear(e);
+        return GPE_OK;
+    }
+    // validate and allocate first, swap last: a bind that fails leaves the keeper that was there, its kept set included
+    if (metric != GPE_KEEP_RES_RMS && metric != GPE_KEEP_ENERGY) FAIL(e, GPE_ERR_INVALID, "keeper: metric %d is none of GPE_KEEP_RES_RMS, GPE_KEEP_ENERGY", metric);
+    if (e->mon_every <= 0) FAIL(e, GPE_ERR_INVALID, "keeper: needs a bound monitor (gpe_bind_monitor): it judges the monitor's records");
+    if (!(min_delta >= 0.0) || !__builtin_isfinite(min_delta)) FAIL(e, GPE_ERR_INVALID, "keeper: min_delta must be finite and >= 0");
+    if (patience < 0) FAIL(e, GPE_ERR_INVALID, "keeper: patience must be >= 0 (0: never stop)");
+    if (e->comm)
+        FAIL(e, GPE_ERR_INVALID, "keeper: this engine has a communicator (gpe_comm_init): every rank's monitor sees its own points, so the ranks would keep "
+                                 "and stop at different records; data-parallel keepers are not supported");
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    float* tb = e->theta_best; KeepDev* kd = e->keep_dev;             // an armed keeper's buffers are reused (P never changes)
+    if (!tb && hipMalloc((void**)&tb, (size_t)e->P * 4 + 256) != hipSuccess) {
+        (void)hipGetLastError();
+        FAIL(e, GPE_ERR_NOMEM, "keeper: no memory for a copy of %d parameters", e->P);
+    }
+    if (!kd && hipMalloc((void**)&kd, sizeof(KeepDev)) != hipSuccess) {
+        (void)hipGetLastError();
+        if (tb != e->theta_best) (void)hipFree(tb);
+        FAIL(e, GPE_ERR_NOMEM, "keeper: no memory for its state");
+    }
+    int rc = keeper_reset(e, kd);
+    if (rc) {                                                         // (an armed keeper may have lost its counters; its buffers stay)
+        if (tb != e->theta_best) (void)hipFree(tb);
+        if (kd != e->keep_dev) (void)hipFree(kd);
+        return rc;
+    }
+    e->theta_best = tb; e->keep_dev = kd;
+    e->keep_metric = metric; e->keep_min_delta = min_delta; e->keep_patience = patience;
+    return GPE_OK;
+}
+
+int gpe_keeper_read(gpe_engine* e, float* h_flat, size_t n, struct gpe_observables* rec, int64_t* seen, int64_t* kept, int64_t* since_best, int* stopped) {
+    if (!e) return GPE_ERR_INVALID;
+    if (h_flat && (int64_t)n != e->P_user) FAIL(e, GPE_ERR_INVALID, "keeper_read: got %zu floats, model has %d", n, e->P_user);
+    KeepDev h;
+    int rc;
+    if ((rc = keeper_state(e, "keeper_read", &h))) return rc;
+    if (seen) *seen = h.seen;
+    if (kept) *kept = h.kept;
+    if (since_best) *since_best = h.since_best;
+    if (stopped) *stopped = h.stopped;
+    if (!h_flat && !rec) return GPE_OK;
+    if (h.kept == 0) FAIL(e, GPE_ERR_INVALID, "keeper_read: nothing kept yet (%lld records judged, none finite)", (long long)h.seen);
+    if (rec) *rec = h.rec;
+    if (h_flat) {
+        if ((rc = flat_from_device(e, e->theta_best, h_flat))) return rc;
+        HIPCHK(e, hipStreamSynchronize(e->stream));
+    }
+    return GPE_OK;
+}
+
+int gpe_keeper_restore(gpe_engine* e) {
+    if (!e) return GPE_ERR_INVALID;
+    KeepDev h;
+    int rc;
+    if ((rc = keeper_state(e, "keeper_restore", &h))) return rc;
+    if (h.kept == 0) FAIL(e, GPE_ERR_INVALID, "keeper_restore: nothing kept yet");
+    HIPCHK(e, hipMemcpyAsync(e->theta, e->theta_best, (size_t)e->P * 4, hipMemcpyDeviceToDevice, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    e->packed_dirty = true;                           // as gpe_set_params: the packed weight copies are rebuilt before their next use
     return GPE_OK;
 }
 
@@ -2424,6 +2527,13 @@ static int monitor_after_steps(gpe_engine* e, int64_t k) {
     int rc;
     if ((rc = mlp_forward(e, e->mon, false))) return rc;
     if ((rc = launch_observe(e, e->mon, e->mon_x, e->mon_n, e->mon_V, e->mon_dv, e->mon_ring + (e->mon_records % e->mon_cap)))) return rc;
+    if (e->keep_metric != GPE_KEEP_NONE) {            // the record just written, judged and -- if it is the best so far -- theta set aside
+        hipLaunchKernelGGL(k_keep_decide, dim3(1), dim3(64), 0, e->stream, (const struct gpe_observables*)(e->mon_ring + (e->mon_records % e->mon_cap)),
+                           keeper_field(e->keep_metric), e->keep_min_delta, (long long)e->keep_patience, e->keep_dev, e->od);
+        const unsigned g = (unsigned)std::min<int64_t>(cdiv((int64_t)cdiv(e->P, 4), KEEP_THREADS), KEEP_MAX_WG);       // a function of P alone
+        hipLaunchKernelGGL(k_keep_copy, dim3(g), dim3(KEEP_THREADS), 0, e->stream, (const KeepDev*)e->keep_dev, (const float*)e->theta, e->theta_best, e->P);
+        HIPCHK(e, hipGetLastError());
+    }
     e->mon_records++;
     return GPE_OK;
 }

@@ -224,3 +224,55 @@ __global__ __launch_bounds__(OBS_THREADS) void k_obs_finish(Phys ph, const doubl
     o.res_rms = sqrt(dv * r2);
     *dst = o;
 }
+
+// ---- keeper (gpe_bind_keeper): the best parameters by one field of the monitor's records, kept on the device ------------------------------
+// Two launches directly behind k_obs_finish on the engine's stream, never captured:
+//   k_keep_decide  one wave reads the ring slot just written, applies the rule (gpe_pinn/keeper.py restates it), files the record and
+//                  the counters, raises or clears the copy flag, and fires the optimiser's own stop (od->stopped) when patience runs out
+//   k_keep_copy    theta -> theta_best where the flag is raised.  A launch of its own: the stream orders it behind the decision, so no
+//                  workgroup can see a half-written flag; its grid is a function of P alone
+struct KeepDev {
+    double best;                  // metric of the kept record (+inf: nothing kept)
+    struct gpe_observables rec;   // the kept record
+    long long seen, kept, since_best;      // records judged / records kept / records since the last one kept
+    int copy;                     // this record improves: k_keep_copy copies
+    int stopped;                  // the keeper's patience fired the stop
+};
+#define KEEP_REC_DOUBLES ((int)(sizeof(struct gpe_observables) / sizeof(double)))
+#define KEEP_THREADS 256
+#define KEEP_MAX_WG 256
+
+// field: index of the chosen double in the record.  Lower is better; a non-finite candidate is no improvement.
+__global__ __launch_bounds__(64) void k_keep_decide(const struct gpe_observables* __restrict__ slot, int field, double min_delta,
+                                                    long long patience, KeepDev* __restrict__ kd, OptDev* __restrict__ od) {
+    const int t = threadIdx.x;
+    const double* src = (const double*)slot;
+    // every lane reads what the rule needs before any lane writes
+    const double m = src[field], best = kd->best;
+    const double mine = t < KEEP_REC_DOUBLES ? src[t] : 0.0;
+    const long long since = kd->since_best;
+    const bool better = isfinite(m) && m < best - min_delta;
+    if (better && t < KEEP_REC_DOUBLES) ((double*)&kd->rec)[t] = mine;      // the record, one double per lane
+    if (t != 0) return;
+    const long long since_new = better ? 0 : since + 1;
+    if (better) { kd->best = m; kd->kept += 1; }
+    kd->copy = better ? 1 : 0;
+    kd->since_best = since_new;
+    kd->seen += 1;
+    if (patience > 0 && since_new >= patience && !od->stopped) {             // the fields the loss-based early stop uses (k_update)
+        od->stopped = 1; od->stop_step = od->step;
+        kd->stopped = 1;
+    }
+}
+
+// P floats, 16 bytes per access where both pointers allow it, the last P % 4 (or all of them) one by one
+__global__ __launch_bounds__(KEEP_THREADS) void k_keep_copy(const KeepDev* __restrict__ kd, const float* __restrict__ theta,
+                                                            float* __restrict__ theta_best, int P) {
+    if (!kd->copy) return;
+    const bool wide = ((((uintptr_t)theta) | ((uintptr_t)theta_best)) & 15) == 0;
+    const int n4 = wide ? P / 4 : 0;
+    const float4* s4 = (const float4*)theta;
+    float4* d4 = (float4*)theta_best;
+    for (int i = blockIdx.x * KEEP_THREADS + threadIdx.x; i < n4; i += gridDim.x * KEEP_THREADS) d4[i] = s4[i];
+    for (int i = 4 * n4 + blockIdx.x * KEEP_THREADS + threadIdx.x; i < P; i += gridDim.x * KEEP_THREADS) theta_best[i] = theta[i];
+}

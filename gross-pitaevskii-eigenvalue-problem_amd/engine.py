@@ -391,19 +391,24 @@ class Engine:
         self._keep[f"orth{k}"] = t
         self._chk(self.lib.gpe_bind_orth(self._h, int(k), C.c_void_p(t.data_ptr()) if t is not None else None))
 
-    def bind_orth_state(self, k: int, params, base_mode: int = -1, perturb_scale: float = 1.0, amplitude: float = 1.0):
+    def bind_orth_state(self, k: int, params, base_mode: int = -1, perturb_scale: float = 1.0, amplitude: float = 1.0, which: str = "last"):
         """Frozen reference state in orthogonality slot k: psi_k = amplitude * (env * perturb_scale * NN_params + phi_base_mode), kept and
         evaluated by the engine on every collocation set it holds -- at the binds and behind every redraw of the sampler -- so that
         an excited state can be trained on sampler-drawn sets.  params: a flat parameter vector of this engine's network, or another
         Engine of the same network, whose get_params() and cfg.base_mode / cfg.perturb_scale are taken (the two keywords are then
-        ignored).  None clears the slot."""
+        ignored); which = "best" takes that engine's kept parameters (best_params(), see bind_keeper) instead of its last.  None clears
+        the slot."""
+        if which not in ("last", "best"):
+            raise ValueError('which: "last" or "best"')
+        if which == "best" and not isinstance(params, Engine):
+            raise ValueError('which="best" needs an Engine (with a keeper) as params')
         if params is None:
             self._chk(self.lib.gpe_bind_orth_state(self._h, int(k), None, 0, -1, 1.0, 1.0))
             self._keep.pop(f"orth{k}", None)
             return
         if isinstance(params, Engine):
             base_mode, perturb_scale = params.cfg.base_mode, params.cfg.perturb_scale
-            params = params.get_params()
+            params = params.best_params() if which == "best" else params.get_params()
         a = np.ascontiguousarray(np.asarray(params, dtype=np.float32).ravel())
         self._chk(self.lib.gpe_bind_orth_state(self._h, int(k), a.ctypes.data_as(C.c_void_p), a.size, int(base_mode),
                                                float(perturb_scale), float(amplitude)))
@@ -578,6 +583,44 @@ class Engine:
         """The same records as one float64 array [count, len(OBSERVABLE_FIELDS)]."""
         arr, count = self._read_monitor_raw(first, count)
         return np.frombuffer(arr, dtype=np.float64).reshape(-1, len(self.OBSERVABLE_FIELDS))[:count].copy()
+
+    # ---- keeper: the best parameters by the held-out monitor, kept on the device (include/gpe_hip.h: gpe_bind_keeper) -------------------
+    KEEP_METRICS = {"res_rms": capi.KEEP_RES_RMS, "energy": capi.KEEP_ENERGY}
+
+    def bind_keeper(self, metric: str = "res_rms", min_delta: float = 0.0, patience: int = 0):
+        """After every monitor record the engine compares `metric` ("res_rms" or "energy", lower is better) with the best so far and, on
+        an improvement by more than min_delta, sets the parameters and the record aside -- on the device, with no host synchronisation.
+        patience > 0: training stops (as by stop_tol / stop_patience) after that many records in a row without improvement.  Needs
+        bind_monitor first; keeper.select restates the rule."""
+        if metric not in self.KEEP_METRICS:
+            raise ValueError(f"metric: one of {sorted(self.KEEP_METRICS)}")
+        self._chk(self.lib.gpe_bind_keeper(self._h, self.KEEP_METRICS[metric], float(min_delta), int(patience)))
+
+    def clear_keeper(self):
+        self._chk(self.lib.gpe_bind_keeper(self._h, capi.KEEP_NONE, 0.0, 0))
+
+    def keeper_state(self) -> dict:
+        """dict(seen, kept, since_best, stopped): records judged, records kept, records since the last one kept, and whether the keeper's
+        patience stopped the optimiser; synchronises."""
+        seen, kept, since, stopped = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int()
+        self._chk(self.lib.gpe_keeper_read(self._h, None, 0, None, C.byref(seen), C.byref(kept), C.byref(since), C.byref(stopped)))
+        return dict(seen=int(seen.value), kept=int(kept.value), since_best=int(since.value), stopped=bool(stopped.value))
+
+    def best_params(self) -> np.ndarray:
+        """The kept parameters (layout of get_params); GPEError while nothing is kept."""
+        a = np.empty(self.n_params, dtype=np.float32)
+        self._chk(self.lib.gpe_keeper_read(self._h, a.ctypes.data_as(C.c_void_p), a.size, None, None, None, None, None))
+        return a
+
+    def best_record(self) -> dict:
+        """The monitor record of the kept parameters, as read_monitor gives records."""
+        out = capi.gpe_observables()
+        self._chk(self.lib.gpe_keeper_read(self._h, None, 0, C.byref(out), None, None, None, None))
+        return out.as_dict()
+
+    def restore_best(self):
+        """The kept parameters become the engine's parameters; Adam moments, scheduler state and the stop flag stay."""
+        self._chk(self.lib.gpe_keeper_restore(self._h))
 
     # ---- pre-training on an analytic target (refine/harmonic_pinn_simulation.py:650-701) -----------------------------------
     def bind_target(self, target):

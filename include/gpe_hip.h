@@ -299,6 +299,36 @@ int gpe_bind_monitor(gpe_engine* e, const float* d_x, int64_t n, const float* d_
  * Only the newest `capacity` records survive: an older one is GPE_ERR_INVALID.  count == 0 with out == NULL just asks. */
 int gpe_read_monitor(gpe_engine* e, int64_t first, int64_t count, struct gpe_observables* out, int64_t* available);
 
+/* ---- keeper: the best parameters by the held-out monitor, kept on the device, and a patience stop (no reference counterpart: the
+ * reference returns what its last epoch left, and its early stop, refine/...:389-400, watches the training loss) -----------------------
+ * Replaces the host loop gpe_run(every) / gpe_read_monitor / gpe_get_params / compare, which costs a synchronisation and a copy of all
+ * parameters per monitor step.  Directly behind every monitor record two kernels run on the engine's stream (never captured, nothing
+ * synchronises, nothing is allocated): with m the chosen field of the record and best = +inf at the start,
+ *   the record IMPROVES iff  isfinite(m) && m < best - min_delta     (lower is better; a tie or a non-finite m does not)
+ *   on improvement: best = m, the record and the parameters are copied aside, since_best = 0; otherwise since_best += 1
+ *   patience > 0 and since_best >= patience and not yet stopped: the optimiser stops exactly as by stop_tol / stop_patience -- further
+ *   steps leave the parameters untouched, gpe_stop_state reports the optimiser step of that record, gpe_reset_optimizer clears it.
+ * gpe_pinn/keeper.py:select restates the rule in fp64 for anyone replaying a monitor log.
+ * Lifetime: gpe_bind_monitor on an engine with an armed keeper resets it to "nothing kept" and leaves it armed (the metric is comparable
+ * on one point set only); clearing the monitor -- also the drop at a new bind with a precomputed base -- disarms it and frees its
+ * buffers.  gpe_set_params, gpe_reset_optimizer (the counters go on: a run that stopped by patience stops again at the next record
+ * without improvement), gpe_set_gamma, redraws and binds of points leave it alone.  gpe_step_dp / gpe_run_dp and the three-phase
+ * entry points ignore it, as they ignore the monitor. */
+enum { GPE_KEEP_NONE = 0, GPE_KEEP_RES_RMS = 1, GPE_KEEP_ENERGY = 2 };   /* the field judged: res_rms, energy (struct gpe_observables) */
+/* Arms the keeper (a second call re-arms it from "nothing kept"); GPE_KEEP_NONE disarms it.  Allocates a second parameter vector and a
+ * small state block here, never later.  GPE_ERR_INVALID: no monitor bound, an unknown metric, min_delta < 0 or not finite, patience < 0
+ * (0: never stop), or an engine with a communicator (gpe_comm_init: every rank's monitor sees its own points, the ranks would keep and
+ * stop differently).  A bind that fails leaves the keeper that was there, its kept set included. */
+int gpe_bind_keeper(gpe_engine* e, int metric, double min_delta, int64_t patience);
+/* synchronise; the kept parameters (caller's layout, as gpe_get_params; n == gpe_param_count), the kept record, records judged / kept /
+ * judged since the last one kept, and whether the keeper's patience fired the stop.  Any out pointer may be NULL.  GPE_ERR_STATE: no
+ * keeper bound.  With nothing kept yet the counters are filled and a request for h_flat or rec fails with GPE_ERR_INVALID. */
+int gpe_keeper_read(gpe_engine* e, float* h_flat, size_t n, struct gpe_observables* rec, int64_t* seen, int64_t* kept, int64_t* since_best,
+                    int* stopped);
+/* The kept parameters become the engine's parameters (device copy, then as gpe_set_params: the packed weight copies are rebuilt
+ * before their next use).  Adam moments, scheduler state and the stop flag stay as they are.  GPE_ERR_INVALID: nothing kept yet. */
+int gpe_keeper_restore(gpe_engine* e);
+
 /* ---- training step: the epoch body refine/...:328-361 ; nb c10:L84-103 ------------------------------ */
 /* phase 1: forward jets + local sums  -> exchange buffer "sums" */
 int gpe_step_begin(gpe_engine* e);

@@ -138,6 +138,9 @@ for si, g in enumerate(gam):
         run_epochs(ne)
     else:                                   # last stage: tighter normalisation, learning rate stepped down (Adam state kept)
         eng.set_loss_weights(1.0, a.w_bc, a.w_norm_final, 0.0, 0.0, a.w_riesz)
+        if device_sampler:                  # the regular grid as held-out monitor, and a keeper on its res_rms: the best state of this stage, kept on the device
+            eng.bind_monitor(xd, every=a.resample, dv=dv)
+            eng.bind_keeper("res_rms")
         # (the ladder ends at lr x 1e-3: Adam turns gradient round-off into steps of size lr, and mu follows the norm with
         #  d mu / d int ~ 8 -- at lr 1e-5 the norm integral wanders by ~2e-4, i.e. mu by ~1.5e-3 for some seeds)
         for frac, lr in ((0.35, a.lr), (0.2, a.lr * 0.3), (0.15, a.lr * 0.1), (0.1, a.lr * 0.03), (0.1, a.lr * 0.01), (0.05, a.lr * 0.003),
@@ -199,6 +202,16 @@ mu = rows[-1]["mu"]
 _int = rows[-1]["norm"]
 _obs = eng.observables()
 mu_normalised = _obs["mu"]
+# mu of the KEPT set (--device-sampler: the lowest held-out res_rms of the last stage) next to mu of the last step
+kept = None
+if device_sampler and not a.big_grid:
+    ks = eng.keeper_state()
+    if ks["kept"] > 0:
+        rec = eng.best_record()
+        kept = dict(step=rec["step"], mu=rec["mu"], mu_abs_err=abs(rec["mu"] - mu_ref), res_rms=rec["res_rms"], energy=rec["energy"], norm=rec["norm"],
+                    records_seen=ks["seen"], records_kept=ks["kept"], res_rms_last=_obs["res_rms"])
+        print(f"kept set (step {rec['step']:.0f}, {ks['kept']} of {ks['seen']} records improved): mu {rec['mu']:.6f} |err| {kept['mu_abs_err']:.2e} res_rms {rec['res_rms']:.3e}   "
+              f"last step: mu {mu_normalised:.6f} |err| {abs(mu_normalised - mu_ref):.2e} res_rms {_obs['res_rms']:.3e}", flush=True)
 # ---- density on a test grid vs the solver ----
 from oracle import gp_ground_state_nd as nd
 gr = truth["grids"][0]
@@ -223,7 +236,7 @@ out = dict(case=a.case, workload=cs["workload"], layers=cs["layers"], points=int
                          w_riesz=a.w_riesz, w_norm_final=a.w_norm_final, resample=a.resample, sets=a.sets,
                          sampler=("device" if device_sampler else "host_cycle") if a.resample > 0 else "fixed_grid",
                          scheduler="constant lr per stage, fresh Adam per stage; last stage lr x (1, 0.3, 0.1, 0.03, 0.01, 0.003, 0.001)"),
-           energy=rows[-1]["riesz"], energy_ref=truth["energy"], big_grid=big,
+           energy=rows[-1]["riesz"], energy_ref=truth["energy"], big_grid=big, kept=kept,
            observables={k: _obs[k] for k in ("norm", "kin", "pot", "inter", "energy", "mu", "mu_lap", "var_x", "peak_density", "res_rms")})
 path = a.out or os.path.join(ROOT, "gpurun_out", f"accuracy_{cs['workload']}.json")
 os.makedirs(os.path.dirname(path), exist_ok=True)

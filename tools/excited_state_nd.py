@@ -34,6 +34,8 @@ ap.add_argument("--w-orth", type=float, default=100.0)
 ap.add_argument("--w-norm", type=float, default=100.0)
 ap.add_argument("--w-riesz", type=float, default=1.0)
 ap.add_argument("--seed", type=int, default=0)
+ap.add_argument("--keep-best", action="store_true", help="ground state: a keeper (Engine.bind_keeper) on a monitor of the regular grid keeps the parameters of the "
+                "lowest res_rms, and psi_0 is frozen from THEM (which=\"best\") instead of from the last step")
 ap.add_argument("--timing", action="store_true", help="also measure ms/step with and without one frozen state")
 ap.add_argument("--timing-only", action="store_true")
 ap.add_argument("--steps", type=int, default=300, help="--timing: steps per timed pass")
@@ -61,10 +63,14 @@ def make(seed, w_orth):
     return eng
 
 
-def train(eng, tag, t0):
-    """--epochs steps on the device sampler, learning rate stepped down (Adam state kept); the numbers on the REGULAR grid"""
+def train(eng, tag, t0, keep_best=False):
+    """--epochs steps on the device sampler, learning rate stepped down (Adam state kept); the numbers on the REGULAR grid.
+    keep_best: the regular grid as held-out monitor every 10 redraws, and a keeper on its res_rms"""
     eng.bind_sampler(S_LO, S_HI, (n, n), every=a.every, seed=1234 + a.seed, clip=S_CLIP)
     eng.reset_optimizer(a.lr)
+    if keep_best:
+        eng.bind_monitor(torch.as_tensor(X, device="cuda"), every=10 * a.every, dv=dv)
+        eng.bind_keeper("res_rms")
     for frac, lr in ((0.5, a.lr), (0.2, a.lr * 0.3), (0.15, a.lr * 0.1), (0.1, a.lr * 0.03), (0.05, a.lr * 0.01)):
         eng.set_lr(lr)
         eng.run(int(a.epochs * frac))
@@ -89,13 +95,20 @@ if not a.timing_only:
     for i in range(a.pretrain):
         g.lib.gpe_mse_begin(g._h); g.lib.gpe_mse_update(g._h)
     g.bind_target(None)
-    sc0, ob0 = train(g, "ground", t0)
+    sc0, ob0 = train(g, "ground", t0, keep_best=a.keep_best)
+    which = "last"
+    if a.keep_best:                          # the numbers of the kept set replace those of the last step: psi_0 is frozen from it
+        rec, ks = g.best_record(), g.keeper_state()
+        print(f"ground state, last step: mu {ob0['mu']:.6f}  res_rms {ob0['res_rms']:.3e};  kept (step {rec['step']:.0f}, {ks['kept']} of {ks['seen']} records "
+              f"improved): mu {rec['mu']:.6f}  res_rms {rec['res_rms']:.3e}", flush=True)
+        out.update(ground_last=dict(mu=ob0["mu"], res_rms=ob0["res_rms"]), ground_kept_step=rec["step"])
+        ob0, which = rec, "best"
     t_ground = time.time() - t0
     print(f"ground state: mu {ob0['mu']:.6f} (exact 1)  E {ob0['energy']:.6f}  norm {ob0['norm']:.6f}  res_rms {ob0['res_rms']:.3e}  ({t_ground:.0f} s)", flush=True)
 
     t1 = time.time()
     x = make(a.seed + 1, a.w_orth)
-    x.bind_orth_state(0, g, amplitude=1.0 / math.sqrt(ob0["norm"]))
+    x.bind_orth_state(0, g, amplitude=1.0 / math.sqrt(ob0["norm"]), which=which)
     sc1, ob1 = train(x, "excited", t1)
     t_excited = time.time() - t1
     psi0 = x.orth_values(0).double()                                   # the frozen, normalised ground state on the regular grid
