@@ -110,6 +110,9 @@ SYMBOLS = {
     "gpe_bind_points": (_int, [_vp, _vp, _i64, _vp]),
     "gpe_bind_sampler": (_int, [_vp, _P(gpe_sampler_spec)]),
     "gpe_sampler_points": (_int, [_vp, _P(_vp), _P(_i64), _P(_i64)]),
+    "gpe_bind_weights": (_int, [_vp, _vp, C.c_double]),
+    "gpe_weights": (_int, [_vp, _P(_vp), _P(_i64), _P(C.c_double), _P(C.c_double)]),
+    "gpe_bind_sampler_graded": (_int, [_vp, _P(gpe_sampler_spec), _vp, _vp, _vp]),
     "gpe_bind_boundary": (_int, [_vp, _vp, _i64, _vp]),
     "gpe_bind_orth": (_int, [_vp, _int, _vp]),
     "gpe_bind_orth_state": (_int, [_vp, _int, _vp, C.c_size_t, _int, _f, _f]),

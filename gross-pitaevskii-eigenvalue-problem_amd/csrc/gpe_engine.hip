@@ -641,6 +641,15 @@ struct gpe_engine {
     int64_t smp_n = 0, smp_first = 0, smp_every = 0;  // every == 0: no sampler
     int64_t smp_draw0 = 0, smp_held = 0;              // draw at the bind / draw the buffer holds (as enqueued)
     int64_t smp_steps = 0;                            // steps enqueued since the bind
+    // graded sampler (gpe_bind_sampler_graded): the cell edges of every axis, one after the other, and the engine-owned weights
+    bool smp_graded = false;
+    float* smp_edges = nullptr;                       // [sum_k shape[k] + 1]; axis k starts at smp_edge_off[k]
+    int64_t smp_edge_off[3] = {0, 0, 0};
+    float* smp_q = nullptr;                           // [smp_n] cell volumes; wq points here while the graded sampler is bound
+    // per-point quadrature weights (gpe_bind_weights): every collocation sum takes q_i, every N of a mean becomes W (Phys::n_global)
+    const float* wq = nullptr;                        // [n_pde]: the caller's array, or smp_q; NULL: unweighted
+    double wq_local = 0.0, wq_total = 0.0;            // sum of this rank's weights / W over all ranks
+    double* wq_red = nullptr;                         // [2] output of k_weight_total, allocated at the first bind
     StepState st;
     std::string err;
     double* sums() { return dbl; }
@@ -790,9 +799,10 @@ static bool seed_in_reverse(gpe_engine* e);
 static bool plain_terms(const gpe_engine* e) {
     return e->cfg.w_riesz == 0.f && e->cfg.lambda_kind == GPE_LAMBDA_RAYLEIGH && e->cfg.w_reg_f == 0.f && e->cfg.w_reg_lam == 0.f;
 }
-// problem class whose head the forward kernels can run (head_point_real): real psi, no orthogonality / Riesz / symmetry terms
+// problem class whose head the forward kernels can run (head_point_real): real psi, no orthogonality / Riesz / symmetry terms, no
+// quadrature weights
 static bool head_class(gpe_engine* e) {
-    return e->fuse_head && e->head_slots && e->path == GPE_PATH_FUSED && !e->wide && e->H <= 64 && e->nd.n_out == 1 && !e->cfg.complex_psi &&
+    return e->fuse_head && !e->wq && e->head_slots && e->path == GPE_PATH_FUSED && !e->wide && e->H <= 64 && e->nd.n_out == 1 && !e->cfg.complex_psi &&
            e->ph.n_orth == 0 && plain_terms(e) && e->cfg.w_sym == 0.f && e->main.C >= 3 && e->main.n > 0;
 }
 // ... by the cooperative forward kernel (small batches; the reverse kernel forms the seeds and adds the triples)
@@ -932,9 +942,9 @@ static bool coop_shape(gpe_engine* e) {
 static int bwd_kind(gpe_engine* e, const Batch& b);
 static bool use_pipe(gpe_engine* e, int C);
 // small batches of the common problem class (real psi, no orthogonality / Riesz / symmetry terms) on the pipelined reverse kernel:
-// the kernel forms the seeds itself and k_seed_pde is not launched
+// the kernel forms the seeds itself and k_seed_pde is not launched (bound quadrature weights keep k_seed_pde: the fused seeds have none)
 static bool seed_in_reverse(gpe_engine* e) {
-    return e->fuse_seed && e->path == GPE_PATH_FUSED && !e->wide && e->nd.n_out == 1 && !e->cfg.complex_psi && e->ph.n_orth == 0 &&
+    return e->fuse_seed && !e->wq && e->path == GPE_PATH_FUSED && !e->wide && e->nd.n_out == 1 && !e->cfg.complex_psi && e->ph.n_orth == 0 &&
            plain_terms(e) && e->cfg.w_sym == 0.f && e->main.C >= 3 && e->main.n > 0 && e->n_pde <= e->fuse_seed_max &&
            use_pipe(e, e->main.C) && bwd_kind(e, e->main) == 3;
 }
@@ -1391,6 +1401,10 @@ static int mlp_backward(gpe_engine* e, Batch& b, const BwdOpts& o) {
 }
 
 // ---- config -> device structs ------------------------------------------------------------------------
+// N of the means without quadrature weights: the configured global count, or the bound local one
+static double counted_n_global(const gpe_engine* e) {
+    return (double)(e->cfg.n_global > 0 ? e->cfg.n_global : (e->n_pde > 0 ? e->n_pde : 1));
+}
 static void fill_phys(gpe_engine* e) {
     const gpe_config& c = e->cfg;
     Phys& p = e->ph;
@@ -1405,7 +1419,7 @@ static void fill_phys(gpe_engine* e) {
     p.w_pde = c.w_pde; p.w_bc = c.w_bc; p.w_norm = c.w_norm; p.w_sym = c.w_sym; p.w_orth = c.w_orth;
     p.sym_sign = c.sym_sign; p.dx = c.dx; p.w_riesz = c.w_riesz; p.riesz_kind = c.riesz_kind;
     p.lambda_kind = c.lambda_kind; p.w_reg_f = c.w_reg_f; p.reg_f_eps = c.reg_f_eps; p.w_reg_lam = c.w_reg_lam; p.reg_lam_eps = c.reg_lam_eps;
-    p.n_global = (double)(c.n_global > 0 ? c.n_global : (e->n_pde > 0 ? e->n_pde : 1));
+    p.n_global = e->wq ? e->wq_total : counted_n_global(e);        // bound weights: W = sum q over all ranks
     p.inv_world = 1.0f / (float)(c.world_size > 0 ? c.world_size : 1);
     int no = 0;
     for (int j = 0; j < GPE_MAX_ORTH; ++j) if (e->orth_host[j]) no = j + 1;      // [4..6] are the precomputed base
@@ -1507,6 +1521,10 @@ int gpe_active_kernels(gpe_engine* e, char* buf, size_t n) {
     if (e->umap.empty()) snprintf(buf, n, "fwd=%s;bwd=%s;split=fwd %d/1024, bwd %d/1024", f, r, sf, sb);
     else snprintf(buf, n, "fwd=%s;bwd=%s;split=fwd %d/1024, bwd %d/1024;padded=hidden widths up to %d run as %d", f, r, sf, sb,
                   *std::max_element(e->user_layers + 1, e->user_layers + e->cfg.n_layers - 1), e->cfg.layers[1]);
+    if (e->wq) {      // bound quadrature weights: head and seeds by the standalone kernels' weighted instances, whatever the batch size
+        const size_t used = strlen(buf);
+        snprintf(buf + used, n - used, ";head=k_head_pde<%d,%d,weighted>;seed=k_seed_pde<%d,%d,weighted>", b.C, b.E, b.C, b.E);
+    }
     return GPE_OK;
 }
 
@@ -1868,7 +1886,7 @@ void gpe_destroy(gpe_engine* e) {
     for (int k = 0; k < GPE_MAX_ORTH; ++k) orth_state_free(e->ost[k]);
     for (hipEvent_t ev : e->ev_pool) (void)hipEventDestroy(ev);
     if (e->ext_exchange) { e->grad = nullptr; e->dbl = nullptr; }
-    void* ps[] = {e->theta, e->am, e->av, e->grad, e->dbl, e->od, e->hist, e->last, (void*)e->orth_dev, e->Wpk, e->WpkT, e->gslab, e->gslab_bc, e->grad_bc, (void*)e->upd_snap, (void*)e->head_slots, (void*)e->upd_ticket, (void*)e->upd_snap_small, (void*)e->obs_buf, (void*)e->obs_out, (void*)e->mon_ring, (void*)e->smp_x, (void*)e->theta_best, (void*)e->keep_dev};
+    void* ps[] = {e->theta, e->am, e->av, e->grad, e->dbl, e->od, e->hist, e->last, (void*)e->orth_dev, e->Wpk, e->WpkT, e->gslab, e->gslab_bc, e->grad_bc, (void*)e->upd_snap, (void*)e->head_slots, (void*)e->upd_ticket, (void*)e->upd_snap_small, (void*)e->obs_buf, (void*)e->obs_out, (void*)e->mon_ring, (void*)e->smp_x, (void*)e->theta_best, (void*)e->keep_dev, (void*)e->smp_edges, (void*)e->smp_q, (void*)e->wq_red};
     for (void* p : ps) if (p) (void)hipFree(p);
     delete e;
 }
@@ -1980,12 +1998,14 @@ static int rebuild_main(gpe_engine* e) {
 
 static void sampler_clear(gpe_engine* e);
 static bool precomputed_base(const gpe_engine* e);
+static void weights_clear(gpe_engine* e) { e->wq = nullptr; e->wq_local = 0.0; e->wq_total = 0.0; }      // (callers run fill_phys)
 static int orth_resize(gpe_engine* e);
 static int orth_refill(gpe_engine* e);
 
 // the bind itself, shared by gpe_bind_points (caller's points) and gpe_bind_sampler (the engine's own buffer)
 static int bind_points_impl(gpe_engine* e, const float* d_x, int64_t n_local, const float* d_V) {
     monitor_drop_if_on_bound_points(e);
+    weights_clear(e);                            // weights belong to rows: the new set starts without
     e->ux = d_x; e->uV = d_V; e->n_pde = n_local;
     int rc = rebuild_main(e);
     if (rc) return rc;
@@ -2022,16 +2042,31 @@ int gpe_bind_points(gpe_engine* e, const float* d_x, int64_t n_local, const floa
 }
 
 // ---- device-side stratified sampler ------------------------------------------------------------------------
+static void graded_free(gpe_engine* e) {         // the graded sampler's edges and weights (the stream is idle); bound weights that were its own go too
+    if (e->wq && e->wq == e->smp_q) weights_clear(e);
+    if (e->smp_edges) { (void)hipFree(e->smp_edges); e->smp_edges = nullptr; }
+    if (e->smp_q) { (void)hipFree(e->smp_q); e->smp_q = nullptr; }
+    e->smp_graded = false;
+}
 static void sampler_clear(gpe_engine* e) {       // the stream is idle (callers synchronise first)
     if (e->smp_x) { (void)hipFree(e->smp_x); e->smp_x = nullptr; }
+    graded_free(e);
     e->smp_n = 0; e->smp_every = 0; e->smp_steps = 0; e->smp_draw0 = 0; e->smp_held = 0; e->smp_first = 0;
 }
 
 // draw `draw` into the point buffer (and the [x ; -x] batch) on the engine's stream; nothing synchronises
-static int sampler_launch(gpe_engine* e, int64_t draw) {
-    float* xs = (e->cfg.w_sym != 0.f && e->sym.n == 2 * e->smp_n) ? e->sym.xown : nullptr;
-    hipLaunchKernelGGL(k_sampler_draw, dim3(cdiv(e->smp_n, SMP_THREADS)), dim3(SMP_THREADS), 0, e->stream, e->smp_grid, e->smp_first,
-                       e->smp_n, (uint64_t)draw, e->smp_x, xs);
+// (with_weights: the graded sampler's bind, which writes the cell volumes too -- they do not depend on the draw)
+static int sampler_launch(gpe_engine* e, int64_t draw, bool with_weights = false) {
+    if (e->smp_graded) {
+        const float* ed = e->smp_edges;
+        hipLaunchKernelGGL(k_sampler_draw_graded, dim3(cdiv(e->smp_n, SMP_THREADS)), dim3(SMP_THREADS), 0, e->stream, e->smp_grid,
+                           ed + e->smp_edge_off[0], ed + e->smp_edge_off[1], ed + e->smp_edge_off[2], e->smp_first, e->smp_n, (uint64_t)draw,
+                           e->smp_x, with_weights ? e->smp_q : (float*)nullptr);
+    } else {
+        float* xs = (e->cfg.w_sym != 0.f && e->sym.n == 2 * e->smp_n) ? e->sym.xown : nullptr;
+        hipLaunchKernelGGL(k_sampler_draw, dim3(cdiv(e->smp_n, SMP_THREADS)), dim3(SMP_THREADS), 0, e->stream, e->smp_grid, e->smp_first,
+                           e->smp_n, (uint64_t)draw, e->smp_x, xs);
+    }
     HIPCHK(e, hipGetLastError());
     e->smp_held = draw;
     return orth_refill(e);                       // frozen orthogonality states: psi_k of the new set, before the step's first kernel
@@ -2048,6 +2083,126 @@ static int sampler_before_step(gpe_engine* e, bool capturing) {
     return sampler_launch(e, want);
 }
 
+// one fixed-order fp64 total of a weight array on the engine's stream, read back here: the bind's one synchronisation
+static int weights_total(gpe_engine* e, const float* d_q, int64_t n, double* total, double* bad) {
+    if (!e->wq_red && hipMalloc((void**)&e->wq_red, 2 * sizeof(double) + 256) != hipSuccess) {
+        (void)hipGetLastError();
+        FAIL(e, GPE_ERR_NOMEM, "bind_weights: no memory for the weight total");
+    }
+    hipLaunchKernelGGL(k_weight_total, dim3(1), dim3(WQ_THREADS), 0, e->stream, d_q, n, e->wq_red);
+    HIPCHK(e, hipGetLastError());
+    double h[2] = {0.0, 0.0};
+    HIPCHK(e, hipMemcpyAsync(h, e->wq_red, sizeof h, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    *total = h[0]; *bad = h[1];
+    return GPE_OK;
+}
+
+// edges == NULL: the uniform grid of gpe_bind_sampler; else the graded grid of gpe_bind_sampler_graded (one host array per used axis)
+static int bind_sampler_impl(gpe_engine* e, const gpe_sampler_spec* sp, const float* const* edges) {
+    const char* who = edges ? "bind_sampler_graded" : "bind_sampler";
+    const int dim = e->nd.dim;
+    if (e->cfg.potential == GPE_POT_PRECOMPUTED) FAIL(e, GPE_ERR_INVALID, "%s: a precomputed potential lives on fixed points", who);
+    if (precomputed_base(e)) FAIL(e, GPE_ERR_INVALID, "%s: a precomputed base lives on fixed points", who);
+    for (int k = 0; k < GPE_MAX_ORTH; ++k)       // (a frozen state is re-evaluated behind every redraw: only caller arrays are refused)
+        if (e->orth_host[k] && !e->ost[k].on) FAIL(e, GPE_ERR_INVALID, "%s: orthogonality array %d is bound, and lives on fixed points", who, k);
+    if (sp->every <= 0) FAIL(e, GPE_ERR_INVALID, "%s: every = %lld, need > 0", who, (long long)sp->every);
+    if (edges && e->cfg.w_sym != 0.f) FAIL(e, GPE_ERR_INVALID, "%s: the symmetry batch has no quadrature weights (w_sym != 0)", who);
+    double cells = 1.0;
+    for (int k = 0; k < 3; ++k) {
+        if ((sp->shape[k] > 0) != (k < dim))
+            FAIL(e, GPE_ERR_INVALID, "%s: shape must use exactly the network's %d input axes (shape[%d] = %lld)", who, dim, k, (long long)sp->shape[k]);
+        if (k >= dim) continue;
+        if (sp->shape[k] > (1 << 24)) FAIL(e, GPE_ERR_INVALID, "%s: shape[%d] = %lld, at most 2^24 cells per axis", who, k, (long long)sp->shape[k]);
+        if (!(sp->hi[k] > sp->lo[k])) FAIL(e, GPE_ERR_INVALID, "%s: hi <= lo on axis %d", who, k);
+        if (!(sp->clip_hi[k] >= sp->clip_lo[k])) FAIL(e, GPE_ERR_INVALID, "%s: clip_hi < clip_lo on axis %d", who, k);
+        cells *= (double)sp->shape[k];
+    }
+    if (sp->first_cell < 0 || sp->n_local <= 0 || (double)sp->first_cell + (double)sp->n_local > cells)
+        FAIL(e, GPE_ERR_INVALID, "%s: cells [%lld, %lld + %lld) outside the grid's %.0f", who, (long long)sp->first_cell, (long long)sp->first_cell, (long long)sp->n_local, cells);
+    // graded grid: strictly increasing finite edges that start at lo and end at hi; W = product over the axes of the fp64 sums, in index
+    // order, of the fp32 widths -- of the WHOLE grid, whichever block of cells this rank holds
+    double w_grid = 1.0;
+    int64_t n_edges = 0;
+    if (edges) {
+        for (int k = 0; k < dim; ++k) {
+            const float* ed = edges[k];
+            if (!ed) FAIL(e, GPE_ERR_INVALID, "%s: no edges for axis %d", who, k);
+            double wk = 0.0;
+            for (int64_t i = 0; i <= sp->shape[k]; ++i) {
+                if (!__builtin_isfinite(ed[i])) FAIL(e, GPE_ERR_INVALID, "%s: edge %lld of axis %d is not finite", who, (long long)i, k);
+                if (i > 0 && !(ed[i] > ed[i - 1])) FAIL(e, GPE_ERR_INVALID, "%s: edges of axis %d do not increase at %lld", who, k, (long long)i);
+                if (i > 0) { const float w = ed[i] - ed[i - 1]; wk += (double)w; }
+            }
+            if (ed[0] != sp->lo[k] || ed[sp->shape[k]] != sp->hi[k])
+                FAIL(e, GPE_ERR_INVALID, "%s: lo / hi of axis %d are not its first / last edge", who, k);
+            w_grid *= wk;
+            n_edges += sp->shape[k] + 1;
+        }
+    }
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    if (e->side) HIPCHK(e, hipStreamSynchronize(e->side));
+    if (e->smp_n != sp->n_local || !e->smp_x) {      // same size: the buffer (and a captured graph's pointers) stay
+        float* p = nullptr;
+        if (hipMalloc((void**)&p, (size_t)sp->n_local * dim * sizeof(float) + 256) != hipSuccess) {
+            (void)hipGetLastError();
+            FAIL(e, GPE_ERR_NOMEM, "%s: no memory for %lld points", who, (long long)sp->n_local);
+        }
+        sampler_clear(e);
+        e->smp_x = p;
+    }
+    graded_free(e);                              // edges and weights of an earlier graded bind
+    SamplerGrid& g = e->smp_grid;
+    memset(&g, 0, sizeof g);
+    g.dim = dim; g.key0 = (uint32_t)sp->seed; g.key1 = (uint32_t)(sp->seed >> 32);
+    for (int k = 0; k < dim; ++k) {
+        g.shape[k] = sp->shape[k]; g.lo[k] = sp->lo[k]; g.clip_lo[k] = sp->clip_lo[k]; g.clip_hi[k] = sp->clip_hi[k];
+        g.h[k] = (float)(((double)sp->hi[k] - (double)sp->lo[k]) / (double)sp->shape[k]);
+    }
+    int rc = GPE_OK;
+    if (edges) {
+        if (hipMalloc((void**)&e->smp_edges, (size_t)n_edges * sizeof(float) + 256) != hipSuccess ||
+            hipMalloc((void**)&e->smp_q, (size_t)sp->n_local * sizeof(float) + 256) != hipSuccess) {
+            (void)hipGetLastError();
+            e->err = std::string(who) + ": no memory for the edges and weights"; rc = GPE_ERR_NOMEM;
+        }
+        int64_t off = 0;
+        for (int k = 0; k < 3 && !rc; ++k) {
+            e->smp_edge_off[k] = k < dim ? off : 0;      // (unused axes point at axis 0: never read)
+            if (k >= dim) continue;
+            if (hipMemcpy(e->smp_edges + off, edges[k], (size_t)(sp->shape[k] + 1) * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+                (void)hipGetLastError();
+                e->err = std::string(who) + ": upload of the edges failed"; rc = GPE_ERR_HIP;
+            }
+            off += sp->shape[k] + 1;
+        }
+        e->smp_graded = !rc;
+    }
+    e->smp_n = sp->n_local; e->smp_first = sp->first_cell; e->smp_every = sp->every; e->smp_draw0 = sp->draw0; e->smp_steps = 0;
+    e->smp_held = sp->draw0;
+    if (e->mse_target) { e->mse_target = nullptr; free_batch(e->mse); }      // a pre-training target lived on the points that just went
+    if (!rc) rc = bind_points_impl(e, e->smp_x, e->smp_n, nullptr);      // allocates the symmetry batch; its copy kernel reads a buffer ...
+    if (!rc) rc = sampler_launch(e, sp->draw0, /*with_weights=*/edges != nullptr);       // ... this launch fills, together with [x ; -x]
+    if (!rc && edges) {                          // the cell volumes become the bound weights, W the whole grid's volume
+        double wl = 0.0, bad = 0.0;
+        rc = weights_total(e, e->smp_q, e->smp_n, &wl, &bad);
+        if (!rc && (bad != 0.0 || !(wl > 0.0) || !__builtin_isfinite(wl) || !(w_grid > 0.0) || !__builtin_isfinite(w_grid))) {
+            e->err = std::string(who) + ": the cell volumes of this block underflow or overflow fp32"; rc = GPE_ERR_INVALID;
+        }
+        if (!rc) { e->wq = e->smp_q; e->wq_local = wl; e->wq_total = w_grid; fill_phys(e); }
+    }
+    if (!rc && hipStreamSynchronize(e->stream) != hipSuccess) { e->err = std::string(who) + ": synchronise failed"; rc = GPE_ERR_HIP; }
+    if (rc) {                                    // never leave a half-bound sampler behind
+        const std::string keep = e->err;
+        (void)hipStreamSynchronize(e->stream);
+        sampler_clear(e);
+        e->ux = nullptr; e->n_pde = 0; free_batch(e->main); free_batch(e->sym);
+        fill_phys(e);
+        e->err = keep;
+    }
+    return rc;
+}
+
 int gpe_bind_sampler(gpe_engine* e, const gpe_sampler_spec* sp) {
     if (!e) return GPE_ERR_INVALID;
     if (!sp) {                                   // clear: the buffer goes, so nothing stays bound
@@ -2056,61 +2211,57 @@ int gpe_bind_sampler(gpe_engine* e, const gpe_sampler_spec* sp) {
         if (e->smp_every <= 0) return GPE_OK;
         monitor_drop_if_on_bound_points(e);
         graph_drop(e);
-        sampler_clear(e);
+        sampler_clear(e);                        // (a graded sampler's weights go with it)
         e->ux = nullptr; e->uV = nullptr; e->n_pde = 0;
         free_batch(e->main); free_batch(e->sym);
         if (e->uxb && e->nb_user > 0) { int rc = setup_batch(e, e->bc, e->uxb, e->nb_user, 1, 0, false, nullptr); if (rc) return rc; }
         e->nb_merged = 0;
         e->acc_clean = false;
+        fill_phys(e);
         return GPE_OK;
     }
-    const int dim = e->nd.dim;
-    if (e->cfg.potential == GPE_POT_PRECOMPUTED) FAIL(e, GPE_ERR_INVALID, "bind_sampler: a precomputed potential lives on fixed points");
-    if (precomputed_base(e)) FAIL(e, GPE_ERR_INVALID, "bind_sampler: a precomputed base lives on fixed points");
-    for (int k = 0; k < GPE_MAX_ORTH; ++k)       // (a frozen state is re-evaluated behind every redraw: only caller arrays are refused)
-        if (e->orth_host[k] && !e->ost[k].on) FAIL(e, GPE_ERR_INVALID, "bind_sampler: orthogonality array %d is bound, and lives on fixed points", k);
-    if (sp->every <= 0) FAIL(e, GPE_ERR_INVALID, "bind_sampler: every = %lld, need > 0", (long long)sp->every);
-    double cells = 1.0;
-    for (int k = 0; k < 3; ++k) {
-        if ((sp->shape[k] > 0) != (k < dim))
-            FAIL(e, GPE_ERR_INVALID, "bind_sampler: shape must use exactly the network's %d input axes (shape[%d] = %lld)", dim, k, (long long)sp->shape[k]);
-        if (k >= dim) continue;
-        if (sp->shape[k] > (1 << 24)) FAIL(e, GPE_ERR_INVALID, "bind_sampler: shape[%d] = %lld, at most 2^24 cells per axis", k, (long long)sp->shape[k]);
-        if (!(sp->hi[k] > sp->lo[k])) FAIL(e, GPE_ERR_INVALID, "bind_sampler: hi <= lo on axis %d", k);
-        if (!(sp->clip_hi[k] >= sp->clip_lo[k])) FAIL(e, GPE_ERR_INVALID, "bind_sampler: clip_hi < clip_lo on axis %d", k);
-        cells *= (double)sp->shape[k];
+    return bind_sampler_impl(e, sp, nullptr);
+}
+
+int gpe_bind_sampler_graded(gpe_engine* e, const gpe_sampler_spec* sp, const float* h_edges0, const float* h_edges1, const float* h_edges2) {
+    if (!e) return GPE_ERR_INVALID;
+    if (!sp) FAIL(e, GPE_ERR_INVALID, "bind_sampler_graded: no spec (gpe_bind_sampler(NULL) clears a sampler of either kind)");
+    const float* edges[3] = {h_edges0, h_edges1, h_edges2};
+    return bind_sampler_impl(e, sp, edges);
+}
+
+int gpe_bind_weights(gpe_engine* e, const float* d_q, double w_total) {
+    if (!e) return GPE_ERR_INVALID;
+    if (!d_q) {                                  // clear: the count-based N is back
+        if (e->smp_graded) FAIL(e, GPE_ERR_STATE, "bind_weights: the graded sampler owns the bound weights (gpe_bind_sampler(NULL) clears both)");
+        HIPCHK(e, hipStreamSynchronize(e->stream));
+        weights_clear(e);
+        fill_phys(e);
+        return GPE_OK;
     }
-    if (sp->first_cell < 0 || sp->n_local <= 0 || (double)sp->first_cell + (double)sp->n_local > cells)
-        FAIL(e, GPE_ERR_INVALID, "bind_sampler: cells [%lld, %lld + %lld) outside the grid's %.0f", (long long)sp->first_cell, (long long)sp->first_cell, (long long)sp->n_local, cells);
+    if (!e->ux || e->n_pde <= 0) FAIL(e, GPE_ERR_STATE, "bind_weights before bind_points");
+    if (e->smp_every > 0) FAIL(e, GPE_ERR_STATE, "bind_weights: a sampler is bound, its rows move at the next redraw");
+    if (e->cfg.w_sym != 0.f) FAIL(e, GPE_ERR_INVALID, "bind_weights: the symmetry batch has no quadrature weights (w_sym != 0)");
+    if (!(w_total >= 0.0) || !__builtin_isfinite(w_total)) FAIL(e, GPE_ERR_INVALID, "bind_weights: w_total = %g, need a finite value >= 0 (0: this rank's total)", w_total);
+    double wl = 0.0, bad = 0.0;
+    int rc = weights_total(e, d_q, e->n_pde, &wl, &bad);
+    if (rc) return rc;
+    if (bad != 0.0) FAIL(e, GPE_ERR_INVALID, "bind_weights: %.0f of the %lld weights are negative or not finite", bad, (long long)e->n_pde);
+    if (!(wl > 0.0) || !__builtin_isfinite(wl)) FAIL(e, GPE_ERR_INVALID, "bind_weights: the weights add up to %g, need a finite total > 0", wl);
+    e->wq = d_q; e->wq_local = wl; e->wq_total = w_total > 0.0 ? w_total : wl;
+    fill_phys(e);
+    return GPE_OK;
+}
+
+int gpe_weights(gpe_engine* e, const float** d_q, int64_t* n, double* w_local, double* w_total) {
+    if (!e) return GPE_ERR_INVALID;
+    if (!e->wq) FAIL(e, GPE_ERR_STATE, "weights: no weights bound");
     HIPCHK(e, hipStreamSynchronize(e->stream));
-    if (e->side) HIPCHK(e, hipStreamSynchronize(e->side));
-    if (e->smp_n != sp->n_local || !e->smp_x) {      // same size: the buffer (and a captured graph's pointers) stay
-        float* p = nullptr;
-        if (hipMalloc((void**)&p, (size_t)sp->n_local * dim * sizeof(float) + 256) != hipSuccess) {
-            (void)hipGetLastError();
-            FAIL(e, GPE_ERR_NOMEM, "bind_sampler: no memory for %lld points", (long long)sp->n_local);
-        }
-        sampler_clear(e);
-        e->smp_x = p;
-    }
-    SamplerGrid& g = e->smp_grid;
-    memset(&g, 0, sizeof g);
-    g.dim = dim; g.key0 = (uint32_t)sp->seed; g.key1 = (uint32_t)(sp->seed >> 32);
-    for (int k = 0; k < dim; ++k) {
-        g.shape[k] = sp->shape[k]; g.lo[k] = sp->lo[k]; g.clip_lo[k] = sp->clip_lo[k]; g.clip_hi[k] = sp->clip_hi[k];
-        g.h[k] = (float)(((double)sp->hi[k] - (double)sp->lo[k]) / (double)sp->shape[k]);
-    }
-    e->smp_n = sp->n_local; e->smp_first = sp->first_cell; e->smp_every = sp->every; e->smp_draw0 = sp->draw0; e->smp_steps = 0;
-    e->smp_held = sp->draw0;
-    if (e->mse_target) { e->mse_target = nullptr; free_batch(e->mse); }      // a pre-training target lived on the points that just went
-    int rc = bind_points_impl(e, e->smp_x, e->smp_n, nullptr);      // allocates the symmetry batch; its copy kernel reads a buffer ...
-    if (!rc) rc = sampler_launch(e, sp->draw0);                   // ... this launch fills, together with [x ; -x]
-    if (!rc && hipStreamSynchronize(e->stream) != hipSuccess) { e->err = "bind_sampler: synchronise failed"; rc = GPE_ERR_HIP; }
-    if (rc) {                                    // never leave a half-bound sampler behind
-        sampler_clear(e);
-        e->ux = nullptr; e->n_pde = 0; free_batch(e->main); free_batch(e->sym);
-    }
-    return rc;
+    if (d_q) *d_q = e->wq;
+    if (n) *n = e->n_pde;
+    if (w_local) *w_local = e->wq_local;
+    if (w_total) *w_total = e->wq_total;
+    return GPE_OK;
 }
 
 int gpe_sampler_points(gpe_engine* e, const float** d_x, int64_t* n, int64_t* draw) {
@@ -2340,21 +2491,26 @@ static int obs_check_points(gpe_engine* e, const char* who, const float* d_x, in
     return GPE_OK;
 }
 // the two reduction passes over the full jets b.O of the points x, and the struct into *dst (device memory); nothing synchronises
-static int launch_observe(gpe_engine* e, Batch& b, const float* x, int64_t n, const float* V, float dv, struct gpe_observables* dst) {
+// q: per-point quadrature weights [n] (the bound set under gpe_bind_weights), or NULL
+static int launch_observe(gpe_engine* e, Batch& b, const float* x, int64_t n, const float* V, float dv, struct gpe_observables* dst,
+                          const float* q = nullptr) {
     const unsigned g = (unsigned)std::min<int64_t>(cdiv(n, OBS_THREADS), OBS_MAX_WG);        // a function of n alone: fixed point -> thread map
     double* slab1 = e->obs_buf;
     double* slab2 = slab1 + (size_t)OBS_MAX_WG * OB_ROW;
     double* raw = slab2 + (size_t)OBS_MAX_WG * OB_ROW;
     const float* const* bp = (const float* const*)e->orth_dev;
-#define OBS_CHAIN(DD)                                                                                                                     \
-    hipLaunchKernelGGL((k_obs_pass1<DD>), dim3(g), dim3(OBS_THREADS), 0, e->stream, e->ph, e->base_norm, x, V, (const float*)b.O, bp, n, b.ld, slab1); \
+#define OBS_CHAIN(DD, WW)                                                                                                                 \
+    hipLaunchKernelGGL((k_obs_pass1<DD, WW>), dim3(g), dim3(OBS_THREADS), 0, e->stream, e->ph, e->base_norm, x, V, (const float*)b.O, bp, n, b.ld, slab1, q); \
     hipLaunchKernelGGL(k_obs_reduce, dim3(1), dim3(OBS_THREADS), 0, e->stream, (const double*)slab1, (int)g, raw);                       \
-    hipLaunchKernelGGL((k_obs_pass2<DD>), dim3(g), dim3(OBS_THREADS), 0, e->stream, e->ph, e->base_norm, x, V, (const float*)b.O, bp, n, b.ld, \
-                       (const double*)raw, (double)dv, slab2);
-    switch (e->nd.dim) {
-        case 1: OBS_CHAIN(1) break;
-        case 2: OBS_CHAIN(2) break;
-        default: OBS_CHAIN(3) break;
+    hipLaunchKernelGGL((k_obs_pass2<DD, WW>), dim3(g), dim3(OBS_THREADS), 0, e->stream, e->ph, e->base_norm, x, V, (const float*)b.O, bp, n, b.ld, \
+                       (const double*)raw, (double)dv, slab2, q);
+    switch (e->nd.dim * 2 + (q ? 1 : 0)) {
+        case 2: OBS_CHAIN(1, false) break;
+        case 3: OBS_CHAIN(1, true) break;
+        case 4: OBS_CHAIN(2, false) break;
+        case 5: OBS_CHAIN(2, true) break;
+        case 6: OBS_CHAIN(3, false) break;
+        default: OBS_CHAIN(3, true) break;
     }
 #undef OBS_CHAIN
     hipLaunchKernelGGL(k_obs_finish, dim3(1), dim3(OBS_THREADS), 0, e->stream, e->ph, (const double*)slab2, (int)g, (const double*)raw, (double)dv,
@@ -2365,15 +2521,17 @@ static int launch_observe(gpe_engine* e, Batch& b, const float* x, int64_t n, co
 
 int gpe_observables(gpe_engine* e, const float* d_x, int64_t n, const float* d_V, float dv, struct gpe_observables* out) {
     if (!e || !out) return GPE_ERR_INVALID;
+    const float* q = nullptr;
     if (!d_x) {
         if (!e->ux) FAIL(e, GPE_ERR_STATE, "observables of the bound points before bind_points");
         d_x = e->ux; n = e->n_pde; d_V = e->uV;
+        q = e->wq;                               // the bound set carries its bound weights; an explicit set and the monitor have none
     }
     int rc;
     if ((rc = obs_check_points(e, "observables", d_x, n, d_V))) return rc;
     if ((rc = obs_ensure(e))) return rc;
     if ((rc = aux_forward(e, d_x, n, 1 + 2 * e->nd.dim, e->nd.dim))) return rc;       // full diagonal second derivatives, as gpe_forward_jets
-    if ((rc = launch_observe(e, e->aux, d_x, n, d_V, dv, e->obs_out))) return rc;
+    if ((rc = launch_observe(e, e->aux, d_x, n, d_V, dv, e->obs_out, q))) return rc;
     HIPCHK(e, hipMemcpyAsync(out, e->obs_out, sizeof *out, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));
     return GPE_OK;
@@ -2564,9 +2722,16 @@ static unsigned head_grid(gpe_engine* e, int64_t n, int threads = 0) {
 static int launch_head_pde(gpe_engine* e) {
     Batch& b = e->main;
     dim3 g(head_grid(e, b.n));
-    DISPATCH_TRAIN(b, hipLaunchKernelGGL((k_head_pde<CC, EE>), g, dim3(e->head_threads), 0, e->stream, e->ph, e->base_norm, b.pts, b.V, b.O,
-                                        (const float* const*)e->orth_dev, b.u, b.Hu, b.ux, e->sums(), b.n, b.ld, e->n_pde,
-                                        e->bc_target, b.Ob, e->lsums()));
+    const float* none = nullptr;
+    if (e->wq) {      // bound quadrature weights: the weighted instance
+        DISPATCH_TRAIN(b, hipLaunchKernelGGL((k_head_pde<CC, EE, true>), g, dim3(e->head_threads), 0, e->stream, e->ph, e->base_norm, b.pts, b.V, b.O,
+                                            (const float* const*)e->orth_dev, b.u, b.Hu, b.ux, e->sums(), b.n, b.ld, e->n_pde,
+                                            e->bc_target, b.Ob, e->lsums(), e->wq));
+    } else {
+        DISPATCH_TRAIN(b, hipLaunchKernelGGL((k_head_pde<CC, EE>), g, dim3(e->head_threads), 0, e->stream, e->ph, e->base_norm, b.pts, b.V, b.O,
+                                            (const float* const*)e->orth_dev, b.u, b.Hu, b.ux, e->sums(), b.n, b.ld, e->n_pde,
+                                            e->bc_target, b.Ob, e->lsums(), none));
+    }
     HIPCHK(e, hipGetLastError());
     return GPE_OK;
 }
@@ -2574,10 +2739,18 @@ static int launch_head_pde(gpe_engine* e) {
 static int launch_seed_pde(gpe_engine* e, float* d_resid, int want_seeds, int head_slots) {
     Batch& b = e->main;
     dim3 g(head_grid(e, e->n_pde));
-    DISPATCH_TRAIN(b, hipLaunchKernelGGL((k_seed_pde<CC, EE>), g, dim3(e->head_threads), 0, e->stream, e->ph, b.pts, b.V,
-                                        (const float* const*)e->orth_dev, b.u, b.Hu, b.ux, e->sums(), b.Ob, d_resid, e->dsc(),
-                                        e->n_pde, b.ld, want_seeds, head_slots ? (const double*)e->head_slots : (const double*)nullptr,
-                                        head_slots, e->sums(), e->lsums()));      // collocation rows only; boundary rows were seeded by the head kernel
+    const float* none = nullptr;
+    if (e->wq) {      // bound quadrature weights: the weighted instance (the head never rode in the forward kernel: head_class)
+        DISPATCH_TRAIN(b, hipLaunchKernelGGL((k_seed_pde<CC, EE, true>), g, dim3(e->head_threads), 0, e->stream, e->ph, b.pts, b.V,
+                                            (const float* const*)e->orth_dev, b.u, b.Hu, b.ux, e->sums(), b.Ob, d_resid, e->dsc(),
+                                            e->n_pde, b.ld, want_seeds, head_slots ? (const double*)e->head_slots : (const double*)nullptr,
+                                            head_slots, e->sums(), e->lsums(), e->wq));
+    } else {
+        DISPATCH_TRAIN(b, hipLaunchKernelGGL((k_seed_pde<CC, EE>), g, dim3(e->head_threads), 0, e->stream, e->ph, b.pts, b.V,
+                                            (const float* const*)e->orth_dev, b.u, b.Hu, b.ux, e->sums(), b.Ob, d_resid, e->dsc(),
+                                            e->n_pde, b.ld, want_seeds, head_slots ? (const double*)e->head_slots : (const double*)nullptr,
+                                            head_slots, e->sums(), e->lsums(), none));      // collocation rows only; boundary rows were seeded by the head kernel
+    }
     HIPCHK(e, hipGetLastError());
     return GPE_OK;
 }
@@ -2676,16 +2849,19 @@ static void after_update(gpe_engine* e) {          // host-side mirror of what k
     e->acc_clean = true;
     e->packed_dirty = e->path == GPE_PATH_FUSED && e->upd_snap != nullptr;      // multi-workgroup update: the next k_begin repacks
 }
+// the pre-training loss is and stays unweighted: its mean is over the point count whatever gpe_bind_weights published as W
+static Phys phys_counted(const gpe_engine* e) { Phys ph = e->ph; ph.n_global = counted_n_global(e); return ph; }
 static void launch_update(gpe_engine* e, const float* grad, const double* sums, const double* lsums, double bc_cnt, int do_update,
                           int mse_mode, double* dbl_keep) {
     const int n_pack = e->path == GPE_PATH_FUSED ? (e->nd.n_lin - 2) * e->H * e->H : 0;
+    const Phys ph = mse_mode ? phys_counted(e) : e->ph;
     if (e->upd_snap) {
         hipLaunchKernelGGL(k_update_part, dim3(UPD_G), dim3(1024), 0, e->stream, e->P, grad, sums, lsums, e->od, e->upd_snap);
-        hipLaunchKernelGGL(k_update<true>, dim3(UPD_G), dim3(1024), 0, e->stream, e->P, e->theta, e->am, e->av, grad, sums, lsums, e->ph,
+        hipLaunchKernelGGL(k_update<true>, dim3(UPD_G), dim3(1024), 0, e->stream, e->P, e->theta, e->am, e->av, grad, sums, lsums, ph,
                            e->oc, e->od, e->hist, e->cap, e->last, bc_cnt, do_update, mse_mode, e->nd, e->H, e->Wpk, e->WpkT, n_pack, e->dbl,
                            (int)(S_COUNT + LS_COUNT + 4), dbl_keep, (const UpdSnap*)e->upd_snap, 1);
     } else {
-        hipLaunchKernelGGL(k_update<false>, dim3(1), dim3(1024), 0, e->stream, e->P, e->theta, e->am, e->av, grad, sums, lsums, e->ph,
+        hipLaunchKernelGGL(k_update<false>, dim3(1), dim3(1024), 0, e->stream, e->P, e->theta, e->am, e->av, grad, sums, lsums, ph,
                            e->oc, e->od, e->hist, e->cap, e->last, bc_cnt, do_update, mse_mode, e->nd, e->H, e->Wpk, e->WpkT, n_pack, e->dbl,
                            (int)(S_COUNT + LS_COUNT + 4), dbl_keep, (const UpdSnap*)nullptr, ((e->fwd_b6 || e->bwd_b6 || e->H > 64) ? 1 : 2) | (e->update_cache ? 0 : 5));
     }
@@ -2736,7 +2912,7 @@ int gpe_mse_begin(gpe_engine* e) {
     e->mse.pts = Pts{e->ux, nullptr, e->n_pde};
     if ((rc = launch_begin(e))) return rc;
     if ((rc = mlp_forward(e, e->mse, true))) return rc;
-    hipLaunchKernelGGL(k_seed_mse, dim3(head_grid(e, e->mse.n, 256)), dim3(256), 0, e->stream, e->ph, e->mse.pts.a, e->mse_target,
+    hipLaunchKernelGGL(k_seed_mse, dim3(head_grid(e, e->mse.n, 256)), dim3(256), 0, e->stream, phys_counted(e), e->mse.pts.a, e->mse_target,
                        e->mse.O, e->mse.Ob, e->dsc() + 2, e->mse.n, e->mse.ld);
     HIPCHK(e, hipGetLastError());
     if ((rc = mlp_backward(e, e->mse, BwdOpts{/*close=*/true}))) return rc;
@@ -3044,7 +3220,7 @@ static std::vector<char> graph_key_of(gpe_engine* e) {
         put(&b->pts.na, sizeof b->pts.na);
         put(ptrs, sizeof ptrs); put(&b->n, sizeof b->n); put(&b->C, sizeof b->C);
     }
-    const void* more[] = {e->bc_target, e->grad, e->dbl, e->stream};
+    const void* more[] = {e->bc_target, e->grad, e->dbl, e->stream, e->wq};
     put(more, sizeof more); put(e->orth_host, sizeof e->orth_host);
     put(&e->cfg.w_bc, sizeof e->cfg.w_bc); put(&e->cfg.w_sym, sizeof e->cfg.w_sym);
     return k;
@@ -3167,12 +3343,17 @@ int gpe_set_loss_weights(gpe_engine* e, const float w[6]) {
     if (!e || !w) return GPE_ERR_INVALID;
     if (w[5] != 0.f && e->nd.n_out != 1 && !(e->cfg.complex_psi && e->nd.n_out == 2 && e->cfg.p == 3))
         FAIL(e, GPE_ERR_INVALID, "the Riesz energy term needs real psi (out=1) or complex psi (out=2) with p = 3");
+    if (e->wq && w[3] != 0.f) FAIL(e, GPE_ERR_INVALID, "the symmetry batch has no quadrature weights: w_sym stays 0 while weights are bound");
     if ((w[3] != 0.f) != (e->cfg.w_sym != 0.f)) FAIL(e, GPE_ERR_INVALID, "the symmetry term cannot be switched on/off after bind_points");
     e->cfg.w_pde = w[0]; e->cfg.w_bc = w[1]; e->cfg.w_norm = w[2]; e->cfg.w_sym = w[3]; e->cfg.w_orth = w[4]; e->cfg.w_riesz = w[5];
     fill_phys(e);
     return GPE_OK;
 }
-int gpe_set_n_global(gpe_engine* e, int64_t n) { if (!e) return GPE_ERR_INVALID; e->cfg.n_global = n; fill_phys(e); return GPE_OK; }
+int gpe_set_n_global(gpe_engine* e, int64_t n) {
+    if (!e) return GPE_ERR_INVALID;
+    if (e->wq) FAIL(e, GPE_ERR_STATE, "set_n_global: quadrature weights are bound, N of the means is their total W (gpe_bind_weights)");
+    e->cfg.n_global = n; fill_phys(e); return GPE_OK;
+}
 int gpe_set_lr(gpe_engine* e, float lr) {
     if (!e) return GPE_ERR_INVALID;
     OptDev h;

@@ -89,8 +89,19 @@ GPE_DEV void head_point_real(const HeadArgs& ha, const float* xv, int64_t m, int
     den += (double)(u * u);
 }
 
+// one summand of a collocation sum: the fp32 term widened, times the row's quadrature weight where weights are bound
+template <bool WQ>
+GPE_DEV double wq_term(double q, float term) {
+    if constexpr (WQ) return q * (double)term;
+    else return (double)term;
+}
+
 // ---- phase 1: u, Hu per point; block partial sums into sums[] (double atomics) ---------------------
-template <int C, int E>
+// WQ (gpe_bind_weights): collocation row m carries the quadrature weight qw[m] >= 0 on every summand it adds to a collocation sum --
+// num, den, the orthogonality overlaps and the energy sums become sum_i q_i (...).  u, Hu and grad u go to memory as they are; the
+// boundary rows riding in the batch have no weight.  The factor is applied in fp64, so an integer weight adds exactly what that many
+// copies of the row would.  WQ = false is the kernel as it was: qw is not read.
+template <int C, int E, bool WQ = false>
 // Rows [n_pde, N) of a merged batch are boundary points (refine/harmonic_pinn_simulation.py:198-210): for those the kernel
 // forms e = base + s*NN - target, adds e^2 to lsums[LS_BC_SE2] and writes their seeds Ob = w_bc*2/cnt * e * s / world directly
 // (they do not depend on mu) -- what k_head_seed_bc does for a separate boundary batch.
@@ -100,7 +111,7 @@ __global__ __launch_bounds__(1024) void k_head_pde(Phys ph, float base_norm, Pts
                                                   float* __restrict__ Hu_out, float* __restrict__ ux_out,
                                                   double* __restrict__ sums, int64_t N, int64_t ld, int64_t n_pde,
                                                   const float* __restrict__ bc_target, float* __restrict__ Ob,
-                                                  double* __restrict__ lsums) {
+                                                  double* __restrict__ lsums, const float* __restrict__ qw = nullptr) {
     constexpr int D = C - 1 - E;
     double num = 0.0, den = 0.0, so[GPE_MAX_ORTH] = {0.0, 0.0, 0.0, 0.0};
     double rzk = 0.0, rzp = 0.0, rzi = 0.0, rzl = 0.0, bse = 0.0;
@@ -129,6 +140,8 @@ __global__ __launch_bounds__(1024) void k_head_pde(Phys ph, float base_norm, Pts
             continue;
         }
         float V = potential_at(ph, xv, Vpre, m);
+        double qd = 1.0;
+        if constexpr (WQ) qd = (double)qw[m];
         float U[2][C];
         for (int o = 0; o < ph.n_out; ++o) load_u_jets<C, E>(ph, O, ld, m, o, xv, base_norm, orth, U[o]);
         float Hu[2] = {0.f, 0.f};
@@ -157,10 +170,10 @@ __global__ __launch_bounds__(1024) void k_head_pde(Phys ph, float base_norm, Pts
             float u = U[o][0];
             u_out[(int64_t)o * ld + m] = u;
             Hu_out[(int64_t)o * ld + m] = Hu[o];
-            num += (double)(u * Hu[o]);
-            den += (double)(u * u);
+            num += wq_term<WQ>(qd, u * Hu[o]);
+            den += wq_term<WQ>(qd, u * u);
         }
-        for (int j = 0; j < ph.n_orth; ++j) so[j] += (double)(orth[j][m] * U[0][0]);
+        for (int j = 0; j < ph.n_orth; ++j) so[j] += wq_term<WQ>(qd, orth[j][m] * U[0][0]);
         if constexpr (D >= 1) {
             if (phys_needs_energy_sums(ph)) {   // Paper nb c6:L163-174 ; src/gross_pitaevskii_2D.py:112-151 ; the energy-functional lambda (:192)
                 float ak, ap, ai; bool nrm;
@@ -171,16 +184,16 @@ __global__ __launch_bounds__(1024) void k_head_pde(Phys ph, float base_norm, Pts
 #pragma unroll
                     for (int k = 0; k < D; ++k) { const float uk = U[o][1 + k]; ux_out[(int64_t)(o * D + k) * ld + m] = uk; g2 = fmaf(uk, uk, g2); }
                 }
-                rzk += (double)(ak * g2);
-                rzp += (double)(ap * V * rho);
-                if (!ph.complex_psi) rzi += (double)(ai * ipowf(fabsf(U[0][0]), ph.p + 1));
+                rzk += wq_term<WQ>(qd, ak * g2);
+                rzp += wq_term<WQ>(qd, ap * V * rho);
+                if (!ph.complex_psi) rzi += wq_term<WQ>(qd, ai * ipowf(fabsf(U[0][0]), ph.p + 1));
                 else {                                     // |psi|^4 (p = 3) and the rotating-frame term: <L_z> = psi_r D psi_i - psi_i D psi_r, D = x d_y - y d_x
-                    rzi += (double)(ai * rho * rho);
+                    rzi += wq_term<WQ>(qd, ai * rho * rho);
                     if constexpr (D >= 2) {
                         if (ph.omega_rot != 0.f) {
                             const float Dr = xv[0] * U[0][2] - xv[1] * U[0][1];
                             const float Di = xv[0] * U[1][2] - xv[1] * U[1][1];
-                            rzl += (double)(U[0][0] * Di - U[1][0] * Dr);
+                            rzl += wq_term<WQ>(qd, U[0][0] * Di - U[1][0] * Dr);
                         }
                     }
                 }
@@ -249,7 +262,10 @@ __global__ __launch_bounds__(64) void k_slots_to_sums(const double* __restrict__
 
 // ---- phase 2: residual + seeds -------------------------------------------------------------------
 // lambda = num/den (global sums), r = Hu - lambda u, sum r^2 -> gtail[GT_SUM_R2]; Ob = dLoss/dO.
-template <int C, int E>
+// WQ (gpe_bind_weights): the loss is sum_i q_i l_i / W plus functions of the weighted sums, and ph.n_global carries W = sum q over all
+// ranks, so the seed of row m is the unweighted expression (its N is W already) times qw[m], and sum r^2 becomes sum q r^2.  The
+// residual written to resid_out stays the plain r.  WQ = false is the kernel as it was: qw is not read.
+template <int C, int E, bool WQ = false>
 __global__ __launch_bounds__(1024) void k_seed_pde(Phys ph, Pts x, const float* __restrict__ Vpre,
                                                   const float* const* __restrict__ orth,
                                                   const float* __restrict__ u_in, const float* __restrict__ Hu_in,
@@ -257,7 +273,8 @@ __global__ __launch_bounds__(1024) void k_seed_pde(Phys ph, Pts x, const float* 
                                                   const double* __restrict__ sums, float* __restrict__ Ob,
                                                   float* __restrict__ resid_out, double* __restrict__ sum_r2, int64_t N,
                                                   int64_t ld, int want_seeds, const double* __restrict__ slots, int nslots,
-                                                  double* __restrict__ sums_out, double* __restrict__ lsums_out) {
+                                                  double* __restrict__ sums_out, double* __restrict__ lsums_out,
+                                                  const float* __restrict__ qw = nullptr) {
     constexpr int D = C - 1 - E;
     __shared__ double red[16];
     double sr2 = 0.0;
@@ -311,11 +328,13 @@ __global__ __launch_bounds__(1024) void k_seed_pde(Phys ph, Pts x, const float* 
         float V = potential_at(ph, xv, Vpre, m);
         float u[2] = {0.f, 0.f}, r[2] = {0.f, 0.f}, rb[2] = {0.f, 0.f};
         float cr = (float)(2.0 * (double)ph.w_pde / ph.n_global);
+        float qv = 1.0f;
+        if constexpr (WQ) qv = qw[m];
         for (int o = 0; o < ph.n_out; ++o) {
             u[o] = u_in[(int64_t)o * ld + m];
             r[o] = Hu_in[(int64_t)o * ld + m] - lam * u[o];
             rb[o] = cr * r[o];
-            sr2 += (double)(r[o] * r[o]);
+            sr2 += wq_term<WQ>((double)qv, r[o] * r[o]);
             if (resid_out) resid_out[m * ph.n_out + o] = r[o];
         }
         if (want_seeds) {
@@ -401,12 +420,39 @@ __global__ __launch_bounds__(1024) void k_seed_pde(Phys ph, Pts x, const float* 
                     }
                 }
 #pragma unroll
-                for (int c = 0; c < C; ++c) Ob[((int64_t)c * ph.n_out + o) * ld + m] = sc * Ub[c];
+                for (int c = 0; c < C; ++c) {
+                    if constexpr (WQ) Ob[((int64_t)c * ph.n_out + o) * ld + m] = qv * (sc * Ub[c]);
+                    else Ob[((int64_t)c * ph.n_out + o) * ld + m] = sc * Ub[c];
+                }
             }
         }
     }
     double t = block_sum_256(sr2, red);
     if (threadIdx.x == 0) atomicAdd(sum_r2, t);
+}
+
+// ---- quadrature weights (gpe_bind_weights): the total of the array and a count of entries the engine refuses ------------------
+// One workgroup, fixed order, fp64, no atomics: thread t adds entries t, t + 1024, ... in index order, then the wave shuffle tree and
+// the waves in order.  out[0] = sum of the finite, non-negative entries, out[1] = number of entries that are negative or not finite.
+// Runs once per bind (the bind synchronises to read both), never inside a step.
+#define WQ_THREADS 1024
+__global__ __launch_bounds__(WQ_THREADS) void k_weight_total(const float* __restrict__ qw, int64_t n, double* __restrict__ out) {
+    __shared__ double red[2 * (WQ_THREADS / 64)];
+    double s = 0.0, bad = 0.0;
+    for (int64_t m = threadIdx.x; m < n; m += WQ_THREADS) {
+        const float q = qw[m];
+        if (q >= 0.f && isfinite(q)) s += (double)q;
+        else bad += 1.0;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { s += __shfl_down(s, o, 64); bad += __shfl_down(bad, o, 64); }
+    if ((threadIdx.x & 63) == 0) { red[2 * (threadIdx.x >> 6)] = s; red[2 * (threadIdx.x >> 6) + 1] = bad; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double ts = 0.0, tb = 0.0;
+        for (int i = 0; i < WQ_THREADS / 64; ++i) { ts += red[2 * i]; tb += red[2 * i + 1]; }
+        out[0] = ts; out[1] = tb;
+    }
 }
 
 // ---- boundary batch (value only): e = base + s*NN - target; sum e^2; Ob = w_bc*2/(cnt) * e * s / world ------
@@ -467,6 +513,7 @@ __global__ __launch_bounds__(256) void k_seed_sym(Phys ph, const float* __restri
 }
 
 // ---- pre-training: loss = mean((NN - target)^2)  (refine/harmonic_pinn_simulation.py:667-668) -----------------------------
+// (unweighted whatever gpe_bind_weights bound: the engine hands it a Phys whose n_global is the point count)
 __global__ __launch_bounds__(256) void k_seed_mse(Phys ph, const float* __restrict__ x, const float* __restrict__ target,
                                                   const float* __restrict__ O, float* __restrict__ Ob,
                                                   double* __restrict__ acc, int64_t N, int64_t ld) {

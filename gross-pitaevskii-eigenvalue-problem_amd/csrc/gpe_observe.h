@@ -12,6 +12,9 @@
 //   k_obs_finish  one workgroup adds those partials in index order and writes the struct (staging slot or monitor ring)
 // Every point belongs to a fixed thread, every partial to a fixed slab row, every sum is added in a fixed tree: no atomics, so a
 // record repeats bit for bit (README, "Reproducibility").
+// WQ (gpe_observables on the bound set while gpe_bind_weights is in force): every point's summands take its quadrature weight qw[m] --
+// the sums approximate integrals with dv * q_i as the measure -- and the peak density stays the plain maximum.  An explicit point set
+// and the monitor run the WQ = false instances, which do not read qw.
 #pragma once
 #include "gpe_head.h"
 
@@ -70,11 +73,11 @@ GPE_DEV void obs_point(const Phys& ph, float base_norm, const float* __restrict_
     for (int o = 0; o < ph.n_out; ++o) load_u_jets<C, D>(ph, O, ld, m, o, xv, base_norm, bptr, U[o]);
 }
 
-template <int D>
+template <int D, bool WQ = false>
 __global__ __launch_bounds__(OBS_THREADS) void k_obs_pass1(Phys ph, float base_norm, const float* __restrict__ x,
                                                            const float* __restrict__ Vpre, const float* __restrict__ O,
                                                            const float* const* __restrict__ bptr, int64_t N, int64_t ld,
-                                                           double* __restrict__ slab) {
+                                                           double* __restrict__ slab, const float* __restrict__ qw = nullptr) {
     constexpr int C = 1 + 2 * D;
     __shared__ double lds[(OBS_THREADS / 64) * OB_COUNT];
     double acc[OB_COUNT];
@@ -94,7 +97,7 @@ __global__ __launch_bounds__(OBS_THREADS) void k_obs_pass1(Phys ph, float base_n
             for (int k = 0; k < D; ++k) { const double uk = (double)U[o][1 + k]; g2 += uk * uk; lap += (double)U[o][1 + D + k]; }
             ulap += u * lap;
         }
-        double s;
+        double s, lz = 0.0;          // (lz: the weighted instance only)
         if (!ph.complex_psi) {
             const double u = (double)U[0][0], a = ph.abs_power ? fabs(u) : u;
             double pw = 1.0;
@@ -106,12 +109,21 @@ __global__ __launch_bounds__(OBS_THREADS) void k_obs_pass1(Phys ph, float base_n
                 const double xx = (double)xv[0], yy = (double)xv[1];
                 const double Dr = xx * (double)U[0][2] - yy * (double)U[0][1];
                 const double Di = xx * (double)U[1][2] - yy * (double)U[1][1];
-                acc[OB_L] += (double)U[0][0] * Di - (double)U[1][0] * Dr;
+                if constexpr (WQ) lz = (double)U[0][0] * Di - (double)U[1][0] * Dr;
+                else acc[OB_L] += (double)U[0][0] * Di - (double)U[1][0] * Dr;
             }
         }
-        acc[OB_I] += rho; acc[OB_K] += g2; acc[OB_P] += V * rho; acc[OB_S] += s; acc[OB_LAP] += ulap;
+        if constexpr (WQ) {
+            const double q = (double)qw[m];
+            acc[OB_L] += q * lz;
+            acc[OB_I] += q * rho; acc[OB_K] += q * g2; acc[OB_P] += q * (V * rho); acc[OB_S] += q * s; acc[OB_LAP] += q * ulap;
 #pragma unroll
-        for (int k = 0; k < D; ++k) { const double xk = (double)xv[k]; acc[OB_X + k] += xk * rho; acc[OB_XX + k] += xk * xk * rho; }
+            for (int k = 0; k < D; ++k) { const double xk = (double)xv[k]; acc[OB_X + k] += q * (xk * rho); acc[OB_XX + k] += q * (xk * xk * rho); }
+        } else {
+            acc[OB_I] += rho; acc[OB_K] += g2; acc[OB_P] += V * rho; acc[OB_S] += s; acc[OB_LAP] += ulap;
+#pragma unroll
+            for (int k = 0; k < D; ++k) { const double xk = (double)xv[k]; acc[OB_X + k] += xk * rho; acc[OB_XX + k] += xk * xk * rho; }
+        }
         acc[OB_MAX] = fmax(acc[OB_MAX], rho);              // (fmax drops NaNs: k_obs_finish takes the NaN of the norm instead)
     }
     const double r = obs_block_reduce<OB_COUNT>(acc, OB_NSUM, lds);
@@ -155,11 +167,12 @@ GPE_DEV ObsParts obs_parts(const Phys& ph, const double* __restrict__ raw, doubl
     return q;
 }
 
-template <int D>
+template <int D, bool WQ = false>
 __global__ __launch_bounds__(OBS_THREADS) void k_obs_pass2(Phys ph, float base_norm, const float* __restrict__ x,
                                                            const float* __restrict__ Vpre, const float* __restrict__ O,
                                                            const float* const* __restrict__ bptr, int64_t N, int64_t ld,
-                                                           const double* __restrict__ raw, double dv, double* __restrict__ slab) {
+                                                           const double* __restrict__ raw, double dv, double* __restrict__ slab,
+                                                           const float* __restrict__ qw = nullptr) {
     constexpr int C = 1 + 2 * D;
     __shared__ double lds[OBS_THREADS / 64];
     const ObsParts q = obs_parts(ph, raw, dv);
@@ -195,7 +208,8 @@ __global__ __launch_bounds__(OBS_THREADS) void k_obs_pass2(Phys ph, float base_n
         }
         for (int o = 0; o < ph.n_out; ++o) {
             const double r = (lin[o] - q.mu * (double)U[o][0]) * is1 + non[o] * isp;      // H[phi] phi - mu phi
-            acc[0] += r * r;
+            if constexpr (WQ) acc[0] += (double)qw[m] * (r * r);
+            else acc[0] += r * r;
         }
     }
     const double r = obs_block_reduce<1>(acc, 1, lds);

@@ -78,3 +78,53 @@ __global__ __launch_bounds__(SMP_THREADS) void k_sampler_draw(SamplerGrid g, int
         if (xs) { xs[j * g.dim + k] = v[k]; xs[(n + j) * g.dim + k] = -v[k]; }
     }
 }
+
+// ---- graded grids (gpe_bind_sampler_graded) -------------------------------------------------------------------------------------------
+// The same draw on a tensor-product grid with caller-given, non-uniform cell edges: axis k has shape[k] cells, cell i spans
+// [edges_k[i], edges_k[i + 1]].  Same Philox call, counter / key layout, word per axis and cell numbering as k_sampler_draw; per axis
+//   a, b   edges_k[i], edges_k[i + 1]
+//   w      b - a                                  one rounded fp32 subtraction: the cell's width
+//   x      a + u * w                              smp_mul_then_add: one rounded multiply, one rounded add, never an fma
+//   clip   as above, by comparisons
+// and the point's quadrature weight is its cell's volume q = w_0, then q * w_1, then * w_2: rounded fp32 multiplies in axis order.  The
+// weights do not depend on the draw: qw != NULL (the bind) writes them, the redraws pass NULL.  g.lo / g.h are not read.
+// gpe_pinn/sampler.py:graded_points / graded_weights restate both in numpy, bit for bit.  Plain vector stores only.
+__global__ __launch_bounds__(SMP_THREADS) void k_sampler_draw_graded(SamplerGrid g, const float* __restrict__ e0, const float* __restrict__ e1,
+                                                                     const float* __restrict__ e2, int64_t first_cell, int64_t n, uint64_t draw,
+                                                                     float* __restrict__ x, float* __restrict__ qw) {
+    const int64_t j = (int64_t)blockIdx.x * SMP_THREADS + threadIdx.x;
+    if (j >= n) return;
+    const uint64_t cell = (uint64_t)(first_cell + j);
+    uint32_t r[4];
+    philox4x32_10((uint32_t)cell, (uint32_t)(cell >> 32), (uint32_t)draw, (uint32_t)(draw >> 32), g.key0, g.key1, r);
+    uint64_t rest = cell;
+    float v[3], w[3];
+#pragma unroll
+    for (int k = 2; k >= 0; --k) {
+        if (k >= g.dim) continue;
+        const float* __restrict__ ed = k == 0 ? e0 : (k == 1 ? e1 : e2);
+        const uint64_t s = (uint64_t)g.shape[k];
+        const uint64_t q = rest / s;
+        const uint32_t ik = (uint32_t)(rest - q * s);         // < shape[k]: edges_k holds shape[k] + 1 entries
+        rest = q;
+        const float a = ed[ik], b = ed[ik + 1];
+        const float u = (float)(r[k] >> 8) * 0x1p-24f;
+        w[k] = b - a;
+        float xv = smp_mul_then_add(a, u, w[k]);
+        xv = xv < g.clip_lo[k] ? g.clip_lo[k] : xv;
+        xv = xv > g.clip_hi[k] ? g.clip_hi[k] : xv;
+        v[k] = xv;
+    }
+    float qv = w[0];
+#pragma unroll
+    for (int k = 1; k < 3; ++k) {
+        if (k >= g.dim) continue;
+        qv = qv * w[k];
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        if (k >= g.dim) continue;
+        x[j * g.dim + k] = v[k];
+    }
+    if (qw) qw[j] = qv;
+}

@@ -325,6 +325,7 @@ class Engine:
             raise ValueError(f"x must be [N,{self.cfg.dim}]")
         Vt = None if V is None else self._to_dev(V, "V").reshape(-1)
         self._keep["x"], self._keep["V"] = x, Vt
+        self._keep.pop("q", None)                            # (the engine drops bound weights at every bind of points)
         self._chk(self.lib.gpe_bind_points(self._h, C.c_void_p(x.data_ptr()), x.shape[0],
                                            C.c_void_p(Vt.data_ptr()) if Vt is not None else None))
         self.n_local = int(x.shape[0])
@@ -369,6 +370,57 @@ class Engine:
         view = _DeviceArrayView(p.value, (int(n.value), self.cfg.dim))      # the engine's buffer as a tensor, without owning it ...
         out = torch.as_tensor(view, device=f"cuda:{self.device}").clone()    # ... and the copy the caller keeps
         return out, int(d.value)
+
+    # ---- per-point quadrature weights (include/gpe_hip.h: gpe_bind_weights) ---------------------------------------------------------------
+    def bind_weights(self, q, total=None):
+        """One weight q_i >= 0 per bound collocation row: every collocation sum takes q_i and every N of a mean becomes W = sum q over
+        all ranks (total; None: this engine's own sum).  cfg.dx stays the multiplier it is -- with cell volumes as weights set dx = 1.
+        bind_points / bind_sampler clear the weights; None clears them here."""
+        if q is None:
+            return self.clear_weights()
+        t = self._to_dev(q, "q").reshape(-1)
+        if t.numel() != getattr(self, "n_local", 0):
+            raise ValueError(f"q must hold one weight per bound point ({getattr(self, 'n_local', 0)})")
+        self._chk(self.lib.gpe_bind_weights(self._h, C.c_void_p(t.data_ptr()), 0.0 if total is None else float(total)))
+        self._keep["q"] = t                                  # (kept only once the engine reads it: a refused bind leaves the old array bound)
+
+    def clear_weights(self):
+        self._chk(self.lib.gpe_bind_weights(self._h, None, 0.0))
+        self._keep.pop("q", None)
+
+    def weights(self) -> dict:
+        """dict(q, local, total): a copy of the weights the step reads (the caller's, or the graded sampler's cell volumes) as a device
+        tensor [n_local], this engine's sum of them and W; synchronises."""
+        p, n, wl, wt = C.c_void_p(), C.c_int64(), C.c_double(), C.c_double()
+        self._chk(self.lib.gpe_weights(self._h, C.byref(p), C.byref(n), C.byref(wl), C.byref(wt)))
+        view = _DeviceArrayView(p.value, (int(n.value),))
+        return dict(q=torch.as_tensor(view, device=f"cuda:{self.device}").clone(), local=wl.value, total=wt.value)
+
+    def bind_sampler_graded(self, edges, every: int, seed: int = 0, first_cell: int = 0, n=None, draw0: int = 0, clip=None):
+        """Graded stratified sampler: bind_sampler on the tensor-product grid whose cells are bounded by `edges` -- one strictly increasing
+        array of cell edges per axis (shape[k] = len(edges[k]) - 1) -- with every point weighted by its cell's volume (bind_weights is
+        implied; total = the whole grid's volume, so set cfg.dx = 1).  sampler.graded_points / graded_weights / graded_total rebuild
+        points, weights and W on the CPU, bit for bit; sampler.sinh_edges makes centre-refined edges."""
+        from . import sampler
+        ed = sampler._edges(edges)
+        d = len(ed)
+        sp = capi.gpe_sampler_spec()          # what the engine cannot honour it refuses itself (GPE_ERR_INVALID): nothing is judged here
+        clo = [float(a[0]) for a in ed] if clip is None else [float(v) for v in sampler._per_axis(clip[0], d, "clip[0]")]
+        chi = [float(a[-1]) for a in ed] if clip is None else [float(v) for v in sampler._per_axis(clip[1], d, "clip[1]")]
+        total = 1
+        for k in range(d):
+            sp.shape[k] = ed[k].size - 1
+            sp.lo[k], sp.hi[k], sp.clip_lo[k], sp.clip_hi[k] = float(ed[k][0]), float(ed[k][-1]), clo[k], chi[k]
+            total *= ed[k].size - 1
+        sp.seed = int(seed) & (2 ** 64 - 1)
+        sp.first_cell = int(first_cell)
+        sp.n_local = total - int(first_cell) if n is None else int(n)
+        sp.draw0, sp.every = int(draw0), int(every)
+        ptrs = [ed[k].ctypes.data_as(C.c_void_p) if k < d else None for k in range(3)]
+        self._chk(self.lib.gpe_bind_sampler_graded(self._h, C.byref(sp), *ptrs))
+        self._keep["x"], self._keep["V"] = None, None
+        self._keep.pop("q", None)
+        self.n_local = int(sp.n_local)
 
     def bind_boundary(self, xb, target=None):
         if xb is None:

@@ -99,3 +99,95 @@ def node_centred(half, n_nodes):
     n_nodes = np.atleast_1d(np.asarray(n_nodes, dtype=np.int64))
     hh = 2.0 * half / (n_nodes - 1)
     return -half - hh / 2, half + hh / 2, (-half, half)
+
+
+# ---- graded grids (csrc/gpe_sampler.h: k_sampler_draw_graded, include/gpe_hip.h: gpe_bind_sampler_graded) -----------------------------
+# The same draw on a tensor-product grid with caller-given, non-uniform cell edges; every point is weighted by its cell's volume.  Per
+# axis, cell i: a = edges[i], b = edges[i + 1], w = b - a (one rounded fp32 subtraction), x = a + u * w (one rounded multiply, one
+# rounded add), the clip by comparisons; weight q = w_0, then q * w_1, then * w_2 (rounded fp32 multiplies in axis order); total
+# W = product over the axes of the fp64 sums, in index order, of the fp32 widths.
+
+def _edges(edges):
+    """[float32 array of cell edges per axis]; a single 1D array of numbers is one axis."""
+    if isinstance(edges, np.ndarray) and edges.ndim == 1 or (len(edges) > 0 and np.isscalar(edges[0])):
+        edges = [edges]
+    ed = [np.ascontiguousarray(np.asarray(a, dtype=np.float32).ravel()) for a in edges]
+    if not 1 <= len(ed) <= 3:
+        raise ValueError("edges: 1 to 3 axes")
+    for a in ed:
+        if a.size < 2 or a.size - 1 > 1 << 24 or not np.all(np.isfinite(a)) or not np.all(a[1:] > a[:-1]):
+            raise ValueError("edges: per axis 2 .. 2^24 + 1 finite, strictly increasing values")
+    return ed
+
+
+def _graded_block(ed, first_cell, n):
+    shape = tuple(a.size - 1 for a in ed)
+    total = int(np.prod([int(s) for s in shape]))
+    first_cell = int(first_cell)
+    n = total - first_cell if n is None else int(n)
+    if first_cell < 0 or n <= 0 or first_cell + n > total:
+        raise ValueError(f"cells [{first_cell}, {first_cell + n}) outside the grid's {total}")
+    cell = np.arange(first_cell, first_cell + n, dtype=np.uint64)
+    return cell, np.unravel_index(cell.astype(np.int64), shape)          # row-major: last axis fastest
+
+
+def graded_points(edges, seed, draw, first_cell: int = 0, n=None, clip=None) -> np.ndarray:
+    """Draw `draw` of the graded stratified set with seed `seed`: rows are cells first_cell .. first_cell + n - 1 (n None: all cells) of
+    the grid bounded by `edges`; clip = (clip_lo, clip_hi), default the end edges.  float32 [n, d]: what Engine.bind_sampler_graded holds."""
+    ed = _edges(edges)
+    d = len(ed)
+    cell, idx = _graded_block(ed, first_cell, n)
+    clo = np.array([a[0] for a in ed], np.float32) if clip is None else _per_axis(clip[0], d, "clip[0]")
+    chi = np.array([a[-1] for a in ed], np.float32) if clip is None else _per_axis(clip[1], d, "clip[1]")
+    if np.any(chi < clo):
+        raise ValueError("clip[1] < clip[0]")
+    seed, draw = int(seed) & (2 ** 64 - 1), int(draw) & (2 ** 64 - 1)
+    ctr = np.empty((cell.size, 4), dtype=np.uint64)
+    ctr[:, 0], ctr[:, 1] = cell & _MASK, cell >> _S32
+    ctr[:, 2], ctr[:, 3] = draw & 0xFFFFFFFF, draw >> 32
+    r = philox4x32(ctr, np.array([seed & 0xFFFFFFFF, seed >> 32], dtype=np.uint64))
+    x = np.empty((cell.size, d), dtype=np.float32)
+    for k in range(d):
+        u = (r[:, k] >> np.uint32(8)).astype(np.float32) * np.float32(2.0 ** -24)
+        a, b = ed[k][idx[k]], ed[k][idx[k] + 1]
+        w = b - a
+        xk = a + u * w
+        xk = np.where(xk < clo[k], clo[k], xk)
+        xk = np.where(xk > chi[k], chi[k], xk)
+        x[:, k] = xk
+    return x
+
+
+def graded_weights(edges, first_cell: int = 0, n=None) -> np.ndarray:
+    """The cell volumes of rows first_cell .. first_cell + n - 1, float32 [n]: the weights Engine.bind_sampler_graded binds (no draw
+    changes them)."""
+    ed = _edges(edges)
+    _, idx = _graded_block(ed, first_cell, n)
+    q = None
+    for k in range(len(ed)):
+        w = ed[k][idx[k] + 1] - ed[k][idx[k]]
+        q = w if q is None else q * w
+    return q.astype(np.float32)
+
+
+def graded_total(edges) -> float:
+    """W of the whole grid as the engine forms it: per axis the fp64 sum, in index order, of the fp32 widths; their product in axis order."""
+    W = 1.0
+    for a in _edges(edges):
+        w = (a[1:] - a[:-1]).astype(np.float64)
+        W *= float(np.cumsum(w)[-1])                  # (cumsum adds in index order; np.sum adds pairwise)
+    return W
+
+
+def sinh_edges(half, cells, stretch):
+    """cells + 1 edges on [-half, half], refined towards the centre: x_i = half * sinh(stretch * t_i) / sinh(stretch), t_i = -1 + 2 i / cells
+    (centre cells are narrower than the outer ones by about stretch / sinh(stretch) ... stretch * cosh(stretch) / sinh(stretch)).
+    stretch -> 0 gives the uniform grid.  Symmetric by construction, end edges exactly -half and half.  float32."""
+    cells = int(cells)
+    if cells < 1 or not half > 0 or stretch < 0:
+        raise ValueError("sinh_edges: cells >= 1, half > 0, stretch >= 0")
+    t = (2.0 * np.arange(cells + 1, dtype=np.float64) - cells) / cells          # exactly antisymmetric: t[cells - i] == -t[i]
+    r = np.abs(t) if stretch < 1e-8 else np.sinh(stretch * np.abs(t)) / np.sinh(stretch)
+    e = (half * r).astype(np.float32) * np.sign(t).astype(np.float32)
+    e[0], e[-1] = -np.float32(half), np.float32(half)
+    return e

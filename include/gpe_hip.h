@@ -267,6 +267,52 @@ int gpe_bind_sampler(gpe_engine* e, const gpe_sampler_spec* spec);
  * Replaces: reading back the bound set in tools/accuracy_nd.py:run_epochs (the host there built it; no reference counterpart). */
 int gpe_sampler_points(gpe_engine* e, const float** d_x, int64_t* n, int64_t* draw);
 
+/* ---- per-point quadrature weights -------------------------------------------------------------------------------------------------
+ * d_q [n_local] fp32 on the device, one weight q_i >= 0 per bound collocation row, caller-owned like d_V.  While weights are bound
+ *   sums   every sum over collocation points takes the factor q_i: num, den, the orthogonality overlaps, the Riesz / energy sums, sum r^2
+ *   means  every N of a mean becomes W = sum q_i over ALL ranks: w_pde sum q r^2 / W, the 2 w_pde / W of the seeds, the energy-lambda
+ *          branch, w_reg_f / (sum q u^2 / W + eps).  gpe_config.dx stays the plain multiplier it is (I = dx sum q u^2, overlaps
+ *          dx sum q psi_k u): a caller whose q_i are cell volumes sets dx = 1
+ *   seeds  dLoss / d(output jets of row i) = the unweighted expression with N -> W, times q_i; a row with q_i = 0 contributes nothing
+ *   rows   boundary rows riding in the batch and the separate boundary batch have no weight
+ *   gpe_scalars.num / den / sum_r2 / integral report the weighted sums.
+ * With integer weights the step equals the unweighted step on the batch with row i repeated q_i times and n_global = sum q.
+ * The step then forms head and seeds with the weighted instances of the standalone kernels (k_head_pde / k_seed_pde), at every batch
+ * size: the fused head / seed code of the small-batch kernels has no weights (gpe_active_kernels names them: ";head=...;seed=...").
+ * gpe_observables on the bound set (d_x == NULL) honours the weights: every sum takes q_i, dv stays the multiplier, peak_density stays
+ * the plain maximum, n the row count.  An explicit d_x, the monitor and the gpe_mse_* pre-training loss are and stay unweighted.
+ * The bind reduces the array once (one kernel, fp64, fixed order, no atomics) and synchronises once: w_local = sum q_i of this rank.
+ * w_total > 0: the caller's W over all ranks (data-parallel runs); 0: W = w_local.  d_q == NULL clears the weights and restores the
+ * count-based N.  gpe_bind_points and gpe_bind_sampler clear bound weights (weights belong to rows).  While weights are bound
+ * gpe_set_n_global returns GPE_ERR_STATE and gpe_set_loss_weights with w_sym != 0 GPE_ERR_INVALID.  A captured graph is rebuilt after
+ * a bind or a clear, as after a bind of points.
+ * GPE_ERR_INVALID: a negative or non-finite entry, w_local == 0, w_total negative or not finite, w_sym != 0 (the symmetry batch has no
+ * weights).  GPE_ERR_STATE: no points bound, or a sampler bound (its rows move; d_q == NULL under a graded sampler, which owns its
+ * weights, too).  A bind that fails leaves what was there.
+ * Replaces: nothing a caller could do host-side -- without weights every training set had to be a uniform grid (the reference's 2D
+ * prepare_training_data draws a polar set and weights nothing: src/gross_pitaevskii_2D.py). */
+int gpe_bind_weights(gpe_engine* e, const float* d_q, double w_total);
+/* synchronise; the array the step reads (the caller's, or the graded sampler's own), its length, sum q_i of this rank and W.  Any out
+ * pointer may be NULL.  GPE_ERR_STATE: no weights bound.
+ * Replaces: the caller's own bookkeeping of sum q (and, under a graded sampler, rebuilding the cell volumes on the host). */
+int gpe_weights(gpe_engine* e, const float** d_q, int64_t* n, double* w_local, double* w_total);
+/* Graded stratified sampler: gpe_bind_sampler on a tensor-product grid with caller-given, non-uniform cell edges -- one uniformly
+ * placed point per cell, weighted by its cell's volume.  spec as for gpe_bind_sampler (shape, clip_*, seed, first_cell, n_local, draw0,
+ * every mean what they mean there); h_edges{k}: HOST array of shape[k] + 1 strictly increasing finite floats per used axis (NULL for
+ * the others), copied to the device here; spec.lo[k] / hi[k] must equal the first / last edge.
+ *   point   cell i of axis k: a = edges_k[i], b = edges_k[i + 1], w = b - a (one rounded fp32 subtraction), u as above,
+ *           x = a + u * w (one rounded multiply, one rounded add, never an fma), then the clip by comparisons
+ *   weight  q = w_0, then q * w_1, then * w_2: rounded fp32 multiplies in axis order; written once at the bind (no draw changes it)
+ *   W       product over the axes of the fp64 sums, in index order, of the fp32 widths -- of the WHOLE grid, not of this rank's block
+ * gpe_pinn/sampler.py (graded_points, graded_weights, graded_total) restates all three, bit for bit.  The bind allocates the engine-owned
+ * point buffer and an engine-owned weight buffer [n_local], draws draw0, and binds both (as gpe_bind_weights with w_total = W).  Cadence,
+ * graph cutting, gpe_sampler_points, the refill of frozen orthogonality states behind every redraw and the data-parallel / three-phase
+ * entry points behave as with the uniform sampler.  gpe_bind_sampler(NULL) and gpe_bind_points clear it, weights included.
+ * GPE_ERR_INVALID: whatever gpe_bind_sampler refuses, edges that are missing, not finite or not strictly increasing, lo / hi other than
+ * the end edges, w_sym != 0.
+ * Replaces: a host loop that redraws a graded set, recomputes nothing but uploads points every K steps (no reference counterpart). */
+int gpe_bind_sampler_graded(gpe_engine* e, const gpe_sampler_spec* spec, const float* h_edges0, const float* h_edges1, const float* h_edges2);
+
 /* ---- forward-only entry points ---------------------------------------------------------------- */
 /* model.forward(x) (refine/...:121-125): d_out [n, out] row-major */
 int gpe_forward(gpe_engine* e, const float* d_x, int64_t n, float* d_out);
@@ -378,7 +424,9 @@ int gpe_stop_state(gpe_engine* e, int* stopped, int64_t* stop_step);
  * loss = mean((NN(x) - target)^2) on the bound points; d_target [n_local,out].  gpe_mse_step: one plain Adam step (no
  * clipping, no scheduler, refine/...:663-670); gpe_mse_loss_grad: loss + gradient without update (the reference's L-BFGS
  * tail, refine/...:672-687, runs host-side on these; read the gradient with gpe_get_grad).  Single-rank entry points; the
- * phases gpe_mse_begin / gpe_mse_update bracket an all-reduce of the gradient exchange buffer when world_size > 1. */
+ * phases gpe_mse_begin / gpe_mse_update bracket an all-reduce of the gradient exchange buffer when world_size > 1.
+ * The pre-training loss is and stays UNWEIGHTED: quadrature weights bound by gpe_bind_weights change neither its sum nor its mean
+ * (n_global, or the bound count). */
 int gpe_bind_target(gpe_engine* e, const float* d_target);
 int gpe_mse_begin(gpe_engine* e);                    /* forward, seeds, reverse -> gradient exchange buffer (tail: sum of squares) */
 int gpe_mse_update(gpe_engine* e);                   /* Adam on the exchanged gradient */
@@ -390,7 +438,7 @@ int gpe_set_gamma(gpe_engine* e, float gamma);
 int gpe_set_power(gpe_engine* e, int p);
 int gpe_set_lr(gpe_engine* e, float lr);
 int gpe_set_perturb_scale(gpe_engine* e, float s);
-int gpe_set_n_global(gpe_engine* e, int64_t n_global);
+int gpe_set_n_global(gpe_engine* e, int64_t n_global);   /* GPE_ERR_STATE while quadrature weights are bound: N is their total W */
 /* loss weights between steps: the host-side ReLoBRaLo balancing of src/gross_pitaevskii_2D_ReLoBRaLo.py:259-342 only needs the
  * per-term scalars gpe_residual / gpe_step return and this setter.  w[6] = {pde, bc, norm, sym, orth, riesz}. */
 int gpe_set_loss_weights(gpe_engine* e, const float w[6]);

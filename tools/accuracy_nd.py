@@ -41,6 +41,9 @@ ap.add_argument("--resample", type=int, default=0, help="epochs between changes 
 ap.add_argument("--sets", type=int, default=16, help="number of jittered collocation sets cycled through")
 ap.add_argument("--device-sampler", action="store_true", help="with --resample: the engine's own sampler (Engine.bind_sampler) draws a fresh stratified set on "
                                                              "the device every --resample epochs, instead of cycling through --sets sets built here")
+ap.add_argument("--graded", type=float, default=None, metavar="STRETCH",
+                help="with --device-sampler: train on the GRADED sampler (Engine.bind_sampler_graded) -- the same number of cells per axis over the box, "
+                     "refined towards the centre by sampler.sinh_edges(half, n, STRETCH), every point weighted by its cell volume")
 ap.add_argument("--big-grid", default="", help="e.g. 64,128,64: after the schedule, continue on THIS grid (BASELINE's per-GPU size) for --big-epochs epochs "
                                                "at the low end of the learning-rate ladder, and evaluate mu there (same weights, fresh Adam)")
 ap.add_argument("--big-epochs", type=int, default=3000)
@@ -77,6 +80,8 @@ flat = bench.reference_init(cs["layers"], seed=a.seed)
 cfg = gpe_pinn.GPEConfig(layers=cs["layers"], gamma=0.0, p=3, kinetic_coeff=0.5, pot_scale=0.5, omega=tuple(cs["omega"]) + (1.0,) * (3 - d),
                          dx=dv, w_bc=a.w_bc, w_norm=a.w_norm, lr=a.lr, sched=capi.SCHED_CONST, history_capacity=8,
                          w_riesz=a.w_riesz, riesz_kind=capi.RIESZ_VARIATIONAL)
+if a.graded is not None:
+    cfg.dx = 1.0                            # the quadrature weights are the cell volumes themselves (the regular grid gets weights of dv below)
 eng = gpe_pinn.Engine(cfg)
 eng.set_params(flat)
 xd = torch.as_tensor(X, device="cuda")
@@ -85,6 +90,9 @@ eng.bind_boundary(torch.as_tensor(xb, device="cuda"))
 # stratified collocation sets (--resample): the grid point moved uniformly inside its cell; the first and last cells of an axis stay inside the box
 xsets = [xd]
 device_sampler = a.device_sampler and a.resample > 0
+graded = a.graded is not None
+if graded and not device_sampler:
+    ap.error("--graded needs --device-sampler and --resample")
 if a.resample > 0 and not device_sampler:
     rng = np.random.default_rng(1234 + a.seed)
     for _ in range(a.sets):
@@ -121,7 +129,12 @@ for i in range(a.pretrain):
     elif i % 500 == 0:
         print(f"pretrain {i}: mse {sc['loss']:.3e}", flush=True)
 eng.bind_target(None)
-if device_sampler:
+edges = None
+if graded:
+    from gpe_pinn.sampler import sinh_edges
+    edges = [sinh_edges(half, n, a.graded)] * d
+    eng.bind_sampler_graded(edges, every=a.resample, seed=1234 + a.seed)
+elif device_sampler:
     # cells centred on the grid nodes (so the quadrature weight stays the cell volume dv), points kept inside the physical box
     from gpe_pinn.sampler import node_centred
     s_lo, s_hi, s_clip = node_centred([half] * d, [n] * d)
@@ -156,6 +169,8 @@ for si, g in enumerate(gam):
     sc = eng.read_scalars()
     if last and a.resample > 0:                 # the reported numbers: on the REGULAR grid, not on the last jittered set
         eng.bind_points(xd)
+        if graded:                          # cfg.dx is 1 in this mode: the regular grid's quadrature weight rides as a per-point weight
+            eng.bind_weights(torch.full((X.shape[0],), dv, device="cuda"))
         sc = eng.residual(want_fields=False)[0]
     rows.append(dict(gamma=g, epochs=ne, mu=sc["mu"], loss=sc["loss"], pde=sc["pde"], norm=sc["integral"], lr=sc["lr"], riesz=sc["riesz"]))
     print(f"stage {si}: gamma {g:8.2f} mu {sc['mu']:.6f} E {sc['riesz']:.6f} loss {sc['loss']:.3e} pde {sc['pde']:.3e} int {sc['integral']:.6f} lr {sc['lr']:.1e} "
@@ -234,7 +249,8 @@ out = dict(case=a.case, workload=cs["workload"], layers=cs["layers"], points=int
            density_rel_l2=float(np.sqrt(((dens - dref) ** 2).sum() / (dref ** 2).sum())),
            schedule=dict(pretrain=a.pretrain, epochs=a.epochs, final=a.final, stages=a.stages, lr=a.lr, w_norm=a.w_norm, w_bc=a.w_bc,
                          w_riesz=a.w_riesz, w_norm_final=a.w_norm_final, resample=a.resample, sets=a.sets,
-                         sampler=("device" if device_sampler else "host_cycle") if a.resample > 0 else "fixed_grid",
+                         sampler=("device_graded" if graded else "device" if device_sampler else "host_cycle") if a.resample > 0 else "fixed_grid",
+                         graded_stretch=a.graded, graded_edges=(None if edges is None else [float(v) for v in edges[0]]),
                          scheduler="constant lr per stage, fresh Adam per stage; last stage lr x (1, 0.3, 0.1, 0.03, 0.01, 0.003, 0.001)"),
            energy=rows[-1]["riesz"], energy_ref=truth["energy"], big_grid=big, kept=kept,
            observables={k: _obs[k] for k in ("norm", "kin", "pot", "inter", "energy", "mu", "mu_lap", "var_x", "peak_density", "res_rms")})

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Wall time per step of gpe_run for any network / batch size (harmonic trap, north-star loss):  step_time_nd.py 2,128,128,128,128,128,1 16384 [steps]"""
+"""Wall time per step of gpe_run for any network / batch size (harmonic trap, north-star loss):  step_time_nd.py 2,128,128,128,128,128,1 16384 [steps] [ones]
+A fourth argument `ones` binds quadrature weights of 1 (Engine.bind_weights): the same step on the standalone weighted head / seed kernels."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -14,9 +15,12 @@ eng = gpe_pinn.Engine(cfg)
 torch.manual_seed(0)
 eng.set_params((torch.randn(eng.n_params) * 0.1).numpy())
 eng.bind_points(torch.as_tensor(x, device="cuda"))
+ones = len(sys.argv) > 4 and sys.argv[4] == "ones"
+if ones:
+    eng.bind_weights(torch.ones(N, device="cuda"))
 eng.run(30); eng.synchronize()
 t = []
 for _ in range(3):
     t0 = time.perf_counter(); eng.run(steps); eng.synchronize(); t.append((time.perf_counter() - t0) / steps * 1e6)
 k = eng.active_kernels
-print("%s N=%d: %.1f us/step  %.3g points/s  fwd=%s bwd=%s" % (sys.argv[1], N, min(t), N / min(t) * 1e6, k["fwd"][:28], k["bwd"][:28]))
+print("%s N=%d%s: %.1f us/step  %.3g points/s  fwd=%s bwd=%s" % (sys.argv[1], N, " weights=1" if ones else "", min(t), N / min(t) * 1e6, k["fwd"][:28], k["bwd"][:28]))
