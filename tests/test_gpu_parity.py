@@ -138,6 +138,13 @@ CASES = {
     "2d_shifted_tanh_100x3_pads_to_128": (dict(layers=[2, 100, 100, 100, 1], activation=1, gamma=50.0, dx=0.01), 300, True),
     "2d_complex_72x3_pads_to_128": (dict(layers=[2, 72, 72, 72, 2], complex_psi=True, gamma=30.0, omega_rot=0.8, dx=0.02), 200, True),
     "1d_single_hidden": (dict(layers=[1, 64, 1], gamma=1.0, dx=0.01, base_mode=1), 50, False),
+    # the symmetry batch (x -> [x ; -x], value only: the (1, 0) instances of the reverse kernels, as the pre-training step runs them) beyond
+    # 1D plain MLPs at H <= 64: five maps in 2D, H = 128, residual blocks
+    "2d_32x6_five_maps_w_sym": (dict(layers=[2, 32, 32, 32, 32, 32, 32, 1], gamma=10.0, dx=0.01, w_sym=5.0), 401, True),
+    "2d_128x3_w_sym": (dict(layers=[2, 128, 128, 128, 1], gamma=100.0, dx=0.01, w_sym=5.0), 300, True),
+    "1d_residual_64x2blocks_w_sym": (dict(layers=[1, 64, 64, 64, 1], net_kind=go.NET_RESIDUAL, activation=1, kinetic_coeff=1.0,
+                                          potential=go.POT_GAUSSIAN, pot_a=0.5, gamma=3.0, p=4, base_mode=1, perturb_scale=0.05, w_sym=5.0,
+                                          sym_sign=-1.0, dx=0.03), 333, True),
 }
 
 
