@@ -213,6 +213,7 @@ def test_step_matches_oracle(name, path):
     assert abs(rs["loss"] - osc["loss"]) <= f * 1e-4 * abs(osc["loss"])
     grad = eng.get_grad()
     assert H.rel_err(grad, ograd) < f * 5e-5
+    assert not H.block_failures(grad, ograd, pb.layers, pb.net_kind, f)         # ... and per weight matrix / bias, of the block's own maximum
     assert abs(sc["grad_norm"] - np.linalg.norm(ograd)) < f * 1e-4 * np.linalg.norm(ograd)
     # Adam + clip on the device vs the oracle's optimiser (first step moves every weight by ~lr)
     new, _, _ = go.optimizer_step(go.OptState(lr0=1e-3), flat, ograd, osc["loss"])

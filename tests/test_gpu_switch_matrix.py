@@ -191,8 +191,9 @@ def run_cell(name, N, env, multi=False, dp=False):
     return out
 
 
-def check_oracle(cell, o, multi):
-    """failures of one cell against the fp64 oracle (tolerances of test_step_matches_oracle)"""
+def check_oracle(cell, o, multi, name):
+    """failures of one cell of class `name` against the fp64 oracle (tolerances of test_step_matches_oracle, and the gradient per
+    parameter block)"""
     bad = []
     osc = o["sc"]
     for c in range(cell["jets"].shape[0]):
@@ -212,6 +213,8 @@ def check_oracle(cell, o, multi):
     eg = Hl.rel_err(cell["grad"], o["grad"])
     if not eg < 5e-5:
         bad.append(f"gradient rel err {eg:.3e}")
+    kw = CLASSES[name][0]
+    bad += Hl.block_failures(cell["grad"], o["grad"], kw["layers"], kw.get("net_kind", go.NET_MLP))
     d = np.abs(cell["params"] - o["new"])
     if not (np.quantile(d, 0.99) < 2e-5 and d.max() < 2.1e-3):
         bad.append(f"parameters after Adam: q99 {np.quantile(d, 0.99):.3e} max {d.max():.3e}")
@@ -275,7 +278,7 @@ def test_switch_against_the_oracle(switch):
             SEEN.setdefault(switch, []).append(dict(cls=name, N=N, env=env, kernels=kstr(cell["kern"]), default=kstr(ref["kern"])))
             if cell["kern"] != ref["kern"] or cell["path"] != ref["path"]:
                 differs.append(tag)
-            fails += [f"{tag} {m}" for m in check_oracle(cell, oracle(name, N, traj=multi), multi)]
+            fails += [f"{tag} {m}" for m in check_oracle(cell, oracle(name, N, traj=multi), multi, name)]
             if expect == "bitwise":
                 fails += [f"{tag} {m}" for m in check_bitwise(cell, ref, multi)]
     assert cells > 0, f"{switch}: applies to no class of the matrix"
@@ -315,7 +318,7 @@ def test_residual_networks_keep_the_cooperative_kernels_with_gpe_coop_0(name):
     N, _, _ = CLASSES[name][1][0]
     cell = run_cell(name, N, {"GPE_COOP": "0"})
     k = cell["kern"]
-    bad = check_oracle(cell, oracle(name, N), False)
+    bad = check_oracle(cell, oracle(name, N), False, name)
     if not (cell["path"] == gpe_pinn.PATH_FUSED and k["fwd"].startswith("f_forward_coop<") and k["bwd"].startswith("f_backward_coop<")):
         bad.append("not the cooperative residual kernels")
     assert not bad, f"{name} GPE_COOP=0 {kstr(k)}: " + "; ".join(bad)
