@@ -35,6 +35,7 @@ typedef enum { ncclFloat = 7, ncclDouble = 8 } ncclDataType_t;
 #include "gpe_generic.h"
 #include "gpe_fused.h"
 #include "gpe_wide_api.h"
+#include "gpe_env.h"
 
 static thread_local std::string g_create_error;
 
@@ -774,7 +775,7 @@ static int setup_batch(gpe_engine* e, Batch& b, const float* x, int64_t n, int C
 #endif
 
 static size_t fused_w_bytes(gpe_engine* e) { return (size_t)(e->nd.n_lin - 2) * e->H * e->H * sizeof(float); }
-static size_t fused_small_bytes(gpe_engine* e) {       // = small_count() of gpe_fused.h, rounded up to 16 bytes
+static size_t fused_small_bytes(gpe_engine* e) {       // = small_count() of gpe_fused.h, rounded up to 16 bytes (NOT read_switches' smallb, on purpose)
     size_t n = (size_t)(4 + (e->nd.n_lin - 2) + e->nd.n_out) * e->H + 4;
     return ((n + 3) & ~(size_t)3) * sizeof(float);
 }
@@ -979,16 +980,13 @@ static size_t coop_lds(gpe_engine* e, int C) {
     const size_t zb = e->bwd_b6 && H <= 64 ? (size_t)3 * C * (NT / 2) * 256 : (size_t)C * NT * 256;     // B6: three bf16 pieces, 24 B per four values
     return (n_gsm + 4 * (size_t)H) * sizeof(float) + fused_small_bytes(e) + (zb + 2 * (size_t)C * NT * F_TILE) * sizeof(float);
 }
+#define LDS_ATTR(BYTES, ...) (void)hipFuncSetAttribute((const void*)__VA_ARGS__, hipFuncAttributeMaxDynamicSharedMemorySize, BYTES)
 template <int HH, int CC, int EE, int NO>
 static void set_pipe_lds(int bytes) {
     if constexpr (!(HH == 64 && CC == 5)) {
-        (void)hipFuncSetAttribute((const void*)f_backward_pipe<HH, CC, EE, NO, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        (void)hipFuncSetAttribute((const void*)f_backward_pipe<HH, CC, EE, NO, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        (void)hipFuncSetAttribute((const void*)f_backward_pipe<HH, CC, EE, NO, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+        LDS_ATTR(bytes, f_backward_pipe<HH, CC, EE, NO, 1>); LDS_ATTR(bytes, f_backward_pipe<HH, CC, EE, NO, 2>); LDS_ATTR(bytes, f_backward_pipe<HH, CC, EE, NO, 3>);
         if constexpr (NO == 1 && CC >= 3) {
-            (void)hipFuncSetAttribute((const void*)f_backward_pipe<HH, CC, EE, 1, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-            (void)hipFuncSetAttribute((const void*)f_backward_pipe<HH, CC, EE, 1, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-            (void)hipFuncSetAttribute((const void*)f_backward_pipe<HH, CC, EE, 1, 3, true>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+            LDS_ATTR(bytes, f_backward_pipe<HH, CC, EE, 1, 1, true>); LDS_ATTR(bytes, f_backward_pipe<HH, CC, EE, 1, 2, true>); LDS_ATTR(bytes, f_backward_pipe<HH, CC, EE, 1, 3, true>);
         }
     }
 }
@@ -1448,6 +1446,305 @@ static int reset_opt(gpe_engine* e, float lr) {
     return GPE_OK;
 }
 
+// ---- engine creation, phase by phase (gpe_create calls each once, in this order) -------------------------------------------------------
+// check_config, pad_widths, describe_net and select_path work on the configuration alone: no HIP call, so every refusal comes before the
+// device is touched.  The first rule that fails is the one the caller sees.
+#define CFAIL(...) do { char _b[512]; snprintf(_b, sizeof _b, __VA_ARGS__); e->err = _b; return GPE_ERR_INVALID; } while (0)
+// 1. every refusal that needs the configuration only
+static int check_config(gpe_engine* e, const gpe_config& in) {
+    if (in.abi_version != GPE_ABI_VERSION) CFAIL("abi_version %d != %d", in.abi_version, GPE_ABI_VERSION);
+    const gpe_config& c = e->cfg = in;
+    if (c.n_layers < 3 || c.n_layers > GPE_MAX_LAYERS) CFAIL("n_layers must be in [3,%d]", GPE_MAX_LAYERS);
+    const int dim = c.layers[0], no = c.layers[c.n_layers - 1];
+    if (dim < 1 || dim > GPE_MAX_DIM) CFAIL("dim must be 1..3");
+    if (no < 1 || no > 2) CFAIL("output width must be 1 or 2");
+    if (c.complex_psi && (no != 2 || c.p != 3)) CFAIL("complex psi needs out=2 and p=3");
+    if (!c.complex_psi && no != 1) CFAIL("real psi needs out=1");
+    if (c.potential < 0 || c.potential > GPE_POT_NONE) CFAIL("Unknown potential type: %d", c.potential);
+    if (c.base_mode >= 0 && (dim != 1 || no != 1)) CFAIL("Hermite base needs dim=1, out=1");
+    if (c.p < 1 || c.p > 32) CFAIL("power p must be in [1,32]");
+    if (c.omega_rot != 0.f && (!c.complex_psi || dim < 2)) CFAIL("rotation needs complex psi and dim>=2");
+    if (c.base_kind < 0 || c.base_kind > GPE_BASE_PRECOMPUTED) CFAIL("Unknown base kind: %d", c.base_kind);
+    if (c.envelope < 0 || c.envelope > GPE_ENV_SIN) CFAIL("Unknown envelope: %d", c.envelope);
+    if (c.envelope != GPE_ENV_NONE && (dim != 1 || no != 1)) CFAIL("the boundary factor needs dim=1, out=1");
+    if (c.w_riesz != 0.f && no != 1 && !(c.complex_psi && no == 2 && c.p == 3))
+        CFAIL("the Riesz energy term needs real psi (out=1) or complex psi (out=2) with p = 3");
+    if (c.riesz_kind < 0 || c.riesz_kind > GPE_RIESZ_VARIATIONAL) CFAIL("Unknown Riesz kind: %d", c.riesz_kind);
+    if (c.lambda_kind != GPE_LAMBDA_RAYLEIGH && c.lambda_kind != GPE_LAMBDA_ENERGY) CFAIL("Unknown lambda kind: %d", c.lambda_kind);
+    if (c.lambda_kind == GPE_LAMBDA_ENERGY && (c.complex_psi || no != 1 || (c.p & 1) == 0))
+        CFAIL("the energy-functional lambda needs real psi (out=1) and an odd power p");
+    if (c.w_reg_lam != 0.f && c.lambda_kind != GPE_LAMBDA_ENERGY) CFAIL("the 1/lambda^2 regulariser needs the energy-functional lambda");
+    if ((c.w_reg_f != 0.f || c.w_reg_lam != 0.f) && (c.complex_psi || no != 1)) CFAIL("the regularisers need real psi (out=1)");
+    if ((c.w_reg_f != 0.f && !(c.reg_f_eps > 0.f)) || (c.w_reg_lam != 0.f && !(c.reg_lam_eps > 0.f))) CFAIL("regulariser eps must be > 0");
+    for (int i = 1; i < c.n_layers - 1; ++i)
+        if (c.layers[i] < 1 || c.layers[i] > 1024) CFAIL("hidden width %d out of range", c.layers[i]);
+    return GPE_OK;
+}
+
+// the whole-network kernels at H <= 64 keep all parameters (padded to 64) in LDS: the one rule pad_widths picks a width by and select_path
+// admits a network to the fused set by
+static bool fused_lds_fits(size_t Ppad, int n_lin, int H, int dim) {
+    return (Ppad + (size_t)(8 + n_lin + 3) * H + 8 + 4 * (dim + 2) * F_TILE) * sizeof(float) <= 160 * 1024;
+}
+
+// 2. Width padding.  The MFMA kernel sets are instantiated for one hidden width of 32, 64, 128 or 256; other plain-tanh MLPs of width <= 256 --
+// the 2D scripts' own [2,100,100,100,1] (src/gross_pitaevskii_2D_minimal.py:377), ragged widths -- are run as the next such width with
+// zero rows / columns / biases in the padding.  A padded unit sees z = 0, gives tanh(0) = 0 with all jets 0, feeds zero outgoing weights
+// and so receives the gradient 0 exactly on every one of its weights: Adam leaves them at 0 and the network stays the caller's.
+// ShiftedTanh (tanh + 1) would give 1 there: its padded units get the bias -40 instead of 0 -- tanh(-40) = -1 exactly in fp32 (exp(-80) + 1 = 1),
+// so the unit outputs exactly 0 with slope 1 - t^2 = 0, every gradient that touches it is 0 again, and the bias itself stays where it is.
+// GPE_PAD_WIDTH=0 or GPE_PATH_GENERIC: as given.  Fills user_layers, and for a padded network umap, pad_bias, P_user and the padded cfg.layers.
+static void pad_widths(gpe_engine* e) {
+    const gpe_config& c = e->cfg;
+    const int dim = c.layers[0], no = c.layers[c.n_layers - 1];
+    for (int i = 0; i < c.n_layers; ++i) e->user_layers[i] = c.layers[i];
+    int wmax = 0; bool uni = true;
+    for (int i = 1; i < c.n_layers - 1; ++i) { wmax = std::max(wmax, c.layers[i]); uni = uni && c.layers[i] == c.layers[1]; }
+    const bool native = uni && (wmax == 32 || wmax == 64 || wmax == 128 || wmax == 256);
+    // (widths above 256 -- train_pinn's default [2,400,400,400,1], src/gross_pitaevskii_2D_minimal.py:278 -- have no whole-network kernel: they are
+    // padded to the next multiple of 256 so that the GENERIC set runs every hidden map on its 128 x 128-tile MFMA kernels instead of the VALU ones)
+    const bool big = wmax > 256 && wmax <= 1024 && !(uni && wmax % 256 == 0);
+    if (!(env_on("GPE_PAD_WIDTH") && (big || (!native && wmax <= 256)) && c.path != GPE_PATH_GENERIC && c.net_kind == GPE_NET_MLP &&
+          (c.activation == GPE_ACT_TANH || c.activation == GPE_ACT_TANH_PLUS1) && c.n_layers - 2 >= 2))
+        return;
+    // the smallest instantiated width that holds the widest layer and whose kernels take this depth (32 / 64: all weights in LDS)
+    int Hp = big ? (int)round_up(wmax, 256) : 0;
+    if (!big)
+    for (int h : {32, 64, 128, 256}) {
+        if (h < wmax) continue;
+        if (h <= 64) {
+            const int Lm = c.n_layers - 3;                        // hidden -> hidden maps
+            const size_t pp = round_up((size_t)dim * h + h + (size_t)Lm * (h * h + h) + (size_t)h * no + no, 64);
+            if (!fused_lds_fits(pp, c.n_layers - 1, h, dim)) continue;
+        }
+        Hp = h; break;
+    }
+    int pl[GPE_MAX_LAYERS];
+    for (int i = 0; i < c.n_layers; ++i) pl[i] = (i == 0 || i == c.n_layers - 1) ? c.layers[i] : Hp;
+    int offp = 0;
+    for (int j = 0; j + 1 < c.n_layers; ++j) {
+        const int iu = c.layers[j], ou = c.layers[j + 1], ip = pl[j], op = pl[j + 1];
+        for (int o = 0; o < ou; ++o) for (int i = 0; i < iu; ++i) e->umap.push_back(offp + o * ip + i);
+        offp += ip * op;
+        for (int o = 0; o < ou; ++o) e->umap.push_back(offp + o);
+        if (c.activation == GPE_ACT_TANH_PLUS1 && j + 2 < c.n_layers) for (int o = ou; o < op; ++o) e->pad_bias.push_back(offp + o);
+        offp += op;
+    }
+    e->P_user = (int)e->umap.size();
+    for (int i = 1; i < c.n_layers - 1; ++i) e->cfg.layers[i] = Hp;
+}
+
+// 3. the network as the kernels see it: NetDesc, P, Ppad (and P_user of a network that runs as given)
+static int describe_net(gpe_engine* e) {
+    const gpe_config& c = e->cfg;
+    const int dim = c.layers[0], no = c.layers[c.n_layers - 1];
+    NetDesc& nd = e->nd;
+    memset(&nd, 0, sizeof nd);
+    nd.dim = dim; nd.n_out = no; nd.shift = c.activation == GPE_ACT_TANH_PLUS1 ? 1.f : 0.f;
+    if (c.net_kind != GPE_NET_MLP && c.net_kind != GPE_NET_RESIDUAL) CFAIL("Unknown network kind: %d", c.net_kind);
+    for (int j = 0; j < GPE_MAX_LAYERS; ++j) { nd.skip[j] = -1; nd.shiftv[j] = nd.shift; }
+    if (c.net_kind == GPE_NET_RESIDUAL) {      // refine/box_to_gaussian_pinn_simulation.py:100-130
+        const int nb = c.n_layers - 3;
+        if (nb < 1 || 2 * nb + 3 > GPE_MAX_LAYERS) CFAIL("residual network: 1..%d blocks", (GPE_MAX_LAYERS - 3) / 2);
+        for (int i = 2; i < c.n_layers - 1; ++i) if (c.layers[i] != c.layers[1]) CFAIL("residual network: one hidden width");
+        nd.n_lin = 2 * nb + 2;
+        nd.width[0] = dim;
+        for (int i = 1; i <= 2 * nb + 1; ++i) nd.width[i] = c.layers[1];
+        nd.width[nd.n_lin] = no;
+        for (int bq = 0; bq < nb; ++bq) nd.skip[2 * bq + 2] = 2 * bq;     // lin2 of block bq adds hidden layer 2 bq (the block input)
+        for (int h = 1; h < nd.n_lin - 1; ++h) nd.shiftv[h] = 0.f;        // plain tanh inside the blocks; the first layer keeps `activation`
+    } else {
+        nd.n_lin = c.n_layers - 1;
+        for (int i = 0; i < c.n_layers; ++i) nd.width[i] = c.layers[i];
+    }
+    int off = 0;
+    for (int j = 0; j < nd.n_lin; ++j) {
+        nd.offW[j] = off; off += nd.width[j] * nd.width[j + 1];
+        nd.offB[j] = off; off += nd.width[j + 1];
+    }
+    nd.n_params = off;
+    e->P = off;
+    if (e->umap.empty()) e->P_user = off;
+    e->Ppad = (int)round_up(off, 64);
+    return GPE_OK;
+}
+
+// 4. path and kernel set: path, H, wide, wide_fwd (and fwd_wg_per_cu, refused here when this build cannot honour it).
+// The fused kernels need >= 2 hidden layers of one width H.  All of this is FIXED before read_switches parses GPE_COOP and the rest: a
+// residual network admitted to the fused set here has only the cooperative <..., RES> kernels, and GPE_COOP=0 cannot take that back.
+// Hence coop_only(): fwd_coop() / bwd_kind() ask it before they look at e->coop (such a network once ran the plain-MLP kernels: a silently wrong loss).
+static int select_path(gpe_engine* e) {
+    const gpe_config& c = e->cfg;
+    const NetDesc& nd = e->nd;
+    const int dim = nd.dim, no = nd.n_out, H = c.layers[1];
+    bool uniform = true;
+    for (int i = 2; i < c.n_layers - 1; ++i) uniform = uniform && (c.layers[i] == c.layers[1]);
+    const int Lh = nd.n_lin - 1;                                                 // hidden layers (an MLP's n_layers - 2; a residual network's 2 blocks + 1)
+    // residual blocks (refine/box_to_gaussian_pinn_simulation.py): round 4 -- one or two blocks of width 32 / 64, real psi, on the cooperative
+    // whole-network kernels (f_forward_coop / f_backward_coop <..., RES>); everything else on the generic set
+    const bool residual = c.net_kind == GPE_NET_RESIDUAL;
+    if (residual && !((H == 32 || H == 64) && no == 1 && (nd.n_lin - 2 == 2 || nd.n_lin - 2 == 4))) uniform = false;
+    if (residual && !env_on("GPE_RES_FUSED")) uniform = false;
+    bool fused_ok = uniform && (H == 32 || H == 64) && Lh >= 2 && fused_lds_fits((size_t)e->Ppad, nd.n_lin, H, dim);
+    if (residual && (H == 128 || H == 256)) uniform = false;                    // (no residual form of the 8-wave kernels)
+    if (uniform && H == 128 && Lh >= 2 && dim <= 2) fused_ok = true;          // cooperative kernels, weights streamed from L2
+    // wide kernel set: H = 256 and 3D H = 128 entirely; 1D/2D H = 128: its per-map reverse kernels (no register spills, -5..7 % against
+    // f_backward_coop<128>) behind the cooperative forward kernel (7 % faster than w_forward there) -- same stored-activation format.
+    // GPE_WIDE=1: forward too; GPE_WIDE=0: cooperative kernels only (1D/2D)
+    const int wmode = env_int("GPE_WIDE", -1);
+    if (uniform && Lh >= 2 && (H == 256 || (H == 128 && dim == 3))) { fused_ok = true; e->wide = true; e->wide_fwd = true; }
+    else if (uniform && Lh >= 2 && H == 128 && wmode != 0) { fused_ok = true; e->wide = true; e->wide_fwd = wmode == 1; }
+    if (c.path == GPE_PATH_FUSED && !fused_ok)
+        CFAIL("fused path needs >=2 hidden layers of one width: 32 or 64 (P*4 <= 160KB LDS), 128 or 256");
+    e->path = (c.path == GPE_PATH_GENERIC || !fused_ok) ? GPE_PATH_GENERIC : GPE_PATH_FUSED;
+    e->H = H;
+    if (e->path == GPE_PATH_FUSED) {
+        // f_forward is compiled for GPE_FWD_WAVES resident workgroups per CU (__launch_bounds__): more cannot be honoured by this build
+        e->fwd_wg_per_cu = env_int("GPE_FWD_WG_PER_CU", e->fwd_wg_per_cu);
+        if (e->fwd_wg_per_cu < 1 || e->fwd_wg_per_cu > GPE_FWD_WAVES)
+            CFAIL("GPE_FWD_WG_PER_CU=%d: this build runs f_forward at 1..%d workgroups per CU (more need a build with -DGPE_FWD_WAVES raised to match)",
+                  e->fwd_wg_per_cu, GPE_FWD_WAVES);
+    }
+    return GPE_OK;
+}
+#undef CFAIL
+
+// the device and the stream: the first HIP call of creation
+static int open_device(gpe_engine* e, int device, void* hip_stream) {
+    e->device = device; e->stream = (hipStream_t)hip_stream;
+    hipError_t st = hipSetDevice(device);
+    if (st != hipSuccess) { e->err = std::string("hipSetDevice: ") + hipGetErrorString(st); return GPE_ERR_HIP; }
+    if (hipDeviceProp_t prop; hipGetDeviceProperties(&prop, device) == hipSuccess) e->num_cu = prop.multiProcessorCount;
+    return GPE_OK;
+}
+
+struct AllocSwitches { bool update_multi = true, side_stream = true; };     // switches that only decide what alloc_state allocates
+
+// 5. every remaining GPE_* switch; allocates nothing.  What select_path fixed is not reopened here (see there).
+static void read_switches(gpe_engine* e, AllocSwitches& sw) {
+    const int H = e->H, Lh = e->nd.n_lin - 1, no = e->nd.n_out;
+    // GPE_UPDATE_MULTI=0: the single-workgroup update at every size; GPE_UPDATE_MULTI_MIN (tests): the multi-workgroup form from this many parameters on
+    sw.update_multi = e->P >= env_int("GPE_UPDATE_MULTI_MIN", UPD_MULTI_MIN) && env_on("GPE_UPDATE_MULTI");
+    e->update_cache = env_on("GPE_UPDATE_CACHE");
+    e->fuse_seed = env_on("GPE_FUSE_SEED"); e->fuse_seed_max = env_i64("GPE_FUSE_SEED_MAX", e->fuse_seed_max);
+    e->pipe_share = env_int("GPE_PIPE_SHARE", e->pipe_share);
+    e->share_min_tiles = env_int_in("GPE_SHARE_MIN_TILES", e->share_min_tiles, 1, INT32_MAX);
+    e->fwd_share = env_int("GPE_FWD_SHARE", e->fwd_share);
+    e->fuse_head = env_on("GPE_FUSE_HEAD");
+    e->fuse_head_tile_min = env_i64("GPE_FUSE_HEAD_TILE_MIN", e->fuse_head_tile_min); e->fuse_head_max = env_i64("GPE_FUSE_HEAD_MAX", e->fuse_head_max);
+    // opt-in: measured 1 us SLOWER than the two launches at 2 048 .. 65 536 points (profiles/r04/small_batch.txt) -- 200 workgroups'
+    // tickets on one address (~12 ns apiece) and the write-through hand-off cost what the saved launch gives
+    e->fuse_update = env_opt_in("GPE_FUSE_UPDATE");
+    // opt-in as well: measured EQUAL to the single-workgroup update (35.8 vs 35.7 us at 2 048 points, 41.4 vs 41.0 at 4 000,
+    // profiles/r04/small_batch.txt) -- at these sizes a dependent launch costs ~4 us whatever it runs, and the update's own chain is short
+    e->split_update = env_opt_in("GPE_SPLIT_UPDATE");
+    if (e->path == GPE_PATH_FUSED) {
+        e->wide_min_tiles = env_i64_in("GPE_WIDE_MIN_TILES", e->wide_min_tiles, 0, INT64_MAX);
+        const int Cmain = e->nd.dim + 2;        // training batches: value, dim first derivatives, Laplacian
+        const size_t wb = (size_t)(Lh - 1) * H * H * sizeof(float);
+        // (smallb, and the bwd_racc bound that adds it to the kernel's own operands, differ from fused_small_bytes() by a few bytes on purpose)
+        const size_t smallb = ((size_t)(4 + (Lh - 1) + no) * H + 8) * sizeof(float);
+        e->fwd_wlds = env_on("GPE_WLDS") && H <= 64 && wb + smallb <= 64 * 1024;          // 0 = weights from L2, 1 = from LDS
+        e->fwd_b6 = env_opt_in("GPE_FWD_B6") && H <= 64;                 // 1: f_forward_b6 for the large-batch forward pass at H <= 64
+        e->bwd_b6 = env_opt_in("GPE_BWD_B6") && H <= 64 && H >= 32;      // 1: the cooperative reverse kernel's adjoint products on the bf16 pipe
+        e->bwd_pipe = env_on("GPE_PIPE");                                // 0: the two-barrier cooperative reverse kernel (f_backward_coop) at H <= 64
+        e->coop_wg_per_cu = env_int_in("GPE_COOP_WG_PER_CU", e->coop_wg_per_cu, 1, 2);
+        e->coop = env_int("GPE_COOP", 1); e->coop_max_tiles = env_i64("GPE_COOP_MAX_TILES", 0);   // (on: measured faster than the per-wave-tile kernels at every batch size)
+        e->coop128 = env_on("GPE_COOP128"); e->coop_fwd128 = env_on("GPE_COOP_FWD128");
+        e->coop_fwd_max_tiles = env_i64("GPE_COOP_FWD_MAX_TILES", (int64_t)e->num_cu * 8);   // measured: wins below ~32 768 points, loses 8 % at 1M
+        e->stage_min_tiles = env_i64("GPE_STAGE_MIN_TILES", 0);          // batches with fewer tiles take the unstaged per-wave-tile kernels
+        e->bwd_racc = env_on("GPE_RACC") && H <= 64 && (Lh - 1) >= 1 && (Lh - 1) <= 3 &&
+                      ((size_t)e->Ppad + 4 * (size_t)H + 4 * (size_t)Cmain * F_TILE) * sizeof(float) + smallb + wb <= 160 * 1024;
+    }
+    e->gen_mfma = env_on("GPE_GEN_MFMA"); e->gen_mfma2 = env_on("GPE_GEN_MFMA2");
+    e->gen_min_chunk = (env_i64_in("GPE_GEN_MIN_CHUNK", e->gen_min_chunk, 16, INT64_MAX) + 15) / 16 * 16;
+    e->head_wg_per_cu = env_int_in("GPE_HEAD_WG_PER_CU", e->head_wg_per_cu, 1, INT32_MAX);
+    if (const int ht = env_int("GPE_HEAD_THREADS", e->head_threads); ht == 256 || ht == 512 || ht == 1024) e->head_threads = ht;
+    e->merge_bc = env_on("GPE_MERGE_BC");
+    // gpe_run replays captured graphs of graph_steps steps each.  Round 4: ONE graph launch per 8 steps takes the host from 31 to
+    // 3 us per step at 2 048 points with the step time unchanged (35.5 us: the GPU is the bound); a one-step graph is slower (44.8 us).
+    // Default: on for batches up to graph_max_points (where the host thread was ~90 % busy enqueueing); GPE_GRAPH=0 / 1 forces it
+    e->use_graph = env_on("GPE_GRAPH"); e->graph_forced = env_set("GPE_GRAPH");
+    e->graph_steps = env_int_in("GPE_GRAPH_STEPS", e->graph_steps, 1, 64);
+    sw.side_stream = env_on("GPE_SIDE_STREAM");
+}
+
+// 6. every device allocation of creation, the side stream and its events
+static int alloc_state(gpe_engine* e, const AllocSwitches& sw) {
+    const int H = e->H, Lh = e->nd.n_lin - 1;
+    e->cap = e->cfg.history_capacity > 0 ? e->cfg.history_capacity : 65536;
+    auto alloc = [&](void** p, size_t bytes) -> bool {
+        hipError_t s2 = hipMalloc(p, bytes + 256);
+        if (s2 != hipSuccess) { e->err = std::string("hipMalloc: ") + hipGetErrorString(s2); return false; }
+        (void)hipMemset(*p, 0, bytes + 256);
+        return true;
+    };
+    bool ok = alloc((void**)&e->theta, (size_t)e->P * 4) && alloc((void**)&e->am, (size_t)e->P * 4) &&
+              alloc((void**)&e->av, (size_t)e->P * 4) && alloc((void**)&e->grad, ((size_t)e->P + GT_COUNT) * 4) &&
+              alloc((void**)&e->dbl, (S_COUNT + LS_COUNT + 4) * sizeof(double)) && alloc((void**)&e->od, sizeof(OptDev)) &&
+              alloc((void**)&e->hist, (size_t)e->cap * sizeof(gpe_scalars)) && alloc((void**)&e->last, sizeof(gpe_scalars)) &&
+              alloc((void**)&e->orth_dev, 8 * sizeof(float*));
+    if (ok && sw.update_multi) ok = alloc((void**)&e->upd_snap, sizeof(UpdSnap));
+    if (ok && e->fuse_head) ok = alloc((void**)&e->head_slots, (size_t)HEAD_SLOTS * 4 * sizeof(double));
+    if (ok && e->fuse_update) ok = alloc((void**)&e->upd_ticket, 64);
+    if (ok && e->split_update && !e->upd_snap && upd_chunk_host(e->P) <= 1024) ok = alloc((void**)&e->upd_snap_small, sizeof(UpdSnap));
+    if (ok && e->path == GPE_PATH_FUSED) {
+        e->nslab = (H >= 128) ? std::max(e->nslab_g, e->num_cu) : e->num_cu * 2;     // H = 128: 16 atomic slabs, or one per workgroup (cooperative)
+        // WpkT is followed by the bf16 pieces of the same maps (3 x 2 bytes per weight; pack_weight_element, f_forward_b6)
+        ok = alloc((void**)&e->Wpk, (size_t)(Lh - 1) * H * H * 4) && alloc((void**)&e->WpkT, (size_t)(Lh - 1) * H * H * (4 + 6 + 6)) &&
+             alloc((void**)&e->gslab, (size_t)e->nslab * e->Ppad * 4);
+    }
+    if (ok) ok = alloc((void**)&e->grad_bc, (size_t)e->P * 4);
+    if (ok && e->path == GPE_PATH_FUSED) ok = alloc((void**)&e->gslab_bc, (size_t)e->nslab * e->Ppad * 4);
+    if (!ok) return GPE_ERR_NOMEM;
+    if (sw.side_stream && (hipStreamCreateWithFlags(&e->side, hipStreamNonBlocking) != hipSuccess ||
+                           hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming) != hipSuccess ||
+                           hipEventCreateWithFlags(&e->ev_join, hipEventDisableTiming) != hipSuccess)) {
+        e->err = "side stream / events could not be created";
+        return GPE_ERR_HIP;
+    }
+    return GPE_OK;
+}
+
+// 7. the kernels that take more dynamic LDS than the 64 KB a launch gets by default
+static void raise_lds_limits(gpe_engine* e) {
+    if (e->path == GPE_PATH_FUSED) {
+        if (e->wide) wide_init();
+        const int lds_b = 160 * 1024, lds_f = 64 * 1024;
+#define SETLDS(HH, CC, EE, NO)                                                                                                                      \
+    LDS_ATTR(lds_b, f_backward<HH, CC, EE, NO, false, 0>); LDS_ATTR(lds_b, f_backward<HH, CC, EE, NO, true, 1>);                                    \
+    LDS_ATTR(lds_b, f_backward<HH, CC, EE, NO, true, 2>); LDS_ATTR(lds_b, f_backward<HH, CC, EE, NO, true, 3>);                                     \
+    LDS_ATTR(lds_b, f_backward_coop<HH, CC, EE, NO, 1>); LDS_ATTR(lds_b, f_backward_coop<HH, CC, EE, NO, 2>); LDS_ATTR(lds_b, f_backward_coop<HH, CC, EE, NO, 3>); \
+    if constexpr (NO == 1) {                                                                                                                        \
+        LDS_ATTR(lds_b, f_backward_coop<HH, CC, EE, 1, 2, false, true>); LDS_ATTR(lds_b, f_backward_coop<HH, CC, EE, 1, 4, false, true>);           \
+        LDS_ATTR(lds_b, f_backward_coop<HH, CC, EE, 1, 4>); LDS_ATTR(lds_b, f_backward_coop<HH, CC, EE, 1, 5>); }                                   \
+    set_pipe_lds<HH, CC, EE, NO>(lds_b);                                                                                                            \
+    LDS_ATTR(lds_b, f_backward_coop<HH, CC, EE, NO, 1, true>); LDS_ATTR(lds_b, f_backward_coop<HH, CC, EE, NO, 2, true>); LDS_ATTR(lds_b, f_backward_coop<HH, CC, EE, NO, 3, true>); \
+    LDS_ATTR(lds_f, f_forward<HH, CC, EE, NO, true>); LDS_ATTR(80 * 1024, f_forward_b6<HH, CC, EE, NO, true>)
+#ifdef GPE_FAST_BUILD
+        SETLDS(64, 1, 0, 1); SETLDS(64, 4, 1, 1);
+#else
+        SETLDS(64, 1, 0, 1); SETLDS(64, 3, 1, 1); SETLDS(64, 4, 1, 1); SETLDS(64, 5, 1, 1);
+        SETLDS(64, 1, 0, 2); SETLDS(64, 3, 1, 2); SETLDS(64, 4, 1, 2); SETLDS(64, 5, 1, 2);
+        SETLDS(32, 1, 0, 1); SETLDS(32, 3, 1, 1); SETLDS(32, 4, 1, 1); SETLDS(32, 5, 1, 1);
+        SETLDS(32, 1, 0, 2); SETLDS(32, 3, 1, 2); SETLDS(32, 4, 1, 2); SETLDS(32, 5, 1, 2);
+#define SETLDS128(CC, EE, NO)                                                                                                                       \
+    LDS_ATTR(lds_b, f_backward_coop<128, CC, EE, NO, 1>); LDS_ATTR(lds_b, f_backward_coop<128, CC, EE, NO, 2>); LDS_ATTR(lds_b, f_backward_coop<128, CC, EE, NO, 3>); \
+    LDS_ATTR(lds_b, f_backward_coop<128, CC, EE, NO, 4>); LDS_ATTR(lds_b, f_backward_coop<128, CC, EE, NO, 5>);                                     \
+    LDS_ATTR(lds_b, f_forward_coop<128, CC, EE, NO, 1>); LDS_ATTR(lds_b, f_forward_coop<128, CC, EE, NO, 2>); LDS_ATTR(lds_b, f_forward_coop<128, CC, EE, NO, 3>); \
+    LDS_ATTR(lds_b, f_forward_coop<128, CC, EE, NO, 4>); LDS_ATTR(lds_b, f_forward_coop<128, CC, EE, NO, 5>);                                       \
+    LDS_ATTR(lds_b, f_backward<128, CC, EE, NO, false, 0>)
+        SETLDS128(1, 0, 1); SETLDS128(3, 1, 1); SETLDS128(4, 1, 1); SETLDS128(1, 0, 2); SETLDS128(3, 1, 2); SETLDS128(4, 1, 2);
+#undef SETLDS128
+#endif
+#undef SETLDS
+    }
+    LDS_ATTR(160 * 1024, g_bwd_weight_mfma2<1, 0>); LDS_ATTR(160 * 1024, g_bwd_weight_mfma2<4, 1>);
+#ifndef GPE_FAST_BUILD
+    LDS_ATTR(160 * 1024, g_bwd_weight_mfma2<3, 1>); LDS_ATTR(160 * 1024, g_bwd_weight_mfma2<5, 1>);
+#endif
+}
+
 extern "C" {
 
 int gpe_abi_version(void) { return GPE_ABI_VERSION; }
@@ -1534,332 +1831,17 @@ int gpe_create(const gpe_config* cfg, int device, void* hip_stream, gpe_engine**
     if (!cfg || !out) { g_create_error = "null argument"; return GPE_ERR_INVALID; }
     *out = nullptr;
     gpe_engine* e = new gpe_engine();
-    auto bail = [&](int code) { g_create_error = e->err; delete e; return code; };
-#define CFAIL(...) do { char _b[512]; snprintf(_b, sizeof _b, __VA_ARGS__); e->err = _b; return bail(GPE_ERR_INVALID); } while (0)
-    if (cfg->abi_version != GPE_ABI_VERSION) CFAIL("abi_version %d != %d", cfg->abi_version, GPE_ABI_VERSION);
-    e->cfg = *cfg;
-    const gpe_config& c = e->cfg;
-    if (c.n_layers < 3 || c.n_layers > GPE_MAX_LAYERS) CFAIL("n_layers must be in [3,%d]", GPE_MAX_LAYERS);
-    const int dim = c.layers[0], no = c.layers[c.n_layers - 1];
-    if (dim < 1 || dim > GPE_MAX_DIM) CFAIL("dim must be 1..3");
-    if (no < 1 || no > 2) CFAIL("output width must be 1 or 2");
-    if (c.complex_psi && (no != 2 || c.p != 3)) CFAIL("complex psi needs out=2 and p=3");
-    if (!c.complex_psi && no != 1) CFAIL("real psi needs out=1");
-    if (c.potential < 0 || c.potential > GPE_POT_NONE) CFAIL("Unknown potential type: %d", c.potential);
-    if (c.base_mode >= 0 && (dim != 1 || no != 1)) CFAIL("Hermite base needs dim=1, out=1");
-    if (c.p < 1 || c.p > 32) CFAIL("power p must be in [1,32]");
-    if (c.omega_rot != 0.f && (!c.complex_psi || dim < 2)) CFAIL("rotation needs complex psi and dim>=2");
-    if (c.base_kind < 0 || c.base_kind > GPE_BASE_PRECOMPUTED) CFAIL("Unknown base kind: %d", c.base_kind);
-    if (c.envelope < 0 || c.envelope > GPE_ENV_SIN) CFAIL("Unknown envelope: %d", c.envelope);
-    if (c.envelope != GPE_ENV_NONE && (dim != 1 || no != 1)) CFAIL("the boundary factor needs dim=1, out=1");
-    if (c.w_riesz != 0.f && no != 1 && !(c.complex_psi && no == 2 && c.p == 3))
-        CFAIL("the Riesz energy term needs real psi (out=1) or complex psi (out=2) with p = 3");
-    if (c.riesz_kind < 0 || c.riesz_kind > GPE_RIESZ_VARIATIONAL) CFAIL("Unknown Riesz kind: %d", c.riesz_kind);
-    if (c.lambda_kind != GPE_LAMBDA_RAYLEIGH && c.lambda_kind != GPE_LAMBDA_ENERGY) CFAIL("Unknown lambda kind: %d", c.lambda_kind);
-    if (c.lambda_kind == GPE_LAMBDA_ENERGY && (c.complex_psi || no != 1 || (c.p & 1) == 0))
-        CFAIL("the energy-functional lambda needs real psi (out=1) and an odd power p");
-    if (c.w_reg_lam != 0.f && c.lambda_kind != GPE_LAMBDA_ENERGY) CFAIL("the 1/lambda^2 regulariser needs the energy-functional lambda");
-    if ((c.w_reg_f != 0.f || c.w_reg_lam != 0.f) && (c.complex_psi || no != 1)) CFAIL("the regularisers need real psi (out=1)");
-    if ((c.w_reg_f != 0.f && !(c.reg_f_eps > 0.f)) || (c.w_reg_lam != 0.f && !(c.reg_lam_eps > 0.f))) CFAIL("regulariser eps must be > 0");
-    for (int i = 1; i < c.n_layers - 1; ++i)
-        if (c.layers[i] < 1 || c.layers[i] > 1024) CFAIL("hidden width %d out of range", c.layers[i]);
-    // Width padding.  The MFMA kernel sets are instantiated for one hidden width of 32, 64, 128 or 256; other plain-tanh MLPs of width <= 256 --
-    // the 2D scripts' own [2,100,100,100,1] (src/gross_pitaevskii_2D_minimal.py:377), ragged widths -- are run as the next such width with
-    // zero rows / columns / biases in the padding.  A padded unit sees z = 0, gives tanh(0) = 0 with all jets 0, feeds zero outgoing weights
-    // and so receives the gradient 0 exactly on every one of its weights: Adam leaves them at 0 and the network stays the caller's.
-    // ShiftedTanh (tanh + 1) would give 1 there: its padded units get the bias -40 instead of 0 -- tanh(-40) = -1 exactly in fp32 (exp(-80) + 1 = 1),
-    // so the unit outputs exactly 0 with slope 1 - t^2 = 0, every gradient that touches it is 0 again, and the bias itself stays where it is.
-    // GPE_PAD_WIDTH=0 or GPE_PATH_GENERIC: as given.
-    for (int i = 0; i < c.n_layers; ++i) e->user_layers[i] = c.layers[i];
-    {
-        const char* envp = getenv("GPE_PAD_WIDTH");
-        int wmax = 0; bool uni = true;
-        for (int i = 1; i < c.n_layers - 1; ++i) { wmax = std::max(wmax, c.layers[i]); uni = uni && c.layers[i] == c.layers[1]; }
-        const bool native = uni && (wmax == 32 || wmax == 64 || wmax == 128 || wmax == 256);
-        // (widths above 256 -- train_pinn's default [2,400,400,400,1], src/gross_pitaevskii_2D_minimal.py:278 -- have no whole-network kernel: they are
-        // padded to the next multiple of 256 so that the GENERIC set runs every hidden map on its 128 x 128-tile MFMA kernels instead of the VALU ones)
-        const bool big = wmax > 256 && wmax <= 1024 && !(uni && wmax % 256 == 0);
-        if (!(envp && atoi(envp) == 0) && (big || (!native && wmax <= 256)) && c.path != GPE_PATH_GENERIC && c.net_kind == GPE_NET_MLP &&
-            (c.activation == GPE_ACT_TANH || c.activation == GPE_ACT_TANH_PLUS1) && c.n_layers - 2 >= 2) {
-            // the smallest instantiated width that holds the widest layer and whose kernels take this depth (32 / 64: all weights in LDS)
-            int Hp = big ? (int)round_up(wmax, 256) : 0;
-            if (!big)
-            for (int h : {32, 64, 128, 256}) {
-                if (h < wmax) continue;
-                if (h <= 64) {
-                    const int Lm = c.n_layers - 3;                        // hidden -> hidden maps
-                    const size_t pp = round_up((size_t)dim * h + h + (size_t)Lm * (h * h + h) + (size_t)h * no + no, 64);
-                    if ((pp + (size_t)(8 + c.n_layers + 2) * h + 8 + 4 * (dim + 2) * F_TILE) * sizeof(float) > 160 * 1024) continue;
-                }
-                Hp = h;
-                break;
-            }
-            int pl[GPE_MAX_LAYERS];
-            for (int i = 0; i < c.n_layers; ++i) pl[i] = (i == 0 || i == c.n_layers - 1) ? c.layers[i] : Hp;
-            int offp = 0;
-            for (int j = 0; j + 1 < c.n_layers; ++j) {
-                const int iu = c.layers[j], ou = c.layers[j + 1], ip = pl[j], op = pl[j + 1];
-                for (int o = 0; o < ou; ++o) for (int i = 0; i < iu; ++i) e->umap.push_back(offp + o * ip + i);
-                offp += ip * op;
-                for (int o = 0; o < ou; ++o) e->umap.push_back(offp + o);
-                if (c.activation == GPE_ACT_TANH_PLUS1 && j + 2 < c.n_layers) for (int o = ou; o < op; ++o) e->pad_bias.push_back(offp + o);
-                offp += op;
-            }
-            e->P_user = (int)e->umap.size();
-            for (int i = 1; i < c.n_layers - 1; ++i) e->cfg.layers[i] = Hp;
-        }
-    }
-    NetDesc& nd = e->nd;
-    memset(&nd, 0, sizeof nd);
-    nd.dim = dim; nd.n_out = no; nd.shift = c.activation == GPE_ACT_TANH_PLUS1 ? 1.f : 0.f;
-    if (c.net_kind != GPE_NET_MLP && c.net_kind != GPE_NET_RESIDUAL) CFAIL("Unknown network kind: %d", c.net_kind);
-    for (int j = 0; j < GPE_MAX_LAYERS; ++j) { nd.skip[j] = -1; nd.shiftv[j] = nd.shift; }
-    if (c.net_kind == GPE_NET_RESIDUAL) {      // refine/box_to_gaussian_pinn_simulation.py:100-130
-        const int nb = c.n_layers - 3;
-        if (nb < 1 || 2 * nb + 3 > GPE_MAX_LAYERS) CFAIL("residual network: 1..%d blocks", (GPE_MAX_LAYERS - 3) / 2);
-        for (int i = 2; i < c.n_layers - 1; ++i) if (c.layers[i] != c.layers[1]) CFAIL("residual network: one hidden width");
-        nd.n_lin = 2 * nb + 2;
-        nd.width[0] = dim;
-        for (int i = 1; i <= 2 * nb + 1; ++i) nd.width[i] = c.layers[1];
-        nd.width[nd.n_lin] = no;
-        for (int bq = 0; bq < nb; ++bq) nd.skip[2 * bq + 2] = 2 * bq;     // lin2 of block bq adds hidden layer 2 bq (the block input)
-        for (int h = 1; h < nd.n_lin - 1; ++h) nd.shiftv[h] = 0.f;        // plain tanh inside the blocks; the first layer keeps `activation`
-    } else {
-        nd.n_lin = c.n_layers - 1;
-        for (int i = 0; i < c.n_layers; ++i) nd.width[i] = c.layers[i];
-    }
-    int off = 0;
-    for (int j = 0; j < nd.n_lin; ++j) {
-        nd.offW[j] = off; off += nd.width[j] * nd.width[j + 1];
-        nd.offB[j] = off; off += nd.width[j + 1];
-    }
-    nd.n_params = off;
-    e->P = off;
-    if (e->umap.empty()) e->P_user = off;
-    e->Ppad = (int)round_up(off, 64);
-    // path selection: fused kernels need >= 2 hidden layers of one width H in {32, 64}
-    bool uniform = true;
-    for (int i = 2; i < c.n_layers - 1; ++i) uniform = uniform && (c.layers[i] == c.layers[1]);
-    const int H = c.layers[1];
-    const int Lh = nd.n_lin - 1;                                                 // hidden layers (an MLP's n_layers - 2; a residual network's 2 blocks + 1)
-    size_t lds_need = ((size_t)e->Ppad + (size_t)(8 + nd.n_lin + 3) * c.layers[1] + 8 + 4 * (dim + 2) * F_TILE) * sizeof(float);
-    // residual blocks (refine/box_to_gaussian_pinn_simulation.py): round 4 -- one or two blocks of width 32 / 64, real psi, on the cooperative
-    // whole-network kernels (f_forward_coop / f_backward_coop <..., RES>); everything else on the generic set
-    const bool residual = c.net_kind == GPE_NET_RESIDUAL;
-    if (residual && !((H == 32 || H == 64) && no == 1 && (nd.n_lin - 2 == 2 || nd.n_lin - 2 == 4))) uniform = false;
-    { const char* envr = getenv("GPE_RES_FUSED"); if (residual && envr && atoi(envr) == 0) uniform = false; }
-    bool fused_ok = uniform && (H == 32 || H == 64) && Lh >= 2 && lds_need <= 160 * 1024;
-    if (residual && (H == 128 || H == 256)) uniform = false;                    // (no residual form of the 8-wave kernels)
-    if (uniform && H == 128 && Lh >= 2 && dim <= 2) fused_ok = true;          // cooperative kernels, weights streamed from L2
-    // wide kernel set: H = 256 and 3D H = 128 entirely; 1D/2D H = 128: its per-map reverse kernels (no register spills, -5..7 % against
-    // f_backward_coop<128>) behind the cooperative forward kernel (7 % faster than w_forward there) -- same stored-activation format.
-    // GPE_WIDE=1: forward too; GPE_WIDE=0: cooperative kernels only (1D/2D)
-    const char* envw = getenv("GPE_WIDE");
-    const int wmode = envw ? atoi(envw) : -1;
-    if (uniform && Lh >= 2 && (H == 256 || (H == 128 && dim == 3))) { fused_ok = true; e->wide = true; e->wide_fwd = true; }
-    else if (uniform && Lh >= 2 && H == 128 && wmode != 0) { fused_ok = true; e->wide = true; e->wide_fwd = wmode == 1; }
-    if (c.path == GPE_PATH_FUSED && !fused_ok)
-        CFAIL("fused path needs >=2 hidden layers of one width: 32 or 64 (P*4 <= 160KB LDS), 128 or 256");
-    e->path = (c.path == GPE_PATH_GENERIC || !fused_ok) ? GPE_PATH_GENERIC : GPE_PATH_FUSED;
-    e->H = H;
-    if (e->path == GPE_PATH_FUSED) {
-        // f_forward is compiled for GPE_FWD_WAVES resident workgroups per CU (__launch_bounds__): more cannot be honoured by this build
-        const char* envfw = getenv("GPE_FWD_WG_PER_CU");
-        if (envfw && (atoi(envfw) < 1 || atoi(envfw) > GPE_FWD_WAVES))
-            CFAIL("GPE_FWD_WG_PER_CU=%s: this build runs f_forward at 1..%d workgroups per CU (more need a build with -DGPE_FWD_WAVES raised to match)",
-                  envfw, GPE_FWD_WAVES);
-    }
-#undef CFAIL
-    e->device = device;
-    e->stream = (hipStream_t)hip_stream;
-    hipError_t st = hipSetDevice(device);
-    if (st != hipSuccess) { e->err = std::string("hipSetDevice: ") + hipGetErrorString(st); return bail(GPE_ERR_HIP); }
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) == hipSuccess) e->num_cu = prop.multiProcessorCount;
-    e->cap = c.history_capacity > 0 ? c.history_capacity : 65536;
-    auto alloc = [&](void** p, size_t bytes) -> bool {
-        hipError_t s2 = hipMalloc(p, bytes + 256);
-        if (s2 != hipSuccess) { e->err = std::string("hipMalloc: ") + hipGetErrorString(s2); return false; }
-        (void)hipMemset(*p, 0, bytes + 256);
-        return true;
-    };
-    bool ok = alloc((void**)&e->theta, (size_t)e->P * 4) && alloc((void**)&e->am, (size_t)e->P * 4) &&
-              alloc((void**)&e->av, (size_t)e->P * 4) && alloc((void**)&e->grad, ((size_t)e->P + GT_COUNT) * 4) &&
-              alloc((void**)&e->dbl, (S_COUNT + LS_COUNT + 4) * sizeof(double)) && alloc((void**)&e->od, sizeof(OptDev)) &&
-              alloc((void**)&e->hist, (size_t)e->cap * sizeof(gpe_scalars)) && alloc((void**)&e->last, sizeof(gpe_scalars)) &&
-              alloc((void**)&e->orth_dev, 8 * sizeof(float*));
-    {
-        const char* envu = getenv("GPE_UPDATE_MULTI");               // 0: the single-workgroup update at every size
-        const char* envum = getenv("GPE_UPDATE_MULTI_MIN");          // tests: the multi-workgroup form from this many parameters on
-        const int multi_min = envum ? atoi(envum) : UPD_MULTI_MIN;
-        if (ok && e->P >= multi_min && !(envu && atoi(envu) == 0)) ok = alloc((void**)&e->upd_snap, sizeof(UpdSnap));
-        const char* envuc = getenv("GPE_UPDATE_CACHE");
-        e->update_cache = !(envuc && atoi(envuc) == 0);
-        const char* envf3 = getenv("GPE_FUSE_SEED");
-        e->fuse_seed = !(envf3 && atoi(envf3) == 0);
-        const char* envf4 = getenv("GPE_FUSE_SEED_MAX");
-        if (envf4) e->fuse_seed_max = atoll(envf4);
-        const char* envps = getenv("GPE_PIPE_SHARE");
-        if (envps) e->pipe_share = atoi(envps);
-        const char* envsm = getenv("GPE_SHARE_MIN_TILES");
-        if (envsm && atoi(envsm) > 0) e->share_min_tiles = atoi(envsm);
-        const char* envfs = getenv("GPE_FWD_SHARE");
-        if (envfs) e->fwd_share = atoi(envfs);
-        const char* envf5 = getenv("GPE_FUSE_HEAD");
-        e->fuse_head = !(envf5 && atoi(envf5) == 0);
-        const char* envf7 = getenv("GPE_FUSE_HEAD_TILE_MIN");
-        if (envf7) e->fuse_head_tile_min = atoll(envf7);
-        const char* envf6 = getenv("GPE_FUSE_HEAD_MAX");
-        if (envf6) e->fuse_head_max = atoll(envf6);
-        if (ok && e->fuse_head) ok = alloc((void**)&e->head_slots, (size_t)HEAD_SLOTS * 4 * sizeof(double));
-        // opt-in: measured 1 us SLOWER than the two launches at 2 048 .. 65 536 points (profiles/r04/small_batch.txt) -- 200 workgroups'
-        // tickets on one address (~12 ns apiece) and the write-through hand-off cost what the saved launch gives
-        const char* envfu = getenv("GPE_FUSE_UPDATE");
-        e->fuse_update = envfu && atoi(envfu) != 0;
-        if (ok && e->fuse_update) ok = alloc((void**)&e->upd_ticket, 64);
-        // opt-in as well: measured EQUAL to the single-workgroup update (35.8 vs 35.7 us at 2 048 points, 41.4 vs 41.0 at 4 000,
-        // profiles/r04/small_batch.txt) -- at these sizes a dependent launch costs ~4 us whatever it runs, and the update's own chain is short
-        const char* envsu = getenv("GPE_SPLIT_UPDATE");
-        e->split_update = envsu && atoi(envsu) != 0;
-        if (ok && e->split_update && !e->upd_snap && upd_chunk_host(e->P) <= 1024) ok = alloc((void**)&e->upd_snap_small, sizeof(UpdSnap));
-
-    }
-    if (ok && e->path == GPE_PATH_FUSED) {
-        e->nslab = (H >= 128) ? std::max(e->nslab_g, e->num_cu) : e->num_cu * 2;     // H = 128: 16 atomic slabs, or one per workgroup (cooperative)
-        if (e->wide) wide_init();
-        { const char* envm = getenv("GPE_WIDE_MIN_TILES"); if (envm && atoll(envm) >= 0) e->wide_min_tiles = atoll(envm); }
-        // WpkT is followed by the bf16 pieces of the same maps (3 x 2 bytes per weight; pack_weight_element, f_forward_b6)
-        ok = alloc((void**)&e->Wpk, (size_t)(Lh - 1) * H * H * 4) && alloc((void**)&e->WpkT, (size_t)(Lh - 1) * H * H * (4 + 6 + 6)) &&
-             alloc((void**)&e->gslab, (size_t)e->nslab * e->Ppad * 4);
-        if (ok) {
-            const int Cmain = dim + 2;        // training batches: value, dim first derivatives, Laplacian
-            const size_t wb = (size_t)(Lh - 1) * H * H * sizeof(float);
-            const char* env = getenv("GPE_WLDS");                     // tuning switch: 0 = weights from L2, 1 = from LDS
-            const bool want = env ? (atoi(env) != 0) : true;
-            const size_t smallb = ((size_t)(4 + (Lh - 1) + no) * H + 8) * sizeof(float);
-            e->fwd_wlds = want && H <= 64 && wb + smallb <= 64 * 1024;
-            const char* envb6 = getenv("GPE_FWD_B6");                  // 1: f_forward_b6 for the large-batch forward pass at H <= 64
-            e->fwd_b6 = envb6 && atoi(envb6) != 0 && H <= 64;
-            const char* envb7 = getenv("GPE_BWD_B6");                  // 1: the cooperative reverse kernel's adjoint products on the bf16 pipe
-            e->bwd_b6 = envb7 && atoi(envb7) != 0 && H <= 64 && H >= 32;
-            const char* envp = getenv("GPE_PIPE");                     // 0: the two-barrier cooperative reverse kernel (f_backward_coop) at H <= 64
-            e->bwd_pipe = !envp || atoi(envp) != 0;
-            const char* envw = getenv("GPE_COOP_WG_PER_CU");
-            if (envw && atoi(envw) >= 1 && atoi(envw) <= 2) e->coop_wg_per_cu = atoi(envw);
-            const char* envfw = getenv("GPE_FWD_WG_PER_CU");
-            if (envfw) e->fwd_wg_per_cu = atoi(envfw);                 // (range checked above, before any allocation)
-            const char* envc = getenv("GPE_COOP");
-            e->coop = envc ? atoi(envc) : 1;          // measured: faster than the per-wave-tile kernels at every batch size
-            const char* envm = getenv("GPE_COOP_MAX_TILES");
-            e->coop_max_tiles = envm ? atoll(envm) : 0;
-            const char* env8 = getenv("GPE_COOP128");
-            e->coop128 = !env8 || atoi(env8) != 0;
-            const char* env9 = getenv("GPE_COOP_FWD128");
-            e->coop_fwd128 = !env9 || atoi(env9) != 0;
-            const char* envf = getenv("GPE_COOP_FWD_MAX_TILES");
-            e->coop_fwd_max_tiles = envf ? atoll(envf) : (int64_t)e->num_cu * 8;   // measured: wins below ~32 768 points, loses 8 % at 1M
-            const char* envs = getenv("GPE_STAGE_MIN_TILES");        // batches with fewer tiles take the unstaged per-wave-tile kernels
-            e->stage_min_tiles = envs ? atoll(envs) : 0;
-            const char* envr = getenv("GPE_RACC");
-            e->bwd_racc = (!envr || atoi(envr) != 0) && H <= 64 && (Lh - 1) >= 1 && (Lh - 1) <= 3 &&
-                          ((size_t)e->Ppad + 4 * (size_t)H + 4 * (size_t)Cmain * F_TILE) * sizeof(float) + smallb + wb <= 160 * 1024;
-            // allow > 64 KB dynamic LDS
-            const int lds_b = 160 * 1024, lds_f = 64 * 1024;
-#define SETLDS(HH, CC, EE, NO)                                                                                                   \
-    (void)hipFuncSetAttribute((const void*)f_backward<HH, CC, EE, NO, false, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_b); \
-    (void)hipFuncSetAttribute((const void*)f_backward<HH, CC, EE, NO, true, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_b);  \
-    (void)hipFuncSetAttribute((const void*)f_backward<HH, CC, EE, NO, true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_b);  \
-    (void)hipFuncSetAttribute((const void*)f_backward<HH, CC, EE, NO, true, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_b);  \
-    (void)hipFuncSetAttribute((const void*)f_backward_coop<HH, CC, EE, NO, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_b); \
-    (void)hipFuncSetAttribute((const void*)f_backward_coop<HH, CC, EE, NO, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_b); \
-    (void)hipFuncSetAttribute((const void*)f_backward_coop<HH, CC, EE, NO, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_b); \
-    if constexpr (NO == 1) {                                                                                                        \
-        (void)hipFuncSetAttribute((const void*)f_backward_coop<HH, CC, EE, 1, 2, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_b); \
-        (void)hipFuncSetAttribute((const void*)f_backward_coop<HH, CC, EE, 1, 4, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_b); \
-        (void)hipFuncSetAttribute((const void*)f_backward_coop<HH, CC, EE, 1, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_b); \
-        (void)hipFuncSetAttribute((const void*)f_backward_coop<HH, CC, EE, 1, 5>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_b); \
-    }                                                                                                                               \
-    set_pipe_lds<HH, CC, EE, NO>(lds_b);                                                                                        \
-    (void)hipFuncSetAttribute((const void*)f_backward_coop<HH, CC, EE, NO, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_b); \
-    (void)hipFuncSetAttribute((const void*)f_backward_coop<HH, CC, EE, NO, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_b); \
-    (void)hipFuncSetAttribute((const void*)f_backward_coop<HH, CC, EE, NO, 3, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_b); \
-    (void)hipFuncSetAttribute((const void*)f_forward<HH, CC, EE, NO, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_f);      \
-    (void)hipFuncSetAttribute((const void*)f_forward_b6<HH, CC, EE, NO, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024)
-#ifdef GPE_FAST_BUILD
-            SETLDS(64, 1, 0, 1); SETLDS(64, 4, 1, 1);
-#else
-            SETLDS(64, 1, 0, 1); SETLDS(64, 3, 1, 1); SETLDS(64, 4, 1, 1); SETLDS(64, 5, 1, 1);
-            SETLDS(64, 1, 0, 2); SETLDS(64, 3, 1, 2); SETLDS(64, 4, 1, 2); SETLDS(64, 5, 1, 2);
-            SETLDS(32, 1, 0, 1); SETLDS(32, 3, 1, 1); SETLDS(32, 4, 1, 1); SETLDS(32, 5, 1, 1);
-            SETLDS(32, 1, 0, 2); SETLDS(32, 3, 1, 2); SETLDS(32, 4, 1, 2); SETLDS(32, 5, 1, 2);
-#undef SETLDS
-#define SETLDS128(CC, EE, NO)                                                                                                  \
-    (void)hipFuncSetAttribute((const void*)f_backward_coop<128, CC, EE, NO, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_b); \
-    (void)hipFuncSetAttribute((const void*)f_backward_coop<128, CC, EE, NO, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_b); \
-    (void)hipFuncSetAttribute((const void*)f_backward_coop<128, CC, EE, NO, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_b); \
-    (void)hipFuncSetAttribute((const void*)f_backward_coop<128, CC, EE, NO, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_b); \
-    (void)hipFuncSetAttribute((const void*)f_backward_coop<128, CC, EE, NO, 5>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_b); \
-    (void)hipFuncSetAttribute((const void*)f_forward_coop<128, CC, EE, NO, 5>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_b); \
-    (void)hipFuncSetAttribute((const void*)f_forward_coop<128, CC, EE, NO, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_b); \
-    (void)hipFuncSetAttribute((const void*)f_forward_coop<128, CC, EE, NO, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_b); \
-    (void)hipFuncSetAttribute((const void*)f_forward_coop<128, CC, EE, NO, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_b); \
-    (void)hipFuncSetAttribute((const void*)f_forward_coop<128, CC, EE, NO, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_b); \
-    (void)hipFuncSetAttribute((const void*)f_backward<128, CC, EE, NO, false, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_b)
-            SETLDS128(1, 0, 1); SETLDS128(3, 1, 1); SETLDS128(4, 1, 1); SETLDS128(1, 0, 2); SETLDS128(3, 1, 2); SETLDS128(4, 1, 2);
-#undef SETLDS128
-#endif
-        }
-    }
-    if (ok) {
-        ok = alloc((void**)&e->grad_bc, (size_t)e->P * 4);
-        if (ok && e->path == GPE_PATH_FUSED) ok = alloc((void**)&e->gslab_bc, (size_t)e->nslab * e->Ppad * 4);
-        const char* envm2 = getenv("GPE_GEN_MFMA");
-        e->gen_mfma = !envm2 || atoi(envm2) != 0;
-        { const char* envc = getenv("GPE_GEN_MIN_CHUNK"); if (envc && atoll(envc) >= 16) e->gen_min_chunk = (atoll(envc) + 15) / 16 * 16; }
-        const char* envm3 = getenv("GPE_GEN_MFMA2");
-        e->gen_mfma2 = !envm3 || atoi(envm3) != 0;
-#ifndef GPE_FAST_BUILD
-        (void)hipFuncSetAttribute((const void*)g_bwd_weight_mfma2<1, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)g_bwd_weight_mfma2<3, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)g_bwd_weight_mfma2<4, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)g_bwd_weight_mfma2<5, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-#else
-        (void)hipFuncSetAttribute((const void*)g_bwd_weight_mfma2<1, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)g_bwd_weight_mfma2<4, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-#endif
-        const char* envh = getenv("GPE_HEAD_WG_PER_CU");
-        if (envh && atoi(envh) > 0) e->head_wg_per_cu = atoi(envh);
-        const char* envht = getenv("GPE_HEAD_THREADS");
-        if (envht && (atoi(envht) == 256 || atoi(envht) == 512 || atoi(envht) == 1024)) e->head_threads = atoi(envht);
-        const char* envb = getenv("GPE_MERGE_BC");
-        e->merge_bc = !envb || atoi(envb) != 0;
-        const char* envg = getenv("GPE_GRAPH");
-        // gpe_run replays captured graphs of graph_steps steps each.  Round 4: ONE graph launch per 8 steps takes the host from 31 to
-        // 3 us per step at 2 048 points with the step time unchanged (35.5 us: the GPU is the bound); a one-step graph is slower (44.8 us).
-        // Default: on for batches up to graph_max_points (where the host thread was ~90 % busy enqueueing); GPE_GRAPH=0 / 1 forces it
-        e->use_graph = envg ? atoi(envg) != 0 : true;
-        e->graph_forced = envg != nullptr;
-        const char* envgs = getenv("GPE_GRAPH_STEPS");
-        if (envgs && atoi(envgs) >= 1 && atoi(envgs) <= 64) e->graph_steps = atoi(envgs);
-        const char* envq = getenv("GPE_SIDE_STREAM");
-        if (ok && (!envq || atoi(envq) != 0)) {
-            if (hipStreamCreateWithFlags(&e->side, hipStreamNonBlocking) != hipSuccess ||
-                hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming) != hipSuccess ||
-                hipEventCreateWithFlags(&e->ev_join, hipEventDisableTiming) != hipSuccess) {
-                e->err = "side stream / events could not be created";
-                return bail(GPE_ERR_HIP);
-            }
-        }
-    }
-    if (!ok) return bail(GPE_ERR_NOMEM);
-    fill_phys(e);
-    int rc = reset_opt(e, c.lr);
-    if (rc) return bail(rc);
-    if (!e->pad_bias.empty()) {                   // (the padding's biases are in place before the first gpe_set_params, too)
-        std::vector<float> pb(e->pad_bias.size(), -40.f);
-        for (size_t i = 0; i < pb.size(); ++i)
-            if (hipMemcpy(e->theta + e->pad_bias[i], &pb[i], sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { e->err = "hipMemcpy (padding)"; return bail(GPE_ERR_HIP); }
-    }
+    AllocSwitches sw;
+    int rc = check_config(e, *cfg);
+    if (!rc) { pad_widths(e); rc = describe_net(e); }
+    if (!rc) rc = select_path(e);
+    if (!rc) rc = open_device(e, device, hip_stream);
+    if (!rc) { read_switches(e, sw); rc = alloc_state(e, sw); }
+    if (!rc) { raise_lds_limits(e); fill_phys(e); rc = reset_opt(e, e->cfg.lr); }
+    const float pad_b = -40.f;                    // (the padding's biases are in place before the first gpe_set_params, too)
+    for (size_t i = 0; !rc && i < e->pad_bias.size(); ++i)
+        if (hipMemcpy(e->theta + e->pad_bias[i], &pad_b, sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { e->err = "hipMemcpy (padding)"; rc = GPE_ERR_HIP; }
+    if (rc) { g_create_error = e->err; delete e; return rc; }
     *out = e;
     return GPE_OK;
 }
@@ -3002,7 +2984,7 @@ int gpe_comm_init(gpe_engine* e, const void* id128, int rank, int world) {
     memcpy(&id, id128, sizeof id);
     RCCLCHK(e, e->rccl.CommInitRank(&e->comm, world, id, rank));
     e->comm_rank = rank; e->comm_world = world;
-    { const char* envi = getenv("GPE_DP_INLINE"); e->dp_inline = !(envi && atoi(envi) == 0); }
+    e->dp_inline = env_on("GPE_DP_INLINE");
     HIPCHK(e, hipStreamCreateWithFlags(&e->comm_stream, hipStreamNonBlocking));
     HIPCHK(e, hipEventCreateWithFlags(&e->ev_x0, hipEventDisableTiming));
     HIPCHK(e, hipEventCreateWithFlags(&e->ev_x1, hipEventDisableTiming));

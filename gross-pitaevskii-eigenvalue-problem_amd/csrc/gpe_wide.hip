@@ -5,6 +5,7 @@
 
 #include "gpe_wide.h"
 #include "gpe_wide_api.h"
+#include "gpe_env.h"
 
 static size_t small4(const NetDesc& nd, int H) { return (size_t)(((4 + (nd.n_lin - 2) + nd.n_out) * H + 4 + 3) & ~3); }
 
@@ -89,7 +90,7 @@ static int wide_fwd_mt() {
 #else
     // opt-in (GPE_WIDE_FWD_MT=1): measured SLOWER than w_forward at H = 128 -- cfg3 forward 0.644 against 0.610 ms (f_forward_coop<128>: 0.580),
     // cfg4 1.56-1.58 against 1.52-1.54 (1.46), profiles/r04/wide_forward_mt_ab.txt
-    static const int mt = [] { const char* v = getenv("GPE_WIDE_FWD_MT"); return v ? atoi(v) : 0; }();
+    static const int mt = env_int("GPE_WIDE_FWD_MT", 0);          // (read once per process)
     return mt;
 #endif
 }
@@ -124,8 +125,7 @@ static void launch_bwd(const WideCall& a) {
     const size_t lds_m = ((size_t)7 * HH + 4 + small4(a.nd, HH) + (W_MAP_PIPE(HH, CC) ? 2 : 1) * ((size_t)CC * NT * 256 + (size_t)CC * W_NW * F_TILE)) * sizeof(float);
     float* zcur = a.Z0;
     float* znext = a.Z1;
-    const char* envt = getenv("GPE_WIDE_TOP");                 // 0: the output layer as a launch of its own (w_bwd_out)
-    const bool fuse_top = !(envt && atoi(envt) == 0);
+    const bool fuse_top = env_on("GPE_WIDE_TOP");              // 0: the output layer as a launch of its own (w_bwd_out); read at every launch
     if (!fuse_top) {
         if (no == 1)
             hipLaunchKernelGGL((w_bwd_out<HH, CC, EE, 1, NS>), dim3(grid), dim3(512), lds_o, a.stream, a.nd, a.theta, a.pts, a.stored, a.Ob,

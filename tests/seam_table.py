@@ -39,7 +39,7 @@ DEFAULTS = {
     "fwd_wg_per_cu": (r"int\s+fwd_wg_per_cu\s*=\s*(\d+)\s*;", 2),
     "head_wg_per_cu": (r"int\s+head_wg_per_cu\s*=\s*(\d+)\s*;", 1),
     "head_threads": (r"int\s+head_threads\s*=\s*(\d+)\s*;", 1024),
-    "coop_fwd_tiles_per_cu": (r"coop_fwd_max_tiles\s*=\s*envf\s*\?\s*atoll\(envf\)\s*:\s*\(int64_t\)e->num_cu\s*\*\s*(\d+)\s*;", 8),
+    "coop_fwd_tiles_per_cu": (r"coop_fwd_max_tiles\s*=\s*env_i64\(\s*\"GPE_COOP_FWD_MAX_TILES\"\s*,\s*\(int64_t\)e->num_cu\s*\*\s*(\d+)\s*\)\s*;", 8),
     "HEAD_SLOTS": (r"#define\s+HEAD_SLOTS\s+(\d+)", 512),
     "merge_bc_ratio": (r"e->nb_user\s*\*\s*(\d+)\s*<=\s*e->n_pde", 8),
     "gen_min_chunk": (r"int64_t\s+gen_min_chunk\s*=\s*(\d+)\s*;", 32),

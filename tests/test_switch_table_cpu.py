@@ -1,5 +1,6 @@
-"""The switch table (tests/switch_table.py) names every GPE_* variable the library reads, and nothing else: a new getenv in the
-sources fails here until its row -- values, the classes it applies to, what the switch matrix expects of it -- is added."""
+"""The switch table (tests/switch_table.py) names every GPE_* variable the library reads, and nothing else: a new read in the
+sources fails here until its row -- values, the classes it applies to, what the switch matrix expects of it -- is added.  A read is a
+call of one of csrc/gpe_env.h's readers (or a raw getenv) with the switch's name as a string literal."""
 import os
 import re
 
@@ -9,7 +10,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "gross-pitaevskii-eigenvalue-problem_amd", "csrc")
 UNITS = ("gpe_engine.hip", "gpe_wide.hip")
 
-GETENV = re.compile(r'getenv\(\s*"(GPE_[A-Z0-9_]+)"\s*\)')
+READERS = ("env_set", "env_on", "env_opt_in", "env_int", "env_i64", "env_int_in", "env_i64_in")
+GETENV = re.compile(r'\b(?:getenv|' + "|".join(READERS) + r')\(\s*"(GPE_[A-Z0-9_]+)"\s*[,)]')
+ANY_READ = re.compile(r'\b(?:getenv|' + "|".join(READERS) + r')\s*\(')
 
 
 def switches_read():
@@ -32,6 +35,23 @@ def test_the_units_read_the_switches_the_table_names():
 def test_getenv_pattern_catches_a_new_switch():
     src = 'int x; { const char* v = getenv("GPE_NEW_THING"); }  getenv( "GPE_OTHER" )'
     assert set(GETENV.findall(src)) == {"GPE_NEW_THING", "GPE_OTHER"}
+    for i, r in enumerate(READERS):
+        for call in (f'e->x = {r}("GPE_NEW_{i}");', f'if ({r}( "GPE_NEW_{i}" , e->x, 1, 2)) y();', f'{r}("GPE_NEW_{i}",0)'):
+            assert GETENV.findall(call) == [f"GPE_NEW_{i}"], call
+    assert not GETENV.findall('my_env_on("GPE_X"); env_on(name); env_int("OTHER_X", 0)')
+
+
+def test_no_read_hides_behind_a_name_that_is_no_literal():
+    """every getenv / reader call of the two units is one the pattern catches; gpe_env.h alone calls getenv with a variable"""
+    with open(os.path.join(CSRC, "gpe_env.h")) as f:
+        assert set(re.findall(r"static inline \w+ (\w+)\(", f.read())) == set(READERS)      # (READERS names every reader there is)
+    for u in UNITS:
+        with open(os.path.join(CSRC, u)) as f:
+            src = f.read()
+        assert len(ANY_READ.findall(src)) == len(GETENV.findall(src)), \
+            f"{u}: a getenv / env_* call whose argument is not a \"GPE_...\" literal: " \
+            + str([ln.strip() for ln in src.split("\n") if ANY_READ.search(ln) and len(ANY_READ.findall(ln)) != len(GETENV.findall(ln))])
+    assert ANY_READ.search('x = getenv (name);') and ANY_READ.search("env_int(n, 0)") and not ANY_READ.search("my_getenv(name)")
 
 
 def _descriptor(**kw):
