@@ -48,6 +48,7 @@ class gpe_config(C.Structure):
         ("base_kind", C.c_int32), ("envelope", C.c_int32), ("box_L", C.c_float), ("env_L", C.c_float),
         ("w_riesz", C.c_float), ("riesz_kind", C.c_int32), ("net_kind", C.c_int32), ("lambda_kind", C.c_int32),
         ("w_reg_f", C.c_float), ("reg_f_eps", C.c_float), ("w_reg_lam", C.c_float), ("reg_lam_eps", C.c_float),
+        ("mixture", C.c_int32), ("mix_g", C.c_float * 3), ("mix_norm", C.c_float * 2),
     ]
 
 
@@ -145,6 +146,8 @@ SYMBOLS = {
     "gpe_mse_step": (_int, [_vp, _P(gpe_scalars)]),
     "gpe_mse_loss_grad": (_int, [_vp, _P(C.c_double)]),
     "gpe_set_gamma": (_int, [_vp, _f]),
+    "gpe_set_mixture": (_int, [_vp, _f, _f, _f]),
+    "gpe_mixture_scalars": (_int, [_vp, _P(C.c_double)]),
     "gpe_set_power": (_int, [_vp, _int]),
     "gpe_set_lr": (_int, [_vp, _f]),
     "gpe_set_perturb_scale": (_int, [_vp, _f]),

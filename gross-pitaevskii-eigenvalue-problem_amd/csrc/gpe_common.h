@@ -41,9 +41,18 @@ struct Phys {
     int lambda_kind;                 // GPE_LAMBDA_*
     float w_reg_f, reg_f_eps, w_reg_lam, reg_lam_eps;
 };
+// Two-component mixture (gpe_config.mixture).  A struct of its own, handed to k_head_mix / k_seed_mix and (inside OptCfg) to the update
+// kernel only: Phys travels by value into every forward / reverse kernel that runs the head or forms the seeds itself (HeadArgs, SeedArgs),
+// and growing it changes how those compile -- the bits of existing small-batch steps moved when these fields were tried there.
+struct MixPhys {
+    int on;                          // 0: not a mixture
+    float g[3], n[2];                // (g11, g22, g12), target norms (n_1, n_2)
+};
 
 // Indices into the double "sums" exchange buffer (all-reduced over ranks between phase 1 and 2).
 enum { S_NUM = 0, S_DEN = 1, S_SYM = 2, S_ORTH0 = 3, /* ..S_ORTH0+3 */ S_RZ_K = 7, S_RZ_P = 8, S_RZ_I = 9, S_RZ_L = 10 /* <L_z> of complex psi */, S_COUNT = 12 };
+// A mixture has no rotation and no 13th sum: component 2's Rayleigh sums take the two slots behind the energy sums (component 1 keeps S_NUM, S_DEN).
+enum { S_MIX_NUM2 = 10, S_MIX_DEN2 = 11 };
 // Local (replicated, never exchanged) double scalars.
 enum { LS_BC_SE2 = 0, LS_BC_CNT = 1, LS_COUNT = 4 };
 // Tail of the float gradient exchange buffer.
@@ -62,6 +71,7 @@ struct OptDev {
     double es_best;
     long long stop_step;
     double b1p, b2p;      // beta1^step, beta2^step (running products: the Adam bias corrections without a pow() per step)
+    double mix[8];        // mixture engines: (mu_1, mu_2, I_1, I_2, num_1, den_1, num_2, den_2) of the last record (gpe_mixture_scalars)
 };
 
 struct OptCfg {
@@ -70,6 +80,7 @@ struct OptCfg {
     float T_0, T_mult, eta_min;
     float factor; int patience; float min_lr, threshold;
     float stop_tol; int stop_patience;
+    MixPhys mix;          // the loss assembly of a mixture step (two mu, two norm terms): the update kernels are the only readers of OptCfg
 };
 
 // Point coordinates of a batch: rows [0, na) come from `a`, rows [na, n) from `b` -- the collocation points and, appended

@@ -200,6 +200,17 @@ GPE_DEV void update_core(int P, float* __restrict__ theta, float* __restrict__ a
         double sr2 = (double)p_sr2;
         double pde = sr2 / ph.n_global;
         double nrm = (I - 1.0) * (I - 1.0);
+        if (oc.mix.on) {                  // two real components: one Rayleigh quotient and one norm term each; the record carries component 1
+            const double num2 = sums[S_MIX_NUM2], den2 = sums[S_MIX_DEN2];
+            const double lam2 = (double)(float)(num2 / den2), I2 = (double)((float)den2 * ph.dx);
+            lam = (double)(float)(num / den);
+            const double d1 = I - (double)oc.mix.n[0], d2 = I2 - (double)oc.mix.n[1];
+            nrm = d1 * d1 + d2 * d2;
+            if (lead && !mse_mode && !(do_update && p_stopped)) {
+                od->mix[0] = lam; od->mix[1] = lam2; od->mix[2] = I; od->mix[3] = I2;
+                od->mix[4] = num; od->mix[5] = den; od->mix[6] = num2; od->mix[7] = den2;
+            }
+        }
         double bc = bc_cnt > 0 ? p_bcse / bc_cnt : 0.0;
         double sym = ph.w_sym != 0.f ? sums[S_SYM] / ph.n_global : 0.0;
         double orth = 0.0;
@@ -1432,6 +1443,10 @@ static void fill_phys(gpe_engine* e) {
     o.T_0 = c.T_0; o.T_mult = c.T_mult; o.eta_min = c.eta_min; o.factor = c.factor; o.patience = c.patience;
     o.min_lr = c.min_lr; o.threshold = c.threshold;
     o.stop_tol = c.stop_tol; o.stop_patience = c.stop_patience;
+    MixPhys& mx = o.mix;
+    mx.on = c.mixture != 0;
+    for (int k = 0; k < 3; ++k) mx.g[k] = c.mixture ? c.mix_g[k] : 0.f;
+    for (int k = 0; k < 2; ++k) mx.n[k] = c.mixture ? c.mix_norm[k] : 0.f;
 }
 
 static int reset_opt(gpe_engine* e, float lr) {
@@ -1458,8 +1473,23 @@ static int check_config(gpe_engine* e, const gpe_config& in) {
     const int dim = c.layers[0], no = c.layers[c.n_layers - 1];
     if (dim < 1 || dim > GPE_MAX_DIM) CFAIL("dim must be 1..3");
     if (no < 1 || no > 2) CFAIL("output width must be 1 or 2");
+    if (c.mixture) {                  // two real components on the n_out = 2 kernels: what does not combine with them, first failing rule first
+        if (no != 2 || c.p != 3) CFAIL("a mixture needs out=2 and p=3");
+        if (c.complex_psi) CFAIL("a mixture has two real components: complex psi does not combine with it");
+        if (c.omega_rot != 0.f) CFAIL("a mixture has no rotating frame: omega_rot must be 0");
+        if (c.base_mode >= 0) CFAIL("a mixture has no analytic base: base_mode must be -1");
+        if (c.envelope != GPE_ENV_NONE) CFAIL("a mixture has no boundary factor: envelope must be GPE_ENV_NONE");
+        if (c.w_sym != 0.f) CFAIL("a mixture has no symmetry term: w_sym must be 0");
+        if (c.w_orth != 0.f) CFAIL("a mixture has no orthogonality term: w_orth must be 0");
+        if (c.w_riesz != 0.f) CFAIL("a mixture has no Riesz energy term: w_riesz must be 0");
+        if (c.lambda_kind != GPE_LAMBDA_RAYLEIGH) CFAIL("a mixture takes one Rayleigh quotient per component: lambda_kind must be GPE_LAMBDA_RAYLEIGH");
+        if (c.w_reg_f != 0.f || c.w_reg_lam != 0.f) CFAIL("a mixture has no regularisers: w_reg_f and w_reg_lam must be 0");
+        if (c.net_kind != GPE_NET_MLP) CFAIL("a mixture needs a plain MLP: residual blocks do not combine with it");
+        for (int k = 0; k < 3; ++k) if (!__builtin_isfinite(c.mix_g[k])) CFAIL("mixture coupling mix_g[%d] is not finite", k);
+        for (int k = 0; k < 2; ++k) if (!(c.mix_norm[k] > 0.f) || !__builtin_isfinite(c.mix_norm[k])) CFAIL("mixture target norm mix_norm[%d] must be finite and > 0", k);
+    }
     if (c.complex_psi && (no != 2 || c.p != 3)) CFAIL("complex psi needs out=2 and p=3");
-    if (!c.complex_psi && no != 1) CFAIL("real psi needs out=1");
+    if (!c.complex_psi && !c.mixture && no != 1) CFAIL("real psi needs out=1");
     if (c.potential < 0 || c.potential > GPE_POT_NONE) CFAIL("Unknown potential type: %d", c.potential);
     if (c.base_mode >= 0 && (dim != 1 || no != 1)) CFAIL("Hermite base needs dim=1, out=1");
     if (c.p < 1 || c.p > 32) CFAIL("power p must be in [1,32]");
@@ -1818,7 +1848,10 @@ int gpe_active_kernels(gpe_engine* e, char* buf, size_t n) {
     if (e->umap.empty()) snprintf(buf, n, "fwd=%s;bwd=%s;split=fwd %d/1024, bwd %d/1024", f, r, sf, sb);
     else snprintf(buf, n, "fwd=%s;bwd=%s;split=fwd %d/1024, bwd %d/1024;padded=hidden widths up to %d run as %d", f, r, sf, sb,
                   *std::max_element(e->user_layers + 1, e->user_layers + e->cfg.n_layers - 1), e->cfg.layers[1]);
-    if (e->wq) {      // bound quadrature weights: head and seeds by the standalone kernels' weighted instances, whatever the batch size
+    if (e->cfg.mixture) {      // a mixture always takes the standalone pair of its own (the fused head / seeds are real-psi only)
+        const size_t used = strlen(buf);
+        snprintf(buf + used, n - used, ";head=k_head_mix<%d,%d%s>;seed=k_seed_mix<%d,%d%s>", b.C, b.E, e->wq ? ",weighted" : "", b.C, b.E, e->wq ? ",weighted" : "");
+    } else if (e->wq) {      // bound quadrature weights: head and seeds by the standalone kernels' weighted instances, whatever the batch size
         const size_t used = strlen(buf);
         snprintf(buf + used, n - used, ";head=k_head_pde<%d,%d,weighted>;seed=k_seed_pde<%d,%d,weighted>", b.C, b.E, b.C, b.E);
     }
@@ -2282,6 +2315,7 @@ static int orth_publish(gpe_engine* e) {         // orth_host -> the device copy
 
 int gpe_bind_orth(gpe_engine* e, int k, const float* d_psi) {
     if (!e || k < 0 || k >= GPE_MAX_ORTH) return GPE_ERR_INVALID;
+    if (e->cfg.mixture) FAIL(e, GPE_ERR_STATE, "bind_orth: a mixture engine has no orthogonality term");
     if (d_psi && e->smp_every > 0) FAIL(e, GPE_ERR_STATE, "bind_orth: a sampler is bound, an orthogonality array would go stale at its next redraw");
     if (e->ost[k].on) {                          // the array (or NULL) replaces a frozen state
         HIPCHK(e, hipStreamSynchronize(e->stream));
@@ -2344,6 +2378,7 @@ static int orth_refill(gpe_engine* e) {
 
 int gpe_bind_orth_state(gpe_engine* e, int k, const float* h_flat, size_t n, int base_mode, float perturb_scale, float amplitude) {
     if (!e) return GPE_ERR_INVALID;
+    if (e->cfg.mixture) FAIL(e, GPE_ERR_STATE, "bind_orth_state: a mixture engine has no orthogonality term");
     if (k < 0 || k >= GPE_MAX_ORTH) FAIL(e, GPE_ERR_INVALID, "bind_orth_state: slot %d, need 0..%d", k, GPE_MAX_ORTH - 1);
     if (!h_flat) return gpe_bind_orth(e, k, nullptr);
     if (e->cfg.complex_psi || e->nd.n_out != 1) FAIL(e, GPE_ERR_INVALID, "bind_orth_state: frozen states need real psi (out=1)");
@@ -2436,6 +2471,7 @@ int gpe_forward_jets(gpe_engine* e, const float* d_x, int64_t n, float* d_jets) 
 
 int gpe_eval_density(gpe_engine* e, const float* d_x, int64_t n, float dx, int abs_flag, float* d_u, float* d_dens) {
     if (!e || !d_x || n <= 0) return GPE_ERR_INVALID;
+    if (e->cfg.mixture) FAIL(e, GPE_ERR_STATE, "eval_density: a mixture engine has one norm per component (use gpe_forward and gpe_mixture_scalars)");
     if (e->cfg.base_mode >= 0 && e->cfg.base_kind == GPE_BASE_PRECOMPUTED)
         FAIL(e, GPE_ERR_INVALID, "eval_density needs an analytic base (the precomputed base exists on the bound points only)");
     int rc = aux_forward(e, d_x, n, 1, 0);
@@ -2503,6 +2539,7 @@ static int launch_observe(gpe_engine* e, Batch& b, const float* x, int64_t n, co
 
 int gpe_observables(gpe_engine* e, const float* d_x, int64_t n, const float* d_V, float dv, struct gpe_observables* out) {
     if (!e || !out) return GPE_ERR_INVALID;
+    if (e->cfg.mixture) FAIL(e, GPE_ERR_STATE, "observables: not defined for a mixture engine (they would read the two components as complex psi)");
     const float* q = nullptr;
     if (!d_x) {
         if (!e->ux) FAIL(e, GPE_ERR_STATE, "observables of the bound points before bind_points");
@@ -2554,6 +2591,7 @@ static void monitor_clear(gpe_engine* e) {
 
 int gpe_bind_monitor(gpe_engine* e, const float* d_x, int64_t n, const float* d_V, float dv, int64_t every, int32_t capacity) {
     if (!e) return GPE_ERR_INVALID;
+    if (e->cfg.mixture && d_x && every > 0) FAIL(e, GPE_ERR_STATE, "monitor: its records are observables, which a mixture engine does not have");
     HIPCHK(e, hipStreamSynchronize(e->stream));
     if (!d_x || every <= 0) { monitor_clear(e); return GPE_OK; }
     // validate and allocate first, swap last: a bind that fails leaves the monitor that was there, records included
@@ -2590,6 +2628,7 @@ int gpe_bind_monitor(gpe_engine* e, const float* d_x, int64_t n, const float* d_
 
 int gpe_bind_keeper(gpe_engine* e, int metric, double min_delta, int64_t patience) {
     if (!e) return GPE_ERR_INVALID;
+    if (e->cfg.mixture && metric != GPE_KEEP_NONE) FAIL(e, GPE_ERR_STATE, "keeper: it judges monitor records, which a mixture engine does not have");
     if (metric == GPE_KEEP_NONE) {
         HIPCHK(e, hipStreamSynchronize(e->stream));
         keeper_clear(e);
@@ -2705,6 +2744,15 @@ static int launch_head_pde(gpe_engine* e) {
     Batch& b = e->main;
     dim3 g(head_grid(e, b.n));
     const float* none = nullptr;
+    if (e->cfg.mixture) {
+        if (e->wq) {
+            DISPATCH_TRAIN(b, hipLaunchKernelGGL((k_head_mix<CC, EE, true>), g, dim3(e->head_threads), 0, e->stream, e->ph, e->oc.mix, b.pts, b.V, b.O, b.u, b.Hu,
+                                                e->sums(), b.n, b.ld, e->n_pde, e->bc_target, b.Ob, e->lsums(), e->wq));
+        } else {
+            DISPATCH_TRAIN(b, hipLaunchKernelGGL((k_head_mix<CC, EE>), g, dim3(e->head_threads), 0, e->stream, e->ph, e->oc.mix, b.pts, b.V, b.O, b.u, b.Hu,
+                                                e->sums(), b.n, b.ld, e->n_pde, e->bc_target, b.Ob, e->lsums(), none));
+        }
+    } else
     if (e->wq) {      // bound quadrature weights: the weighted instance
         DISPATCH_TRAIN(b, hipLaunchKernelGGL((k_head_pde<CC, EE, true>), g, dim3(e->head_threads), 0, e->stream, e->ph, e->base_norm, b.pts, b.V, b.O,
                                             (const float* const*)e->orth_dev, b.u, b.Hu, b.ux, e->sums(), b.n, b.ld, e->n_pde,
@@ -2722,6 +2770,15 @@ static int launch_seed_pde(gpe_engine* e, float* d_resid, int want_seeds, int he
     Batch& b = e->main;
     dim3 g(head_grid(e, e->n_pde));
     const float* none = nullptr;
+    if (e->cfg.mixture) {      // (head_slots is 0: a mixture's head never rides in the forward kernel)
+        if (e->wq) {
+            DISPATCH_TRAIN(b, hipLaunchKernelGGL((k_seed_mix<CC, EE, true>), g, dim3(e->head_threads), 0, e->stream, e->ph, e->oc.mix, b.pts, b.V, b.u, b.Hu,
+                                                e->sums(), b.Ob, d_resid, e->dsc(), e->n_pde, b.ld, want_seeds, e->wq));
+        } else {
+            DISPATCH_TRAIN(b, hipLaunchKernelGGL((k_seed_mix<CC, EE>), g, dim3(e->head_threads), 0, e->stream, e->ph, e->oc.mix, b.pts, b.V, b.u, b.Hu,
+                                                e->sums(), b.Ob, d_resid, e->dsc(), e->n_pde, b.ld, want_seeds, none));
+        }
+    } else
     if (e->wq) {      // bound quadrature weights: the weighted instance (the head never rode in the forward kernel: head_class)
         DISPATCH_TRAIN(b, hipLaunchKernelGGL((k_seed_pde<CC, EE, true>), g, dim3(e->head_threads), 0, e->stream, e->ph, b.pts, b.V,
                                             (const float* const*)e->orth_dev, b.u, b.Hu, b.ux, e->sums(), b.Ob, d_resid, e->dsc(),
@@ -3315,8 +3372,24 @@ int gpe_residual(gpe_engine* e, gpe_scalars* out, float* d_psi, float* d_resid) 
 }
 
 int gpe_set_gamma(gpe_engine* e, float g) { if (!e) return GPE_ERR_INVALID; e->cfg.gamma = g; fill_phys(e); return GPE_OK; }
+int gpe_set_mixture(gpe_engine* e, float g11, float g22, float g12) {
+    if (!e) return GPE_ERR_INVALID;
+    if (!e->cfg.mixture) FAIL(e, GPE_ERR_STATE, "set_mixture: not a mixture engine (gpe_config.mixture)");
+    if (!__builtin_isfinite(g11) || !__builtin_isfinite(g22) || !__builtin_isfinite(g12)) FAIL(e, GPE_ERR_INVALID, "set_mixture: couplings must be finite");
+    e->cfg.mix_g[0] = g11; e->cfg.mix_g[1] = g22; e->cfg.mix_g[2] = g12; fill_phys(e); return GPE_OK;
+}
+int gpe_mixture_scalars(gpe_engine* e, double out[8]) {
+    if (!e || !out) return GPE_ERR_INVALID;
+    if (!e->cfg.mixture) FAIL(e, GPE_ERR_STATE, "mixture_scalars: not a mixture engine (gpe_config.mixture)");
+    OptDev h;
+    HIPCHK(e, hipMemcpyAsync(&h, e->od, sizeof h, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    for (int k = 0; k < 8; ++k) out[k] = h.mix[k];
+    return GPE_OK;
+}
 int gpe_set_power(gpe_engine* e, int p) {
     if (!e) return GPE_ERR_INVALID;
+    if (e->cfg.mixture && p != 3) FAIL(e, GPE_ERR_INVALID, "a mixture needs p=3");
     if (p < 1 || p > 32) FAIL(e, GPE_ERR_INVALID, "power p must be in [1,32]");
     e->cfg.p = p; fill_phys(e); return GPE_OK;
 }
@@ -3325,6 +3398,7 @@ int gpe_set_loss_weights(gpe_engine* e, const float w[6]) {
     if (!e || !w) return GPE_ERR_INVALID;
     if (w[5] != 0.f && e->nd.n_out != 1 && !(e->cfg.complex_psi && e->nd.n_out == 2 && e->cfg.p == 3))
         FAIL(e, GPE_ERR_INVALID, "the Riesz energy term needs real psi (out=1) or complex psi (out=2) with p = 3");
+    if (e->cfg.mixture && (w[3] != 0.f || w[4] != 0.f || w[5] != 0.f)) FAIL(e, GPE_ERR_INVALID, "a mixture has no symmetry, orthogonality or Riesz term");
     if (e->wq && w[3] != 0.f) FAIL(e, GPE_ERR_INVALID, "the symmetry batch has no quadrature weights: w_sym stays 0 while weights are bound");
     if ((w[3] != 0.f) != (e->cfg.w_sym != 0.f)) FAIL(e, GPE_ERR_INVALID, "the symmetry term cannot be switched on/off after bind_points");
     e->cfg.w_pde = w[0]; e->cfg.w_bc = w[1]; e->cfg.w_norm = w[2]; e->cfg.w_sym = w[3]; e->cfg.w_orth = w[4]; e->cfg.w_riesz = w[5];

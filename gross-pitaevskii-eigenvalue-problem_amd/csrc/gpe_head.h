@@ -431,6 +431,136 @@ __global__ __launch_bounds__(1024) void k_seed_pde(Phys ph, Pts x, const float* 
     if (threadIdx.x == 0) atomicAdd(sum_r2, t);
 }
 
+// ---- two-component mixture (gpe_config.mixture): head and seeds of two REAL order parameters in one trap ---------------------------
+//   H_a u_a = -c lap u_a + V u_a + (g_a1 u_1^2 + g_a2 u_2^2) u_a ,  a = 1, 2 ;  one Rayleigh quotient and one norm per component.
+// Kernels of their own, so that the per-point bodies of k_head_pde / k_seed_pde stay what they are.  The reduction is k_head_pde's:
+// grid-stride, fp64 partials, the five partial sums of a workgroup in one shuffle / LDS pass, one double atomic per workgroup and sum;
+// boundary rows riding in the batch are treated as k_head_pde treats those of complex psi (both outputs, cnt = n_bc * 2).  A mixture has
+// no base, envelope, orthogonality or energy sums (gpe_create refuses them), so none of that is here.
+// phase 1: u_a, H_a u_a per point; (num_1, den_1, num_2, den_2) -> sums[S_NUM, S_DEN, S_MIX_NUM2, S_MIX_DEN2], bse -> lsums.
+template <int C, int E, bool WQ = false>
+__global__ __launch_bounds__(1024) void k_head_mix(Phys ph, MixPhys mx, Pts x, const float* __restrict__ Vpre, const float* __restrict__ O,
+                                                  float* __restrict__ u_out, float* __restrict__ Hu_out, double* __restrict__ sums,
+                                                  int64_t N, int64_t ld, int64_t n_pde, const float* __restrict__ bc_target,
+                                                  float* __restrict__ Ob, double* __restrict__ lsums, const float* __restrict__ qw = nullptr) {
+    constexpr int D = C - 1 - E;
+    double num[2] = {0.0, 0.0}, den[2] = {0.0, 0.0}, bse = 0.0;
+    for (int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; m < N; m += (int64_t)gridDim.x * blockDim.x) {
+        if (m >= n_pde) {                              // boundary point riding in this batch
+            const int64_t mb = m - n_pde;
+            const float cnt = (float)((N - n_pde) * 2);
+#pragma unroll
+            for (int o = 0; o < 2; ++o) {
+                float e = ph.bc_nn_scale * O[(int64_t)o * ld + m];
+                if (bc_target) e -= bc_target[mb * 2 + o];
+                bse += (double)(e * e);
+                Ob[(int64_t)o * ld + m] = ph.w_bc * 2.0f / cnt * e * ph.bc_nn_scale * ph.inv_world;
+#pragma unroll
+                for (int c = 1; c < C; ++c) Ob[((int64_t)c * 2 + o) * ld + m] = 0.f;
+            }
+            continue;
+        }
+        float xv[3] = {0.f, 0.f, 0.f};
+        for (int k = 0; k < ph.dim; ++k) xv[k] = pts_at(x, m, ph.dim, k);
+        const float V = potential_at(ph, xv, Vpre, m);
+        double qd = 1.0;
+        if constexpr (WQ) qd = (double)qw[m];
+        float u[2], lap[2] = {0.f, 0.f};
+#pragma unroll
+        for (int o = 0; o < 2; ++o) {
+            u[o] = ph.perturb_scale * O[(int64_t)o * ld + m];
+#pragma unroll
+            for (int j = 0; j < E; ++j) lap[o] += ph.perturb_scale * O[((int64_t)(1 + D + j) * 2 + o) * ld + m];
+        }
+        const float s1 = u[0] * u[0], s2 = u[1] * u[1];
+        const float Hu[2] = {-ph.kin * lap[0] + V * u[0] + (mx.g[0] * s1 + mx.g[2] * s2) * u[0],
+                             -ph.kin * lap[1] + V * u[1] + (mx.g[2] * s1 + mx.g[1] * s2) * u[1]};
+#pragma unroll
+        for (int o = 0; o < 2; ++o) {
+            u_out[(int64_t)o * ld + m] = u[o];
+            Hu_out[(int64_t)o * ld + m] = Hu[o];
+            num[o] += wq_term<WQ>(qd, u[o] * Hu[o]);
+            den[o] += wq_term<WQ>(qd, u[o] * u[o]);
+        }
+    }
+    // all partial sums of the workgroup in one pass (the shuffle tree and wave order of k_head_pde / block_sum_256)
+    constexpr int K = 5;
+    __shared__ double redm[16 * K];
+    double vals[K] = {num[0], den[0], num[1], den[1], bse};
+    const int w = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        double v = vals[k];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+        if ((threadIdx.x & 63) == 0) redm[w * K + k] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < K) {
+        const int k = threadIdx.x;
+        double r = 0.0;
+        for (int i2 = 0; i2 < nw; ++i2) r += redm[i2 * K + k];
+        double* dst = k == 0 ? &sums[S_NUM] : k == 1 ? &sums[S_DEN] : k == 2 ? &sums[S_MIX_NUM2] : k == 3 ? &sums[S_MIX_DEN2] : &lsums[LS_BC_SE2];
+        if (k != 4 || r != 0.0) atomicAdd(dst, r);
+    }
+}
+
+// phase 2: mu_a = num_a / den_a (global sums), r_a = H_a u_a - mu_a u_a, sum (r_1^2 + r_2^2) -> sum_r2; Ob = dLoss/dO with mu_a constant
+// (their branch of the gradient vanishes: sum r_a u_a = 0).  The cross term rb_b 2 g_ab u_a u_b is d r_b / d u_a.  WQ as in k_seed_pde.
+template <int C, int E, bool WQ = false>
+__global__ __launch_bounds__(1024) void k_seed_mix(Phys ph, MixPhys mx, Pts x, const float* __restrict__ Vpre, const float* __restrict__ u_in,
+                                                  const float* __restrict__ Hu_in, const double* __restrict__ sums, float* __restrict__ Ob,
+                                                  float* __restrict__ resid_out, double* __restrict__ sum_r2, int64_t N, int64_t ld,
+                                                  int want_seeds, const float* __restrict__ qw = nullptr) {
+    constexpr int D = C - 1 - E;
+    __shared__ double red[16];
+    double sr2 = 0.0;
+    const double den1 = sums[S_DEN], den2 = sums[S_MIX_DEN2];
+    const float lam[2] = {(float)(sums[S_NUM] / den1), (float)(sums[S_MIX_NUM2] / den2)};
+    const float I[2] = {(float)den1 * ph.dx, (float)den2 * ph.dx};
+    const float cr = (float)(2.0 * (double)ph.w_pde / ph.n_global);
+    const float cn[2] = {ph.w_norm * 4.0f * (I[0] - mx.n[0]) * ph.dx, ph.w_norm * 4.0f * (I[1] - mx.n[1]) * ph.dx};
+    for (int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; m < N; m += (int64_t)gridDim.x * blockDim.x) {
+        float qv = 1.0f;
+        if constexpr (WQ) qv = qw[m];
+        float u[2], r[2], rb[2];
+#pragma unroll
+        for (int o = 0; o < 2; ++o) {
+            u[o] = u_in[(int64_t)o * ld + m];
+            r[o] = Hu_in[(int64_t)o * ld + m] - lam[o] * u[o];
+            rb[o] = cr * r[o];
+            sr2 += wq_term<WQ>((double)qv, r[o] * r[o]);
+            if (resid_out) resid_out[m * 2 + o] = r[o];
+        }
+        if (want_seeds) {
+            float xv[3] = {0.f, 0.f, 0.f};
+            for (int k = 0; k < ph.dim; ++k) xv[k] = pts_at(x, m, ph.dim, k);
+            const float V = potential_at(ph, xv, Vpre, m);
+            const float s1 = u[0] * u[0], s2 = u[1] * u[1], g11 = mx.g[0], g22 = mx.g[1], g12 = mx.g[2];
+            const float cross = 2.f * g12 * u[0] * u[1];
+            const float ub[2] = {rb[0] * (V + 3.f * g11 * s1 + g12 * s2 - lam[0]) + rb[1] * cross + cn[0] * u[0],
+                                 rb[1] * (V + 3.f * g22 * s2 + g12 * s1 - lam[1]) + rb[0] * cross + cn[1] * u[1]};
+            const float sc = ph.perturb_scale;
+#pragma unroll
+            for (int o = 0; o < 2; ++o) {
+                float Ub[C];
+                Ub[0] = ub[o];
+#pragma unroll
+                for (int j = 0; j < D; ++j) Ub[1 + j] = 0.f;
+#pragma unroll
+                for (int j = 0; j < E; ++j) Ub[1 + D + j] = -ph.kin * rb[o];
+#pragma unroll
+                for (int c = 0; c < C; ++c) {
+                    if constexpr (WQ) Ob[((int64_t)c * 2 + o) * ld + m] = qv * (sc * Ub[c]);
+                    else Ob[((int64_t)c * 2 + o) * ld + m] = sc * Ub[c];
+                }
+            }
+        }
+    }
+    double t = block_sum_256(sr2, red);
+    if (threadIdx.x == 0) atomicAdd(sum_r2, t);
+}
+
 // ---- quadrature weights (gpe_bind_weights): the total of the array and a count of entries the engine refuses ------------------
 // One workgroup, fixed order, fp64, no atomics: thread t adds entries t, t + 1024, ... in index order, then the wave shuffle tree and
 // the waves in order.  out[0] = sum of the finite, non-negative entries, out[1] = number of entries that are negative or not finite.

@@ -81,6 +81,9 @@ class GPEConfig:
     reg_f_eps: float = 1e-2
     w_reg_lam: float = 0.0                       # w / (lambda^2 + reg_lam_eps)      src/gross_pitaevskii_2D.py:204
     reg_lam_eps: float = 1e-6
+    mixture: bool = False                        # two real components u_1, u_2 on the two outputs (include/gpe_hip.h: gpe_config.mixture)
+    mix_g: Sequence[float] = (0.0, 0.0, 0.0)     # (g11, g22, g12)
+    mix_norm: Sequence[float] = (1.0, 1.0)       # target norms (n_1, n_2)
 
     def to_c(self) -> capi.gpe_config:
         c = capi.gpe_config()
@@ -104,6 +107,13 @@ class GPEConfig:
                      "beta2", "eps", "clip_norm", "T_0", "T_mult", "eta_min", "factor", "min_lr", "threshold",
                      "stop_tol", "box_L", "env_L", "w_riesz", "w_reg_f", "reg_f_eps", "w_reg_lam", "reg_lam_eps"):
             setattr(c, name, float(getattr(self, name)))
+        c.mixture = int(bool(self.mixture))
+        if len(self.mix_g) != 3 or len(self.mix_norm) != 2:
+            raise ValueError("mix_g = (g11, g22, g12), mix_norm = (n1, n2)")
+        for i in range(3):
+            c.mix_g[i] = float(self.mix_g[i])
+        for i in range(2):
+            c.mix_norm[i] = float(self.mix_norm[i])
         return c
 
     @property
@@ -694,6 +704,19 @@ class Engine:
     def set_gamma(self, g: float):
         self.cfg.gamma = float(g)
         self._chk(self.lib.gpe_set_gamma(self._h, float(g)))
+
+    def set_mixture(self, g11: float, g22: float, g12: float):
+        """Coupling matrix of a mixture engine from the next step on (gamma-continuation)."""
+        self._chk(self.lib.gpe_set_mixture(self._h, float(g11), float(g22), float(g12)))
+        self.cfg.mix_g = (float(g11), float(g22), float(g12))
+
+    MIXTURE_FIELDS = ("mu1", "mu2", "integral1", "integral2", "num1", "den1", "num2", "den2")
+
+    def mixture_scalars(self) -> dict:
+        """Both components' chemical potential, norm integral and Rayleigh sums of the last completed step (or residual()); synchronises."""
+        out = (C.c_double * 8)()
+        self._chk(self.lib.gpe_mixture_scalars(self._h, out))
+        return dict(zip(self.MIXTURE_FIELDS, [float(v) for v in out]))
 
     def set_power(self, p: int):
         self.cfg.p = int(p)

@@ -136,6 +136,23 @@ typedef struct gpe_config {
      *   w_reg_lam / (lambda^2 + reg_lam_eps)     "L_lambda": keeps lambda off zero (reference: w = 1, eps = 1e-6; needs GPE_LAMBDA_ENERGY)
      * mean over n_global; both zero: the terms are not formed */
     float w_reg_f, reg_f_eps, w_reg_lam, reg_lam_eps;
+    /* Two-component mixture (0 = off): the two outputs are the REAL order parameters u_1, u_2 of a binary condensate in one trap V,
+     *   H_a u_a = -c lap u_a + V u_a + (g_a1 u_1^2 + g_a2 u_2^2) u_a,   a = 1, 2,   g_21 = g_12      (layers[last] == 2, p == 3)
+     *   mu_a = sum u_a H_a u_a / sum u_a^2 (one Rayleigh quotient per component),   I_a = dx sum u_a^2,   r_a = H_a u_a - mu_a u_a
+     *   loss = w_pde sum_m (r_1^2 + r_2^2) / N + w_norm sum_a (I_a - n_a)^2 + w_bc bc      (bc as for complex psi: both outputs, cnt = n_b * 2)
+     * Seeds at the output jets, rb_a = 2 w_pde r_a / N, b the other component, mu_a held constant (its branch of the gradient vanishes:
+     * d loss / d mu_a = -2 w_pde / N sum r_a u_a = 0):
+     *   d/du_a     = rb_a (V + 3 g_aa u_a^2 + g_ab u_b^2 - mu_a) + rb_b 2 g_ab u_a u_b + 4 w_norm (I_a - n_a) dx u_a
+     *   d/d(lap u_a) = -c rb_a ;  first-derivative seeds 0
+     * gamma, complex_psi, omega_rot, base_mode, envelope, w_sym, w_orth, w_riesz, lambda_kind, the regularisers and residual blocks do
+     * not combine with a mixture: gpe_create refuses them.  Quadrature weights, merged boundary rows, the samplers, the pre-training
+     * step, gpe_run and the data-parallel entry points work as for any n_out = 2 network; (num_2, den_2) travel in slots 10, 11 of the
+     * first exchange message.  gpe_scalars reports component 1 (mu, num, den, integral) and norm = sum_a (I_a - n_a)^2; component 2 is
+     * read with gpe_mixture_scalars.  The three fields were appended without a change of GPE_ABI_VERSION: a binding verifies its layout
+     * against gpe_sizeof_config(), and a zero-filled tail means "no mixture". */
+    int32_t mixture;
+    float mix_g[3];               /* g_11, g_22, g_12 */
+    float mix_norm[2];            /* target norms n_1, n_2 (> 0) */
 } gpe_config;
 
 /* Per-step scalars (refine/...:364-381 keeps loss every 10 and lambda every 100 epochs). */
@@ -435,6 +452,12 @@ int gpe_mse_loss_grad(gpe_engine* e, double* loss);
 
 /* ---- continuation knobs: the gamma / perturbation loop of refine/...:289-340 -------------------------- */
 int gpe_set_gamma(gpe_engine* e, float gamma);
+/* mixture engines: the coupling matrix (g_11, g_22, g_12) of the NEXT step (gamma-continuation), like gpe_set_gamma: takes effect at the
+ * next enqueued step, a captured graph is rebuilt.  GPE_ERR_STATE: not a mixture engine; GPE_ERR_INVALID: a non-finite coupling. */
+int gpe_set_mixture(gpe_engine* e, float g11, float g22, float g12);
+/* synchronise; out = (mu_1, mu_2, I_1, I_2, num_1, den_1, num_2, den_2) of the last completed step or gpe_residual (the numbers its
+ * gpe_scalars record was formed from; over all ranks in a data-parallel step).  GPE_ERR_STATE: not a mixture engine. */
+int gpe_mixture_scalars(gpe_engine* e, double out[8]);
 int gpe_set_power(gpe_engine* e, int p);
 int gpe_set_lr(gpe_engine* e, float lr);
 int gpe_set_perturb_scale(gpe_engine* e, float s);
