@@ -3249,7 +3249,18 @@ int gpe_step(gpe_engine* e, gpe_scalars* out) {
     return GPE_OK;
 }
 
-// Everything a captured step bakes into its kernel nodes: physics and optimiser constants, batch geometry and pointers.
+// Everything a captured step bakes into its kernel nodes: physics and optimiser constants, batch geometry and pointers.  A replay is valid
+// while this key is unchanged, so whatever a capture freezes must be in it or follow from something that is.  Checklist for a new field:
+//   by-value arguments    Phys and OptCfg whole (every loss weight, gamma, p, n_global / W, n_orth, the mixture couplings), base_norm, the
+//                         boundary count handed to the update (follows from bc.n / main.n and pts.na)
+//   pointers              per batch the point, potential, output, head and activation buffers listed below; S[], Z0 / Z1, A2 and ld are
+//                         allocated by setup_batch together with O, Ob, A0 and A1 and for the same (n, C), so they move only when those do;
+//                         gslab, Wpk / WpkT and head_slots are allocated once at gpe_create; bc_target, grad, dbl, wq, orth_host[] (caller
+//                         arrays, frozen states, the precomputed base)
+//   host-side branches    head in the forward kernel or not and seeds in the reverse kernel or not (n, wq, Phys), boundary rows merged or
+//                         forked to the side stream (main.pts.b, bc.n), weighted or unweighted head / seed kernels (wq)
+// Device-resident state (parameters, Adam moments, OptDev, the contents of any bound array) is read afresh by every replay and needs no
+// entry.  A new setter or bind gets its row in tests/live_table.py, which runs a live capture against it on every kernel family.
 static std::vector<char> graph_key_of(gpe_engine* e) {
     std::vector<char> k;
     auto put = [&](const void* p, size_t n) { const char* c = (const char*)p; k.insert(k.end(), c, c + n); };
