@@ -658,6 +658,12 @@ struct gpe_engine {
     float* smp_edges = nullptr;                       // [sum_k shape[k] + 1]; axis k starts at smp_edge_off[k]
     int64_t smp_edge_off[3] = {0, 0, 0};
     float* smp_q = nullptr;                           // [smp_n] cell volumes; wq points here while the graded sampler is bound
+    // residual-adaptive sampler (gpe_sampler_adaptive): a graded sampler whose cells are blocks of varying row counts (smp_graded is
+    // set too: edges, weights and their lifetime are the graded sampler's); every buffer is allocated at the bind
+    bool smp_adaptive = false;
+    AdaptiveDev smp_ad = {};                          // mass [B + 1], count [B], off [B + 1], vol [B] and the allocation's constants
+    float* smp_vol = nullptr;                         // (smp_ad.vol, writable)
+    float* smp_resid = nullptr;                       // [smp_n][n_out]: the residual of the set held, written by the detour before a redraw
     // per-point quadrature weights (gpe_bind_weights): every collocation sum takes q_i, every N of a mean becomes W (Phys::n_global)
     const float* wq = nullptr;                        // [n_pde]: the caller's array, or smp_q; NULL: unweighted
     double wq_local = 0.0, wq_total = 0.0;            // sum of this rank's weights / W over all ranks
@@ -1901,7 +1907,7 @@ void gpe_destroy(gpe_engine* e) {
     for (int k = 0; k < GPE_MAX_ORTH; ++k) orth_state_free(e->ost[k]);
     for (hipEvent_t ev : e->ev_pool) (void)hipEventDestroy(ev);
     if (e->ext_exchange) { e->grad = nullptr; e->dbl = nullptr; }
-    void* ps[] = {e->theta, e->am, e->av, e->grad, e->dbl, e->od, e->hist, e->last, (void*)e->orth_dev, e->Wpk, e->WpkT, e->gslab, e->gslab_bc, e->grad_bc, (void*)e->upd_snap, (void*)e->head_slots, (void*)e->upd_ticket, (void*)e->upd_snap_small, (void*)e->obs_buf, (void*)e->obs_out, (void*)e->mon_ring, (void*)e->smp_x, (void*)e->theta_best, (void*)e->keep_dev, (void*)e->smp_edges, (void*)e->smp_q, (void*)e->wq_red};
+    void* ps[] = {e->theta, e->am, e->av, e->grad, e->dbl, e->od, e->hist, e->last, (void*)e->orth_dev, e->Wpk, e->WpkT, e->gslab, e->gslab_bc, e->grad_bc, (void*)e->upd_snap, (void*)e->head_slots, (void*)e->upd_ticket, (void*)e->upd_snap_small, (void*)e->obs_buf, (void*)e->obs_out, (void*)e->mon_ring, (void*)e->smp_x, (void*)e->theta_best, (void*)e->keep_dev, (void*)e->smp_edges, (void*)e->smp_q, (void*)e->wq_red, (void*)e->smp_ad.mass, (void*)e->smp_ad.count, (void*)e->smp_ad.off, (void*)e->smp_ad.share, (void*)e->smp_vol, (void*)e->smp_resid};
     for (void* p : ps) if (p) (void)hipFree(p);
     delete e;
 }
@@ -2062,6 +2068,15 @@ static void graded_free(gpe_engine* e) {         // the graded sampler's edges a
     if (e->smp_edges) { (void)hipFree(e->smp_edges); e->smp_edges = nullptr; }
     if (e->smp_q) { (void)hipFree(e->smp_q); e->smp_q = nullptr; }
     e->smp_graded = false;
+    // ... and what the adaptive sampler adds to them
+    if (e->smp_ad.mass) (void)hipFree(e->smp_ad.mass);
+    if (e->smp_ad.count) (void)hipFree(e->smp_ad.count);
+    if (e->smp_ad.off) (void)hipFree(e->smp_ad.off);
+    if (e->smp_ad.share) (void)hipFree(e->smp_ad.share);
+    if (e->smp_vol) { (void)hipFree(e->smp_vol); e->smp_vol = nullptr; }
+    if (e->smp_resid) { (void)hipFree(e->smp_resid); e->smp_resid = nullptr; }
+    e->smp_ad = AdaptiveDev{};
+    e->smp_adaptive = false;
 }
 static void sampler_clear(gpe_engine* e) {       // the stream is idle (callers synchronise first)
     if (e->smp_x) { (void)hipFree(e->smp_x); e->smp_x = nullptr; }
@@ -2072,7 +2087,13 @@ static void sampler_clear(gpe_engine* e) {       // the stream is idle (callers 
 // draw `draw` into the point buffer (and the [x ; -x] batch) on the engine's stream; nothing synchronises
 // (with_weights: the graded sampler's bind, which writes the cell volumes too -- they do not depend on the draw)
 static int sampler_launch(gpe_engine* e, int64_t draw, bool with_weights = false) {
-    if (e->smp_graded) {
+    if (e->smp_adaptive) {                       // counts and offsets from the masses in smp_ad.mass (all zero at the bind), then rows and weights
+        const float* ed = e->smp_edges;
+        hipLaunchKernelGGL(k_adaptive_alloc, dim3(1), dim3(SMP_AD_THREADS), 0, e->stream, e->smp_ad);
+        hipLaunchKernelGGL(k_sampler_draw_adaptive, dim3(cdiv(e->smp_n, SMP_THREADS)), dim3(SMP_THREADS), 0, e->stream, e->smp_grid,
+                           ed + e->smp_edge_off[0], ed + e->smp_edge_off[1], ed + e->smp_edge_off[2], e->smp_ad, (uint64_t)draw,
+                           e->smp_x, e->smp_q);
+    } else if (e->smp_graded) {
         const float* ed = e->smp_edges;
         hipLaunchKernelGGL(k_sampler_draw_graded, dim3(cdiv(e->smp_n, SMP_THREADS)), dim3(SMP_THREADS), 0, e->stream, e->smp_grid,
                            ed + e->smp_edge_off[0], ed + e->smp_edge_off[1], ed + e->smp_edge_off[2], e->smp_first, e->smp_n, (uint64_t)draw,
@@ -2087,6 +2108,27 @@ static int sampler_launch(gpe_engine* e, int64_t draw, bool with_weights = false
     return orth_refill(e);                       // frozen orthogonality states: psi_k of the new set, before the step's first kernel
 }
 
+// The adaptive sampler's detour, enqueued directly before a redraw: the PDE residual of the current parameters on the set held now, with
+// that set's weights, by the launches of gpe_residual up to its seed kernel (k_begin, forward without stored activations, k_head_pde,
+// k_seed_pde without seeds), then the block masses.  It writes the step accumulators, the gradient buffers k_begin zeroes and the
+// collocation batch's forward buffers -- all of which the step behind it starts by zeroing (acc_clean is false: sampler_before_step;
+// a captured graph always starts with k_begin) or overwriting -- and never the parameters, the optimiser state, the scheduler,
+// history, `last` or the stop flag: k_update is not launched.  Nothing synchronises or allocates.
+static int launch_head_pde(gpe_engine* e);
+static int launch_seed_pde(gpe_engine* e, float* d_resid, int want_seeds, int head_slots);
+static int adaptive_masses(gpe_engine* e) {
+    int rc;
+    if ((rc = launch_begin(e, /*force=*/true))) return rc;
+    if ((rc = mlp_forward(e, e->main, false))) return rc;
+    if ((rc = launch_head_pde(e))) return rc;
+    if ((rc = launch_seed_pde(e, e->smp_resid, 0, /*head_slots=*/0))) return rc;
+    const unsigned g = (unsigned)std::min<int64_t>(cdiv((int64_t)e->smp_ad.B, 4), (int64_t)e->num_cu * 4);
+    hipLaunchKernelGGL(k_block_mass, dim3(g), dim3(SMP_MASS_THREADS), 0, e->stream, (const float*)e->smp_resid, (const float*)e->smp_q,
+                       (const int32_t*)e->smp_ad.off, e->nd.n_out, (int)e->smp_ad.B, e->smp_ad.mass);
+    HIPCHK(e, hipGetLastError());
+    return GPE_OK;
+}
+
 // before the first kernel of a step: the set this step runs on.  A redraw leaves the engine as gpe_bind_points of the new set would
 // (the step starts with k_begin; Phys and the merged-boundary Pts depend on the point count and the pointers only, which stay) --
 // without that call's two synchronisations.
@@ -2095,6 +2137,8 @@ static int sampler_before_step(gpe_engine* e, bool capturing) {
     const int64_t want = e->smp_draw0 + e->smp_steps / e->smp_every;
     if (want == e->smp_held) return GPE_OK;
     e->acc_clean = false;
+    int rc;
+    if (e->smp_adaptive && (rc = adaptive_masses(e))) return rc;
     return sampler_launch(e, want);
 }
 
@@ -2114,8 +2158,11 @@ static int weights_total(gpe_engine* e, const float* d_q, int64_t n, double* tot
 }
 
 // edges == NULL: the uniform grid of gpe_bind_sampler; else the graded grid of gpe_bind_sampler_graded (one host array per used axis)
-static int bind_sampler_impl(gpe_engine* e, const gpe_sampler_spec* sp, const float* const* edges) {
-    const char* who = edges ? "bind_sampler_graded" : "bind_sampler";
+struct AdaptiveArgs { int64_t n_points; int32_t n_min, s; };
+// ad != NULL (with edges): the residual-adaptive sampler of gpe_sampler_adaptive -- the cells are blocks, the buffer holds ad->n_points rows
+static int bind_sampler_impl(gpe_engine* e, const gpe_sampler_spec* sp, const float* const* edges, const AdaptiveArgs* ad = nullptr) {
+    const char* who = ad ? "sampler_adaptive" : edges ? "bind_sampler_graded" : "bind_sampler";
+    if (ad && e->comm) FAIL(e, GPE_ERR_STATE, "%s: the engine has a communicator, and a data-parallel allocation needs a mass exchange", who);
     const int dim = e->nd.dim;
     if (e->cfg.potential == GPE_POT_PRECOMPUTED) FAIL(e, GPE_ERR_INVALID, "%s: a precomputed potential lives on fixed points", who);
     if (precomputed_base(e)) FAIL(e, GPE_ERR_INVALID, "%s: a precomputed base lives on fixed points", who);
@@ -2135,6 +2182,15 @@ static int bind_sampler_impl(gpe_engine* e, const gpe_sampler_spec* sp, const fl
     }
     if (sp->first_cell < 0 || sp->n_local <= 0 || (double)sp->first_cell + (double)sp->n_local > cells)
         FAIL(e, GPE_ERR_INVALID, "%s: cells [%lld, %lld + %lld) outside the grid's %.0f", who, (long long)sp->first_cell, (long long)sp->first_cell, (long long)sp->n_local, cells);
+    const int64_t n_rows = ad ? ad->n_points : sp->n_local;
+    if (ad) {
+        if (sp->first_cell != 0 || (double)sp->n_local != cells)
+            FAIL(e, GPE_ERR_INVALID, "%s: single-rank, first_cell must be 0 and n_local the block count %.0f", who, cells);
+        if (ad->n_points <= 0 || ad->n_points > SMP_AD_MAX_POINTS) FAIL(e, GPE_ERR_INVALID, "%s: n_points = %lld, need 1 .. 2^22", who, (long long)ad->n_points);
+        if (ad->n_min < 1 || (double)sp->n_local * (double)ad->n_min > (double)ad->n_points)
+            FAIL(e, GPE_ERR_INVALID, "%s: %lld blocks of at least n_min = %d rows do not fit %lld points", who, (long long)sp->n_local, ad->n_min, (long long)ad->n_points);
+        if (ad->s < 1 || ad->s > 1024) FAIL(e, GPE_ERR_INVALID, "%s: uniform_per_1024 = %d, need 1 .. 1024", who, ad->s);
+    }
     // graded grid: strictly increasing finite edges that start at lo and end at hi; W = product over the axes of the fp64 sums, in index
     // order, of the fp32 widths -- of the WHOLE grid, whichever block of cells this rank holds
     double w_grid = 1.0;
@@ -2155,13 +2211,31 @@ static int bind_sampler_impl(gpe_engine* e, const gpe_sampler_spec* sp, const fl
             n_edges += sp->shape[k] + 1;
         }
     }
+    // adaptive: the block volumes as k_sampler_draw_graded forms a cell's (fp32 widths, rounded fp32 products in axis order), and the
+    // volume shares must not all truncate to zero (K_B > 0 in k_adaptive_alloc)
+    std::vector<float> vol;
+    if (ad) {
+        vol.resize((size_t)sp->n_local);
+        uint64_t kv_sum = 0;
+        for (int64_t b = 0; b < sp->n_local; ++b) {
+            int64_t rest = b, ik[3] = {0, 0, 0};
+            for (int k = dim - 1; k >= 0; --k) { ik[k] = rest % sp->shape[k]; rest /= sp->shape[k]; }
+            float v = edges[0][ik[0] + 1] - edges[0][ik[0]];
+            for (int k = 1; k < dim; ++k) { const float w = edges[k][ik[k] + 1] - edges[k][ik[k]]; v = v * w; }
+            vol[(size_t)b] = v;
+            const double share = (double)v / w_grid * 0x1p30;
+            if (share >= 0.0 && share <= 0x1p31) kv_sum += (uint64_t)share;
+        }
+        if (!(w_grid > 0.0) || !__builtin_isfinite(w_grid) || kv_sum == 0)
+            FAIL(e, GPE_ERR_INVALID, "%s: the block volumes underflow or overflow fp32", who);
+    }
     HIPCHK(e, hipStreamSynchronize(e->stream));
     if (e->side) HIPCHK(e, hipStreamSynchronize(e->side));
-    if (e->smp_n != sp->n_local || !e->smp_x) {      // same size: the buffer (and a captured graph's pointers) stay
+    if (e->smp_n != n_rows || !e->smp_x) {      // same size: the buffer (and a captured graph's pointers) stay
         float* p = nullptr;
-        if (hipMalloc((void**)&p, (size_t)sp->n_local * dim * sizeof(float) + 256) != hipSuccess) {
+        if (hipMalloc((void**)&p, (size_t)n_rows * dim * sizeof(float) + 256) != hipSuccess) {
             (void)hipGetLastError();
-            FAIL(e, GPE_ERR_NOMEM, "%s: no memory for %lld points", who, (long long)sp->n_local);
+            FAIL(e, GPE_ERR_NOMEM, "%s: no memory for %lld points", who, (long long)n_rows);
         }
         sampler_clear(e);
         e->smp_x = p;
@@ -2177,7 +2251,7 @@ static int bind_sampler_impl(gpe_engine* e, const gpe_sampler_spec* sp, const fl
     int rc = GPE_OK;
     if (edges) {
         if (hipMalloc((void**)&e->smp_edges, (size_t)n_edges * sizeof(float) + 256) != hipSuccess ||
-            hipMalloc((void**)&e->smp_q, (size_t)sp->n_local * sizeof(float) + 256) != hipSuccess) {
+            hipMalloc((void**)&e->smp_q, (size_t)n_rows * sizeof(float) + 256) != hipSuccess) {
             (void)hipGetLastError();
             e->err = std::string(who) + ": no memory for the edges and weights"; rc = GPE_ERR_NOMEM;
         }
@@ -2193,7 +2267,26 @@ static int bind_sampler_impl(gpe_engine* e, const gpe_sampler_spec* sp, const fl
         }
         e->smp_graded = !rc;
     }
-    e->smp_n = sp->n_local; e->smp_first = sp->first_cell; e->smp_every = sp->every; e->smp_draw0 = sp->draw0; e->smp_steps = 0;
+    if (ad && !rc) {                             // masses (all zero: the bind allocates by volume), counts, offsets, volumes, residual
+        const size_t B = (size_t)sp->n_local;
+        AdaptiveDev& a = e->smp_ad;
+        if (hipMalloc((void**)&a.mass, (B + 1) * sizeof(double) + 256) != hipSuccess ||
+            hipMalloc((void**)&a.count, B * sizeof(int32_t) + 256) != hipSuccess ||
+            hipMalloc((void**)&a.off, (B + 1) * sizeof(int32_t) + 256) != hipSuccess ||
+            hipMalloc((void**)&a.share, B * sizeof(uint64_t) + 256) != hipSuccess ||
+            hipMalloc((void**)&e->smp_vol, B * sizeof(float) + 256) != hipSuccess ||
+            hipMalloc((void**)&e->smp_resid, (size_t)n_rows * e->nd.n_out * sizeof(float) + 256) != hipSuccess) {
+            (void)hipGetLastError();
+            e->err = std::string(who) + ": no memory for the block masses, counts and the residual"; rc = GPE_ERR_NOMEM;
+        } else if (hipMemset(a.mass, 0, (B + 1) * sizeof(double)) != hipSuccess ||
+                   hipMemcpy(e->smp_vol, vol.data(), B * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipGetLastError();
+            e->err = std::string(who) + ": upload of the block volumes failed"; rc = GPE_ERR_HIP;
+        }
+        a.vol = e->smp_vol; a.B = (int32_t)B; a.N = (int32_t)n_rows; a.n_min = ad->n_min; a.s = ad->s; a.V = w_grid;
+        e->smp_adaptive = !rc;
+    }
+    e->smp_n = n_rows; e->smp_first = sp->first_cell; e->smp_every = sp->every; e->smp_draw0 = sp->draw0; e->smp_steps = 0;
     e->smp_held = sp->draw0;
     if (e->mse_target) { e->mse_target = nullptr; free_batch(e->mse); }      // a pre-training target lived on the points that just went
     if (!rc) rc = bind_points_impl(e, e->smp_x, e->smp_n, nullptr);      // allocates the symmetry batch; its copy kernel reads a buffer ...
@@ -2243,6 +2336,35 @@ int gpe_bind_sampler_graded(gpe_engine* e, const gpe_sampler_spec* sp, const flo
     if (!sp) FAIL(e, GPE_ERR_INVALID, "bind_sampler_graded: no spec (gpe_bind_sampler(NULL) clears a sampler of either kind)");
     const float* edges[3] = {h_edges0, h_edges1, h_edges2};
     return bind_sampler_impl(e, sp, edges);
+}
+
+int gpe_sampler_adaptive(gpe_engine* e, const gpe_sampler_spec* sp, const float* h_edges0, const float* h_edges1, const float* h_edges2,
+                         int64_t n_points, int32_t n_min, int32_t uniform_per_1024) {
+    if (!e) return GPE_ERR_INVALID;
+    if (!sp) FAIL(e, GPE_ERR_INVALID, "sampler_adaptive: no spec (gpe_bind_sampler(NULL) clears a sampler of any kind)");
+    const float* edges[3] = {h_edges0, h_edges1, h_edges2};
+    const AdaptiveArgs ad{n_points, n_min, uniform_per_1024};
+    return bind_sampler_impl(e, sp, edges, &ad);
+}
+
+int gpe_sampler_adaptive_blocks(gpe_engine* e, int64_t* n_blocks, int64_t* n_points) {
+    if (!e) return GPE_ERR_INVALID;
+    if (!e->smp_adaptive) FAIL(e, GPE_ERR_STATE, "sampler_adaptive_blocks: no adaptive sampler bound");
+    if (n_blocks) *n_blocks = e->smp_ad.B;
+    if (n_points) *n_points = e->smp_ad.N;
+    return GPE_OK;
+}
+
+int gpe_sampler_adaptive_state(gpe_engine* e, double* h_mass, double* mass_total, int32_t* h_count, int64_t* draw) {
+    if (!e) return GPE_ERR_INVALID;
+    if (!e->smp_adaptive) FAIL(e, GPE_ERR_STATE, "sampler_adaptive_state: no adaptive sampler bound");
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    const size_t B = (size_t)e->smp_ad.B;
+    if (h_mass) HIPCHK(e, hipMemcpy(h_mass, e->smp_ad.mass, B * sizeof(double), hipMemcpyDeviceToHost));
+    if (mass_total) HIPCHK(e, hipMemcpy(mass_total, e->smp_ad.mass + B, sizeof(double), hipMemcpyDeviceToHost));
+    if (h_count) HIPCHK(e, hipMemcpy(h_count, e->smp_ad.count, B * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (draw) *draw = e->smp_held;
+    return GPE_OK;
 }
 
 int gpe_bind_weights(gpe_engine* e, const float* d_q, double w_total) {
@@ -3032,6 +3154,7 @@ int gpe_comm_unique_id(gpe_engine* e, void* out128) {
 int gpe_comm_init(gpe_engine* e, const void* id128, int rank, int world) {
     if (!e || !id128 || world < 1 || rank < 0 || rank >= world) return GPE_ERR_INVALID;
     if (e->comm) FAIL(e, GPE_ERR_STATE, "communicator already initialised");
+    if (e->smp_adaptive) FAIL(e, GPE_ERR_STATE, "comm_init: an adaptive sampler is bound, and a data-parallel allocation needs a mass exchange");
     if (world != (e->cfg.world_size > 0 ? e->cfg.world_size : 1))
         FAIL(e, GPE_ERR_INVALID, "comm world %d != gpe_config.world_size %d", world, e->cfg.world_size);
     int rc = rccl_load(e);
@@ -3166,6 +3289,7 @@ int gpe_comm_set_async(gpe_engine* e, int on) {
 
 int gpe_step_dp(gpe_engine* e) {
     if (!e) return GPE_ERR_INVALID;
+    if (e->smp_adaptive) FAIL(e, GPE_ERR_STATE, "gpe_step_dp: the adaptive sampler is single-rank");
     if (!e->comm) FAIL(e, GPE_ERR_STATE, "gpe_step_dp before gpe_comm_init");
     if (e->async_grad) return step_dp_async(e);
     int rc;
@@ -3192,6 +3316,7 @@ int gpe_step_dp(gpe_engine* e) {
 }
 
 int gpe_run_dp(gpe_engine* e, int64_t n_steps) {
+    if (e && e->smp_adaptive) FAIL(e, GPE_ERR_STATE, "gpe_run_dp: the adaptive sampler is single-rank");
     for (int64_t i = 0; i < n_steps; ++i) {
         int rc = gpe_step_dp(e);
         if (rc) return rc;

@@ -432,6 +432,47 @@ class Engine:
         self._keep.pop("q", None)
         self.n_local = int(sp.n_local)
 
+    def bind_sampler_adaptive(self, edges, n_points: int, every: int, seed: int = 0, n_min: int = 1, uniform_share: float = 0.5,
+                              clip=None, draw0: int = 0):
+        """Residual-adaptive sampler: the cells bounded by `edges` (as for bind_sampler_graded) are blocks that share `n_points` rows
+        among themselves anew at every redraw -- a share `uniform_share` in (0, 1] (kept as round(1024 * share) / 1024) by volume, the
+        rest by the block's residual mass sum q r^2 of the state being trained, at least `n_min` rows each -- every row a uniformly
+        placed point of its block with weight volume / rows (total = the grid's volume, so set cfg.dx = 1).  The bind allocates by
+        volume.  sampler.adaptive_counts / adaptive_points / adaptive_weights rebuild counts, points and weights on the CPU, bit for
+        bit, from adaptive_state().  Single-rank."""
+        from . import sampler
+        ed = sampler._edges(edges)
+        d = len(ed)
+        sp = capi.gpe_sampler_spec()          # what the engine cannot honour it refuses itself (GPE_ERR_INVALID): nothing is judged here
+        clo = [float(a[0]) for a in ed] if clip is None else [float(v) for v in sampler._per_axis(clip[0], d, "clip[0]")]
+        chi = [float(a[-1]) for a in ed] if clip is None else [float(v) for v in sampler._per_axis(clip[1], d, "clip[1]")]
+        total = 1
+        for k in range(d):
+            sp.shape[k] = ed[k].size - 1
+            sp.lo[k], sp.hi[k], sp.clip_lo[k], sp.clip_hi[k] = float(ed[k][0]), float(ed[k][-1]), clo[k], chi[k]
+            total *= ed[k].size - 1
+        sp.seed = int(seed) & (2 ** 64 - 1)
+        sp.first_cell, sp.n_local = 0, total
+        sp.draw0, sp.every = int(draw0), int(every)
+        ptrs = [ed[k].ctypes.data_as(C.c_void_p) if k < d else None for k in range(3)]
+        self._chk(self.lib.gpe_sampler_adaptive(self._h, C.byref(sp), *ptrs, int(n_points), int(n_min),
+                                                sampler.uniform_per_1024(uniform_share)))
+        self._keep["x"], self._keep["V"] = None, None
+        self._keep.pop("q", None)
+        self.n_local = int(n_points)
+
+    def adaptive_state(self) -> dict:
+        """dict(mass, total, counts, draw): the block masses (float64 [B]) and their total that produced the counts (int32 [B]) of the
+        set the adaptive sampler holds now -- zeros after the bind -- and that set's draw index; synchronises."""
+        nb = C.c_int64()
+        self._chk(self.lib.gpe_sampler_adaptive_blocks(self._h, C.byref(nb), None))       # the engine's own B sizes the host arrays
+        B = int(nb.value)
+        mass, counts = np.zeros(B, np.float64), np.zeros(B, np.int32)
+        tot, d = C.c_double(), C.c_int64()
+        self._chk(self.lib.gpe_sampler_adaptive_state(self._h, mass.ctypes.data_as(C.c_void_p), C.byref(tot),
+                                                      counts.ctypes.data_as(C.c_void_p), C.byref(d)))
+        return dict(mass=mass, total=tot.value, counts=counts, draw=int(d.value))
+
     def bind_boundary(self, xb, target=None):
         if xb is None:
             self._chk(self.lib.gpe_bind_boundary(self._h, None, 0, None))

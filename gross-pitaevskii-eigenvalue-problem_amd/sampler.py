@@ -191,3 +191,104 @@ def sinh_edges(half, cells, stretch):
     e = (half * r).astype(np.float32) * np.sign(t).astype(np.float32)
     e[0], e[-1] = -np.float32(half), np.float32(half)
     return e
+
+
+# ---- residual-adaptive allocation (csrc/gpe_sampler.h: k_adaptive_alloc / k_sampler_draw_adaptive, include/gpe_hip.h: gpe_sampler_adaptive)
+# The cells of a graded grid are BLOCKS that share N rows: block b holds rows [off_b, off_{b+1}), off the exclusive prefix sum of the
+# counts.  The counts come from the block masses m_b (sum q r^2 of the PDE residual over the block's rows, formed on the device) and the
+# block volumes v_b through two fp64 divisions per block and integers behind them, so Python's own integers restate them exactly:
+#   ok = 0 < M < inf;  kA_b = ok ? floor(m_b / M * 2^30) : 0;  kV_b = floor(double(v_b) / V * 2^30);  k_b = (1024 - s) kA_b + s kV_b
+#   K = exclusive prefix sum of k;  R = N - B n_min;  n_b = n_min + (K_{b+1} R) // K_B - (K_b R) // K_B
+# Row j of block b has local index l = j - off_b; Philox counter (b, l, draw lo, draw hi) -- not the (cell lo, cell hi, ...) of the
+# graded sampler: the two layouts meet only in local index 0 (so with one row per block the set equals graded_points) -- and weight float32(double(v_b) / n_b).
+
+ADAPTIVE_MAX_POINTS = 1 << 22
+
+
+def uniform_per_1024(share: float) -> int:
+    """The share of the rows always allocated by volume, in (0, 1], as the engine's integer s = round(1024 * share) in [1, 1024]."""
+    s = int(round(1024.0 * float(share)))
+    if not 0.0 < float(share) <= 1.0 or not 1 <= s <= 1024:
+        raise ValueError("uniform_share: in (0, 1], and at least 1 / 2048")
+    return s
+
+
+def adaptive_counts(mass, total, edges, n_points: int, n_min: int = 1, uniform_per_1024: int = 512) -> np.ndarray:
+    """Rows per block, int32 [B]: mass float64 [B] and total as Engine.adaptive_state() reports them (mass None: the bind's allocation by
+    volume, which is also what total = 0, NaN or inf gives), the blocks bounded by `edges`, n_points rows in all, at least n_min per
+    block, uniform_per_1024 in [1, 1024] of 1024 parts allocated by volume.  Exact integer arithmetic behind two fp64 divisions per block."""
+    v = graded_weights(edges).astype(np.float64)
+    V = graded_total(edges)
+    B, N, n_min, s = v.size, int(n_points), int(n_min), int(uniform_per_1024)
+    if not 1 <= N <= ADAPTIVE_MAX_POINTS or n_min < 1 or B * n_min > N or not 1 <= s <= 1024:
+        raise ValueError("adaptive_counts: 1 <= n_points <= 2^22, n_min >= 1, B * n_min <= n_points, 1 <= uniform_per_1024 <= 1024")
+    M = 0.0 if mass is None else float(total)
+    ok = M > 0.0 and M < np.inf
+    kV = np.floor(v / V * 2.0 ** 30)
+    kA = np.zeros(B)
+    if mass is not None:
+        m = np.asarray(mass, dtype=np.float64).ravel()
+        if m.size != B:
+            raise ValueError(f"adaptive_counts: one mass per block ({B})")
+        ok = ok and bool(np.all(np.isfinite(m)))          # (the engine's total of masses with a NaN or inf among them is not finite)
+        if ok:
+            kA = np.floor(m / M * 2.0 ** 30)
+    R = N - B * n_min
+    K, ks = 0, []
+    for a, b in zip(kA, kV):
+        ks.append((1024 - s) * int(a) + s * int(b))          # Python integers from here on
+    KB = sum(ks)
+    if KB <= 0:
+        raise ValueError("adaptive_counts: the volume shares all truncate to zero")
+    assert KB * R < 2 ** 63
+    out = np.empty(B, dtype=np.int32)
+    for i, k in enumerate(ks):
+        out[i] = n_min + ((K + k) * R) // KB - (K * R) // KB
+        K += k
+    return out
+
+
+def _adaptive_rows(ed, counts):
+    counts = np.asarray(counts, dtype=np.int64).ravel()
+    shape = tuple(a.size - 1 for a in ed)
+    if counts.size != int(np.prod([int(s) for s in shape])) or np.any(counts < 1):
+        raise ValueError("counts: one count >= 1 per block")
+    b = np.repeat(np.arange(counts.size, dtype=np.int64), counts)
+    off = np.concatenate([[0], np.cumsum(counts)])
+    l = np.arange(b.size, dtype=np.int64) - off[b]
+    return counts, b, l, np.unravel_index(b, shape)
+
+
+def adaptive_points(edges, counts, seed, draw, clip=None) -> np.ndarray:
+    """Draw `draw` of the adaptive set with seed `seed` and `counts` rows per block: float32 [sum(counts), d], what
+    Engine.bind_sampler_adaptive holds while adaptive_state()['counts'] == counts."""
+    ed = _edges(edges)
+    d = len(ed)
+    counts, b, l, idx = _adaptive_rows(ed, counts)
+    clo = np.array([a[0] for a in ed], np.float32) if clip is None else _per_axis(clip[0], d, "clip[0]")
+    chi = np.array([a[-1] for a in ed], np.float32) if clip is None else _per_axis(clip[1], d, "clip[1]")
+    if np.any(chi < clo):
+        raise ValueError("clip[1] < clip[0]")
+    seed, draw = int(seed) & (2 ** 64 - 1), int(draw) & (2 ** 64 - 1)
+    ctr = np.empty((b.size, 4), dtype=np.uint64)
+    ctr[:, 0], ctr[:, 1] = b.astype(np.uint64), l.astype(np.uint64)
+    ctr[:, 2], ctr[:, 3] = draw & 0xFFFFFFFF, draw >> 32
+    r = philox4x32(ctr, np.array([seed & 0xFFFFFFFF, seed >> 32], dtype=np.uint64))
+    x = np.empty((b.size, d), dtype=np.float32)
+    for k in range(d):
+        u = (r[:, k] >> np.uint32(8)).astype(np.float32) * np.float32(2.0 ** -24)
+        lo, hi = ed[k][idx[k]], ed[k][idx[k] + 1]
+        w = hi - lo
+        xk = lo + u * w
+        xk = np.where(xk < clo[k], clo[k], xk)
+        xk = np.where(xk > chi[k], chi[k], xk)
+        x[:, k] = xk
+    return x
+
+
+def adaptive_weights(edges, counts) -> np.ndarray:
+    """float32 [sum(counts)]: every row of block b weighs float32(double(v_b) / n_b) -- one fp64 division, one conversion."""
+    ed = _edges(edges)
+    counts, b, _, _ = _adaptive_rows(ed, counts)
+    q = graded_weights(ed).astype(np.float64) / counts.astype(np.float64)
+    return q.astype(np.float32)[b]

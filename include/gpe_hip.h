@@ -329,6 +329,45 @@ int gpe_weights(gpe_engine* e, const float** d_q, int64_t* n, double* w_local, d
  * the end edges, w_sym != 0.
  * Replaces: a host loop that redraws a graded set, recomputes nothing but uploads points every K steps (no reference counterpart). */
 int gpe_bind_sampler_graded(gpe_engine* e, const gpe_sampler_spec* spec, const float* h_edges0, const float* h_edges1, const float* h_edges2);
+/* Residual-adaptive sampler: the cells of a graded grid become BLOCKS, and a buffer of n_points = N rows (a fixed count: buffers, pointers,
+ * kernel selection and a captured graph stay valid) is shared out among them anew at every redraw, by the PDE residual of the state
+ * being trained.  spec, h_edges{k} as for gpe_bind_sampler_graded; B = prod(shape) blocks, row-major, last axis fastest; v_b = the graded
+ * sampler's fp32 cell volume, V its W.  Single-rank: spec.first_cell = 0, spec.n_local = B.
+ *   rows    block b holds rows [off_b, off_{b+1}), off the exclusive prefix sum of the counts n_b; row j lies in block
+ *           b = upper_bound(off, j) - 1 with local index l = j - off_b
+ *   point   Philox4x32-10, counter (b, l, draw & 0xffffffff, draw >> 32), key as above, output word k for axis k; u, w, x = a + u * w and
+ *           the clip per axis exactly as gpe_bind_sampler_graded
+ *   weight  q = float(double(v_b) / double(n_b)) for every row of block b: one IEEE fp64 division, one conversion.  W = V, constant
+ *   masses  directly before redraw m >= 1 (enqueued before the first kernel of step m * every) the engine evaluates the residual of the
+ *           current parameters on the set it holds, with that set's weights, by the forward-only launches of gpe_residual -- without a
+ *           host synchronisation and without writing anything a step reads (optimiser state, scheduler, history, `last`, stop flag) --
+ *           and forms m_b = sum_{i in b} q_i sum_c r_{i,c}^2 and M = sum_b m_b in fp64, each in a fixed order, no atomics
+ *   counts  ok = M > 0 && M < inf;  kA_b = ok ? uint64(floor(m_b / M * 2^30)) : 0;  kV_b = uint64(floor(double(v_b) / V * 2^30));
+ *           k_b = (1024 - s) kA_b + s kV_b with s = uniform_per_1024, the share always allocated by volume (no block starves);
+ *           K the exclusive prefix sum of k;  R = N - B n_min;  n_b = n_min + (K_{b+1} R) / K_B - (K_b R) / K_B in unsigned 64-bit
+ *           integer division.  The counts add up to N exactly; a zero or non-finite mass anywhere gives the allocation by volume, and so
+ *           does the bind (draw0: all masses zero, no forward pass, nothing trained needed).
+ * gpe_pinn/sampler.py (adaptive_counts, adaptive_points, adaptive_weights) restates counts, points and weights, bit for bit.  The bind
+ * allocates every buffer (points, weights, residual, masses, counts, offsets); a redraw allocates and synchronises nothing.  Cadence,
+ * graph cutting (gpe_run), gpe_step / gpe_step_begin, gpe_sampler_points, gpe_weights (w_total = V; w_local = the sum of the bind's
+ * weights), the refill of frozen orthogonality states behind every redraw, the monitor and the keeper behave as with the graded
+ * sampler.  gpe_bind_sampler(NULL) and gpe_bind_points clear it; gpe_bind_weights returns GPE_ERR_STATE while it is bound.
+ * GPE_ERR_INVALID: whatever gpe_bind_sampler_graded refuses (w_sym != 0 included), n_points > 2^22 (the products above stay below
+ * 2^63; hence B <= 2^22), B * n_min > n_points, n_min < 1, uniform_per_1024 outside [1, 1024], first_cell != 0 or n_local != B.
+ * GPE_ERR_STATE: the engine has a communicator; with an adaptive sampler bound gpe_comm_init, gpe_step_dp and gpe_run_dp return it
+ * too (a data-parallel allocation needs a mass exchange).
+ * Replaces: a host loop of gpe_residual, a per-block sum, an allocation and gpe_bind_points + gpe_bind_weights every K steps, with
+ * its synchronisations and uploads (residual-based adaptive sampling: Wu et al. 2023; the reference trains on one fixed grid). */
+int gpe_sampler_adaptive(gpe_engine* e, const gpe_sampler_spec* spec, const float* h_edges0, const float* h_edges1, const float* h_edges2,
+                         int64_t n_points, int32_t n_min, int32_t uniform_per_1024);
+/* synchronise; the block masses h_mass [B] and their total M that produced the counts of the set held now (all zero after the bind), those
+ * counts h_count [B] and the draw index.  Host arrays; any pointer may be NULL.  GPE_ERR_STATE: no adaptive sampler bound.
+ * Replaces: the host's own record of its last allocation in the loop named above. */
+int gpe_sampler_adaptive_state(gpe_engine* e, double* h_mass /*[B]*/, double* mass_total, int32_t* h_count /*[B]*/, int64_t* draw);
+/* B and N of the adaptive sampler bound now: what a caller sizes h_mass / h_count by.  No synchronisation (both are host-side facts of
+ * the bind); either pointer may be NULL.  GPE_ERR_STATE: no adaptive sampler bound.
+ * Replaces: the caller remembering prod(shape) of its own bind. */
+int gpe_sampler_adaptive_blocks(gpe_engine* e, int64_t* n_blocks, int64_t* n_points);
 
 /* ---- forward-only entry points ---------------------------------------------------------------- */
 /* model.forward(x) (refine/...:121-125): d_out [n, out] row-major */

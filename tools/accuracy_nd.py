@@ -44,6 +44,10 @@ ap.add_argument("--device-sampler", action="store_true", help="with --resample: 
 ap.add_argument("--graded", type=float, default=None, metavar="STRETCH",
                 help="with --device-sampler: train on the GRADED sampler (Engine.bind_sampler_graded) -- the same number of cells per axis over the box, "
                      "refined towards the centre by sampler.sinh_edges(half, n, STRETCH), every point weighted by its cell volume")
+ap.add_argument("--adaptive", type=int, nargs="?", const=32, default=None, metavar="BLOCKS",
+                help="with --device-sampler: train on the residual-ADAPTIVE sampler (Engine.bind_sampler_adaptive) -- BLOCKS blocks per axis over the box "
+                     "(np.linspace edges, or with --graded STRETCH its sinh_edges), the grid's point count shared out among them anew at every redraw")
+ap.add_argument("--adaptive-share", type=float, default=0.5, help="--adaptive: the share of the rows always allocated by volume (uniform_share)")
 ap.add_argument("--big-grid", default="", help="e.g. 64,128,64: after the schedule, continue on THIS grid (BASELINE's per-GPU size) for --big-epochs epochs "
                                                "at the low end of the learning-rate ladder, and evaluate mu there (same weights, fresh Adam)")
 ap.add_argument("--big-epochs", type=int, default=3000)
@@ -80,7 +84,7 @@ flat = bench.reference_init(cs["layers"], seed=a.seed)
 cfg = gpe_pinn.GPEConfig(layers=cs["layers"], gamma=0.0, p=3, kinetic_coeff=0.5, pot_scale=0.5, omega=tuple(cs["omega"]) + (1.0,) * (3 - d),
                          dx=dv, w_bc=a.w_bc, w_norm=a.w_norm, lr=a.lr, sched=capi.SCHED_CONST, history_capacity=8,
                          w_riesz=a.w_riesz, riesz_kind=capi.RIESZ_VARIATIONAL)
-if a.graded is not None:
+if a.graded is not None or a.adaptive is not None:
     cfg.dx = 1.0                            # the quadrature weights are the cell volumes themselves (the regular grid gets weights of dv below)
 eng = gpe_pinn.Engine(cfg)
 eng.set_params(flat)
@@ -90,9 +94,13 @@ eng.bind_boundary(torch.as_tensor(xb, device="cuda"))
 # stratified collocation sets (--resample): the grid point moved uniformly inside its cell; the first and last cells of an axis stay inside the box
 xsets = [xd]
 device_sampler = a.device_sampler and a.resample > 0
-graded = a.graded is not None
-if graded and not device_sampler:
+adaptive = a.adaptive is not None
+graded = a.graded is not None and not adaptive      # (with --adaptive, --graded only shapes the block edges)
+weighted = graded or adaptive
+if a.graded is not None and not device_sampler:
     ap.error("--graded needs --device-sampler and --resample")
+if adaptive and not device_sampler:
+    ap.error("--adaptive needs --device-sampler and --resample")
 if a.resample > 0 and not device_sampler:
     rng = np.random.default_rng(1234 + a.seed)
     for _ in range(a.sets):
@@ -130,7 +138,12 @@ for i in range(a.pretrain):
         print(f"pretrain {i}: mse {sc['loss']:.3e}", flush=True)
 eng.bind_target(None)
 edges = None
-if graded:
+if adaptive:
+    from gpe_pinn.sampler import sinh_edges
+    ax_edges = sinh_edges(half, a.adaptive, a.graded) if a.graded is not None else np.linspace(-half, half, a.adaptive + 1).astype(np.float32)
+    edges = [ax_edges] * d
+    eng.bind_sampler_adaptive(edges, n_points=n ** d, every=a.resample, seed=1234 + a.seed, n_min=1, uniform_share=a.adaptive_share)
+elif graded:
     from gpe_pinn.sampler import sinh_edges
     edges = [sinh_edges(half, n, a.graded)] * d
     eng.bind_sampler_graded(edges, every=a.resample, seed=1234 + a.seed)
@@ -169,7 +182,7 @@ for si, g in enumerate(gam):
     sc = eng.read_scalars()
     if last and a.resample > 0:                 # the reported numbers: on the REGULAR grid, not on the last jittered set
         eng.bind_points(xd)
-        if graded:                          # cfg.dx is 1 in this mode: the regular grid's quadrature weight rides as a per-point weight
+        if weighted:                        # cfg.dx is 1 in this mode: the regular grid's quadrature weight rides as a per-point weight
             eng.bind_weights(torch.full((X.shape[0],), dv, device="cuda"))
         sc = eng.residual(want_fields=False)[0]
     rows.append(dict(gamma=g, epochs=ne, mu=sc["mu"], loss=sc["loss"], pde=sc["pde"], norm=sc["integral"], lr=sc["lr"], riesz=sc["riesz"]))
@@ -249,7 +262,9 @@ out = dict(case=a.case, workload=cs["workload"], layers=cs["layers"], points=int
            density_rel_l2=float(np.sqrt(((dens - dref) ** 2).sum() / (dref ** 2).sum())),
            schedule=dict(pretrain=a.pretrain, epochs=a.epochs, final=a.final, stages=a.stages, lr=a.lr, w_norm=a.w_norm, w_bc=a.w_bc,
                          w_riesz=a.w_riesz, w_norm_final=a.w_norm_final, resample=a.resample, sets=a.sets,
-                         sampler=("device_graded" if graded else "device" if device_sampler else "host_cycle") if a.resample > 0 else "fixed_grid",
+                         sampler=("device_adaptive" if adaptive else "device_graded" if graded else "device" if device_sampler else "host_cycle") if a.resample > 0 else "fixed_grid",
+                         adaptive=(dict(blocks_per_axis=a.adaptive, n_points=n ** d, n_min=1, uniform_share=a.adaptive_share,
+                                        uniform_per_1024=int(round(1024 * a.adaptive_share))) if adaptive else None),
                          graded_stretch=a.graded, graded_edges=(None if edges is None else [float(v) for v in edges[0]]),
                          scheduler="constant lr per stage, fresh Adam per stage; last stage lr x (1, 0.3, 0.1, 0.03, 0.01, 0.003, 0.001)"),
            energy=rows[-1]["riesz"], energy_ref=truth["energy"], big_grid=big, kept=kept,
