@@ -151,6 +151,8 @@ SYMBOLS = {
     "gpe_set_gamma": (_int, [_vp, _f]),
     "gpe_set_mixture": (_int, [_vp, _f, _f, _f]),
     "gpe_mixture_scalars": (_int, [_vp, _P(C.c_double)]),
+    "gpe_mixture_energy_weight": (_int, [_vp, _f]),
+    "gpe_mixture_energy": (_int, [_vp, _P(C.c_double)]),
     "gpe_set_power": (_int, [_vp, _int]),
     "gpe_set_lr": (_int, [_vp, _f]),
     "gpe_set_perturb_scale": (_int, [_vp, _f]),

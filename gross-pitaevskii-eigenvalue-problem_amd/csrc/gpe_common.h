@@ -47,12 +47,36 @@ struct Phys {
 struct MixPhys {
     int on;                          // 0: not a mixture
     float g[3], n[2];                // (g11, g22, g12), target norms (n_1, n_2)
+    float wE;                        // weight of the mixture energy term (gpe_mixture_energy_weight); 0: the plain mixture step
 };
 
 // Indices into the double "sums" exchange buffer (all-reduced over ranks between phase 1 and 2).
 enum { S_NUM = 0, S_DEN = 1, S_SYM = 2, S_ORTH0 = 3, /* ..S_ORTH0+3 */ S_RZ_K = 7, S_RZ_P = 8, S_RZ_I = 9, S_RZ_L = 10 /* <L_z> of complex psi */, S_COUNT = 12 };
 // A mixture has no rotation and no 13th sum: component 2's Rayleigh sums take the two slots behind the energy sums (component 1 keeps S_NUM, S_DEN).
 enum { S_MIX_NUM2 = 10, S_MIX_DEN2 = 11 };
+// ... and files nothing in slots 2-9 (symmetry, orthogonality, scalar energy sums): the five sums of its energy term take five of them,
+//   T_a = sum q (c |grad u_a|^2 + V u_a^2),  Q_ab = sum q u_a^2 u_b^2       (k_head_mix<..., EN = true>; S_COUNT stays 12)
+enum { S_MIX_T1 = 2, S_MIX_T2 = 3, S_MIX_Q11 = 4, S_MIX_Q22 = 5, S_MIX_Q12 = 6 };
+
+// Energy of the mixture state normalised to the target norms, v_a = u_a sqrt(n_a / I_a), from the (all-reduced) sums, in double:
+//   E = sum_a n_a T_a / den_a + 1/2 sum_ab g_ab n_a n_b Q_ab / (den_a den_b dx)
+// and the coefficients of its derivative: alpha_a = n_a / den_a, beta_aa = 1/2 g_aa n_a^2 / (den_a^2 dx), beta_12 = g_12 n_1 n_2 /
+// (den_1 den_2 dx), delta_a = dE / d den_a (include/gpe_hip.h).  One place for the update kernel, the seed kernel and the host.
+struct MixEnergy { double E, alpha[2], beta[3] /* 11, 22, 12 */, delta[2]; };
+__host__ GPE_DEV MixEnergy mix_energy_of(const float* g, const float* n, double dx, const double* sums) {
+#pragma clang fp contract(off)      // every copy (update kernel forms, seed kernel, host) rounds alike
+    const double d1 = sums[S_DEN], d2 = sums[S_MIX_DEN2], n1 = (double)n[0], n2 = (double)n[1];
+    const double T1 = sums[S_MIX_T1], T2 = sums[S_MIX_T2], Q11 = sums[S_MIX_Q11], Q22 = sums[S_MIX_Q22], Q12 = sums[S_MIX_Q12];
+    MixEnergy m;
+    m.alpha[0] = n1 / d1; m.alpha[1] = n2 / d2;
+    m.beta[0] = 0.5 * (double)g[0] * n1 * n1 / (d1 * d1 * dx);
+    m.beta[1] = 0.5 * (double)g[1] * n2 * n2 / (d2 * d2 * dx);
+    m.beta[2] = (double)g[2] * n1 * n2 / (d1 * d2 * dx);
+    m.E = m.alpha[0] * T1 + m.alpha[1] * T2 + m.beta[0] * Q11 + m.beta[1] * Q22 + m.beta[2] * Q12;
+    m.delta[0] = -(m.alpha[0] * T1 + 2.0 * m.beta[0] * Q11 + m.beta[2] * Q12) / d1;
+    m.delta[1] = -(m.alpha[1] * T2 + 2.0 * m.beta[1] * Q22 + m.beta[2] * Q12) / d2;
+    return m;
+}
 // Local (replicated, never exchanged) double scalars.
 enum { LS_BC_SE2 = 0, LS_BC_CNT = 1, LS_COUNT = 4 };
 // Tail of the float gradient exchange buffer.

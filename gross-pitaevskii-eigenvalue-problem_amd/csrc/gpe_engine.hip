@@ -170,7 +170,12 @@ GPE_DEV void update_core(int P, float* __restrict__ theta, float* __restrict__ a
         p_num = sums[S_NUM]; p_den = sums[S_DEN]; p_bcse = lsums[LS_BC_SE2]; p_sr2 = grad_load<SC1>(&grad[P + GT_SUM_R2]);
         p_lr = odr->lr; p_b1p = odr->b1p; p_b2p = odr->b2p; p_step = odr->step; p_stopped = odr->stopped;
     }
+    // mixture energy term: in the single-workgroup forms E is formed by the first thread of wave 1 ahead of the barrier below -- inside thread
+    // 0's serial section, the kernel's register peak, it cost four more spilled VGPRs and 0.7 % of the headline step
+    const bool mix_en = oc.mix.on && oc.mix.wE != 0.f;
+    __shared__ double s_mixE;
     if constexpr (!MULTI) {
+        if (mix_en && threadIdx.x == 64) s_mixE = mix_energy_of(oc.mix.g, oc.mix.n, (double)ph.dx, sums).E;
         double acc = 0.0;
         if (cached) {
 #pragma unroll
@@ -223,6 +228,11 @@ GPE_DEV void update_core(int P, float* __restrict__ theta, float* __restrict__ a
         }
         double reg = reg_terms(ph, den, lam);
         double loss = ph.w_pde * pde + ph.w_bc * bc + ph.w_norm * nrm + ph.w_sym * sym + ph.w_orth * orth + ph.w_riesz * riesz + reg;
+        if (mix_en) {        // mixture energy term: E of the state normalised to the target norms, reported as riesz
+            if constexpr (MULTI) riesz = mix_energy_of(oc.mix.g, oc.mix.n, (double)ph.dx, sums).E;
+            else riesz = s_mixE;
+            loss += (double)oc.mix.wE * riesz;
+        }
         if (mse_mode) {           // pre-training: loss = mean((NN - target)^2); plain Adam (no clip, no scheduler, no early stop)
             loss = (double)grad_load<SC1>(&grad[P + GT_MSE_SE2]) / (ph.n_global * ph.n_out);
             lam = 0.0; pde = 0.0; nrm = 0.0; bc = 0.0; sym = 0.0; orth = 0.0; riesz = 0.0; reg = 0.0;
@@ -667,6 +677,7 @@ struct gpe_engine {
     // per-point quadrature weights (gpe_bind_weights): every collocation sum takes q_i, every N of a mean becomes W (Phys::n_global)
     const float* wq = nullptr;                        // [n_pde]: the caller's array, or smp_q; NULL: unweighted
     double wq_local = 0.0, wq_total = 0.0;            // sum of this rank's weights / W over all ranks
+    float mix_wE = 0.f;                               // mixture energy term (gpe_mixture_energy_weight): its weight, 0 = the plain mixture step
     double* wq_red = nullptr;                         // [2] output of k_weight_total, allocated at the first bind
     StepState st;
     std::string err;
@@ -1453,6 +1464,7 @@ static void fill_phys(gpe_engine* e) {
     mx.on = c.mixture != 0;
     for (int k = 0; k < 3; ++k) mx.g[k] = c.mixture ? c.mix_g[k] : 0.f;
     for (int k = 0; k < 2; ++k) mx.n[k] = c.mixture ? c.mix_norm[k] : 0.f;
+    mx.wE = c.mixture ? e->mix_wE : 0.f;
 }
 
 static int reset_opt(gpe_engine* e, float lr) {
@@ -1856,7 +1868,9 @@ int gpe_active_kernels(gpe_engine* e, char* buf, size_t n) {
                   *std::max_element(e->user_layers + 1, e->user_layers + e->cfg.n_layers - 1), e->cfg.layers[1]);
     if (e->cfg.mixture) {      // a mixture always takes the standalone pair of its own (the fused head / seeds are real-psi only)
         const size_t used = strlen(buf);
-        snprintf(buf + used, n - used, ";head=k_head_mix<%d,%d%s>;seed=k_seed_mix<%d,%d%s>", b.C, b.E, e->wq ? ",weighted" : "", b.C, b.E, e->wq ? ",weighted" : "");
+        const char* wqs = e->wq ? ",weighted" : "";
+        const char* ens = e->mix_wE != 0.f ? ",energy" : "";
+        snprintf(buf + used, n - used, ";head=k_head_mix<%d,%d%s%s>;seed=k_seed_mix<%d,%d%s%s>", b.C, b.E, wqs, ens, b.C, b.E, wqs, ens);
     } else if (e->wq) {      // bound quadrature weights: head and seeds by the standalone kernels' weighted instances, whatever the batch size
         const size_t used = strlen(buf);
         snprintf(buf + used, n - used, ";head=k_head_pde<%d,%d,weighted>;seed=k_seed_pde<%d,%d,weighted>", b.C, b.E, b.C, b.E);
@@ -2114,7 +2128,7 @@ static int sampler_launch(gpe_engine* e, int64_t draw, bool with_weights = false
 // collocation batch's forward buffers -- all of which the step behind it starts by zeroing (acc_clean is false: sampler_before_step;
 // a captured graph always starts with k_begin) or overwriting -- and never the parameters, the optimiser state, the scheduler,
 // history, `last` or the stop flag: k_update is not launched.  Nothing synchronises or allocates.
-static int launch_head_pde(gpe_engine* e);
+static int launch_head_pde(gpe_engine* e, bool energy = false);
 static int launch_seed_pde(gpe_engine* e, float* d_resid, int want_seeds, int head_slots);
 static int adaptive_masses(gpe_engine* e) {
     int rc;
@@ -2862,17 +2876,27 @@ static unsigned head_grid(gpe_engine* e, int64_t n, int threads = 0) {
     return (unsigned)std::min<int64_t>(cdiv(n, threads > 0 ? threads : e->head_threads), (int64_t)e->num_cu * e->head_wg_per_cu);
 }
 
-static int launch_head_pde(gpe_engine* e) {
+// energy: a mixture's EN instance, whatever its weight (gpe_mixture_energy)
+static int launch_head_pde(gpe_engine* e, bool energy) {
     Batch& b = e->main;
     dim3 g(head_grid(e, b.n));
     const float* none = nullptr;
+    if (e->cfg.mixture && (energy || e->mix_wE != 0.f)) {
+        if (e->wq) {
+            DISPATCH_TRAIN(b, hipLaunchKernelGGL((k_head_mix<CC, EE, true, true>), g, dim3(e->head_threads), 0, e->stream, e->ph, e->oc.mix, b.pts, b.V, b.O, b.u, b.Hu,
+                                                e->sums(), b.n, b.ld, e->n_pde, e->bc_target, b.Ob, e->lsums(), e->wq, b.ux));
+        } else {
+            DISPATCH_TRAIN(b, hipLaunchKernelGGL((k_head_mix<CC, EE, false, true>), g, dim3(e->head_threads), 0, e->stream, e->ph, e->oc.mix, b.pts, b.V, b.O, b.u, b.Hu,
+                                                e->sums(), b.n, b.ld, e->n_pde, e->bc_target, b.Ob, e->lsums(), none, b.ux));
+        }
+    } else
     if (e->cfg.mixture) {
         if (e->wq) {
             DISPATCH_TRAIN(b, hipLaunchKernelGGL((k_head_mix<CC, EE, true>), g, dim3(e->head_threads), 0, e->stream, e->ph, e->oc.mix, b.pts, b.V, b.O, b.u, b.Hu,
-                                                e->sums(), b.n, b.ld, e->n_pde, e->bc_target, b.Ob, e->lsums(), e->wq));
+                                                e->sums(), b.n, b.ld, e->n_pde, e->bc_target, b.Ob, e->lsums(), e->wq, (float*)nullptr));
         } else {
             DISPATCH_TRAIN(b, hipLaunchKernelGGL((k_head_mix<CC, EE>), g, dim3(e->head_threads), 0, e->stream, e->ph, e->oc.mix, b.pts, b.V, b.O, b.u, b.Hu,
-                                                e->sums(), b.n, b.ld, e->n_pde, e->bc_target, b.Ob, e->lsums(), none));
+                                                e->sums(), b.n, b.ld, e->n_pde, e->bc_target, b.Ob, e->lsums(), none, (float*)nullptr));
         }
     } else
     if (e->wq) {      // bound quadrature weights: the weighted instance
@@ -2892,13 +2916,22 @@ static int launch_seed_pde(gpe_engine* e, float* d_resid, int want_seeds, int he
     Batch& b = e->main;
     dim3 g(head_grid(e, e->n_pde));
     const float* none = nullptr;
+    if (e->cfg.mixture && e->mix_wE != 0.f && want_seeds) {      // the seeds of the energy term ride in the EN instance
+        if (e->wq) {
+            DISPATCH_TRAIN(b, hipLaunchKernelGGL((k_seed_mix<CC, EE, true, true>), g, dim3(e->head_threads), 0, e->stream, e->ph, e->oc.mix, b.pts, b.V, b.u, b.Hu,
+                                                e->sums(), b.Ob, d_resid, e->dsc(), e->n_pde, b.ld, want_seeds, e->wq, (const float*)b.ux));
+        } else {
+            DISPATCH_TRAIN(b, hipLaunchKernelGGL((k_seed_mix<CC, EE, false, true>), g, dim3(e->head_threads), 0, e->stream, e->ph, e->oc.mix, b.pts, b.V, b.u, b.Hu,
+                                                e->sums(), b.Ob, d_resid, e->dsc(), e->n_pde, b.ld, want_seeds, none, (const float*)b.ux));
+        }
+    } else
     if (e->cfg.mixture) {      // (head_slots is 0: a mixture's head never rides in the forward kernel)
         if (e->wq) {
             DISPATCH_TRAIN(b, hipLaunchKernelGGL((k_seed_mix<CC, EE, true>), g, dim3(e->head_threads), 0, e->stream, e->ph, e->oc.mix, b.pts, b.V, b.u, b.Hu,
-                                                e->sums(), b.Ob, d_resid, e->dsc(), e->n_pde, b.ld, want_seeds, e->wq));
+                                                e->sums(), b.Ob, d_resid, e->dsc(), e->n_pde, b.ld, want_seeds, e->wq, none));
         } else {
             DISPATCH_TRAIN(b, hipLaunchKernelGGL((k_seed_mix<CC, EE>), g, dim3(e->head_threads), 0, e->stream, e->ph, e->oc.mix, b.pts, b.V, b.u, b.Hu,
-                                                e->sums(), b.Ob, d_resid, e->dsc(), e->n_pde, b.ld, want_seeds, none));
+                                                e->sums(), b.Ob, d_resid, e->dsc(), e->n_pde, b.ld, want_seeds, none, none));
         }
     } else
     if (e->wq) {      // bound quadrature weights: the weighted instance (the head never rode in the forward kernel: head_class)
@@ -3521,6 +3554,34 @@ int gpe_mixture_scalars(gpe_engine* e, double out[8]) {
     HIPCHK(e, hipMemcpyAsync(&h, e->od, sizeof h, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));
     for (int k = 0; k < 8; ++k) out[k] = h.mix[k];
+    return GPE_OK;
+}
+int gpe_mixture_energy_weight(gpe_engine* e, float w_E) {
+    if (!e) return GPE_ERR_INVALID;
+    if (!e->cfg.mixture) FAIL(e, GPE_ERR_STATE, "mixture_energy_weight: not a mixture engine (gpe_config.mixture)");
+    if (!__builtin_isfinite(w_E) || w_E < 0.f) FAIL(e, GPE_ERR_INVALID, "mixture_energy_weight: the weight must be finite and >= 0");
+    e->mix_wE = w_E; fill_phys(e); return GPE_OK;
+}
+// Forward-only detour on the bound set, like gpe_residual: value and first-derivative jets, the EN head, no seeds; parameters, optimiser
+// state and the last record stay.  The step behind it starts by zeroing the sums filed here (acc_clean is false).
+int gpe_mixture_energy(gpe_engine* e, double out[8]) {
+    if (!e || !out) return GPE_ERR_INVALID;
+    if (!e->cfg.mixture) FAIL(e, GPE_ERR_STATE, "mixture_energy: not a mixture engine (gpe_config.mixture)");
+    if (e->main.n <= 0) FAIL(e, GPE_ERR_STATE, "mixture_energy before bind_points");
+    int rc;
+    e->st = StepState{};
+    StepScope seq{e};
+    if ((rc = launch_begin(e, /*force=*/true))) return rc;
+    if ((rc = mlp_forward(e, e->main, false))) return rc;
+    if ((rc = launch_head_pde(e, /*energy=*/true))) return rc;
+    if (e->comm && (rc = dp_allreduce_inline(e, e->sums(), S_COUNT, ncclDouble))) return rc;      // over all ranks: the first phase's exchange
+    double s[S_COUNT];
+    HIPCHK(e, hipMemcpyAsync(s, e->sums(), sizeof s, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    e->acc_clean = false;
+    const MixEnergy me = mix_energy_of(e->oc.mix.g, e->oc.mix.n, (double)e->ph.dx, s);
+    out[0] = me.E; out[1] = s[S_MIX_T1]; out[2] = s[S_MIX_T2]; out[3] = s[S_MIX_Q11]; out[4] = s[S_MIX_Q22]; out[5] = s[S_MIX_Q12];
+    out[6] = s[S_DEN]; out[7] = s[S_MIX_DEN2];
     return GPE_OK;
 }
 int gpe_set_power(gpe_engine* e, int p) {

@@ -438,13 +438,19 @@ __global__ __launch_bounds__(1024) void k_seed_pde(Phys ph, Pts x, const float* 
 // boundary rows riding in the batch are treated as k_head_pde treats those of complex psi (both outputs, cnt = n_bc * 2).  A mixture has
 // no base, envelope, orthogonality or energy sums (gpe_create refuses them), so none of that is here.
 // phase 1: u_a, H_a u_a per point; (num_1, den_1, num_2, den_2) -> sums[S_NUM, S_DEN, S_MIX_NUM2, S_MIX_DEN2], bse -> lsums.
-template <int C, int E, bool WQ = false>
+// EN (gpe_mixture_energy_weight != 0, gpe_mixture_energy): the energy term of the mixture.  The kernel also reads the first-derivative
+// channels of O, keeps grad u_a in ux_out ([a][k][ld], as k_head_pde does for its Riesz term) and adds T_a = sum q (c |grad u_a|^2 +
+// V u_a^2) and Q_ab = sum q u_a^2 u_b^2 -> sums[S_MIX_T1 .. S_MIX_Q12] in the same pass: ten partial sums instead of five.  EN = false
+// is the kernel as it was: ux_out is not touched.
+template <int C, int E, bool WQ = false, bool EN = false>
 __global__ __launch_bounds__(1024) void k_head_mix(Phys ph, MixPhys mx, Pts x, const float* __restrict__ Vpre, const float* __restrict__ O,
                                                   float* __restrict__ u_out, float* __restrict__ Hu_out, double* __restrict__ sums,
                                                   int64_t N, int64_t ld, int64_t n_pde, const float* __restrict__ bc_target,
-                                                  float* __restrict__ Ob, double* __restrict__ lsums, const float* __restrict__ qw = nullptr) {
+                                                  float* __restrict__ Ob, double* __restrict__ lsums, const float* __restrict__ qw = nullptr,
+                                                  float* __restrict__ ux_out = nullptr) {
     constexpr int D = C - 1 - E;
     double num[2] = {0.0, 0.0}, den[2] = {0.0, 0.0}, bse = 0.0;
+    double en[5] = {0.0, 0.0, 0.0, 0.0, 0.0};          // T_1, T_2, Q_11, Q_22, Q_12 (EN)
     for (int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; m < N; m += (int64_t)gridDim.x * blockDim.x) {
         if (m >= n_pde) {                              // boundary point riding in this batch
             const int64_t mb = m - n_pde;
@@ -482,11 +488,27 @@ __global__ __launch_bounds__(1024) void k_head_mix(Phys ph, MixPhys mx, Pts x, c
             num[o] += wq_term<WQ>(qd, u[o] * Hu[o]);
             den[o] += wq_term<WQ>(qd, u[o] * u[o]);
         }
+        if constexpr (EN) {
+#pragma unroll
+            for (int o = 0; o < 2; ++o) {
+                float g2 = 0.f;
+#pragma unroll
+                for (int k = 0; k < D; ++k) {
+                    const float uk = ph.perturb_scale * O[((int64_t)(1 + k) * 2 + o) * ld + m];
+                    ux_out[(int64_t)(o * D + k) * ld + m] = uk;
+                    g2 = fmaf(uk, uk, g2);
+                }
+                en[o] += wq_term<WQ>(qd, fmaf(ph.kin, g2, V * (o == 0 ? s1 : s2)));
+            }
+            en[2] += wq_term<WQ>(qd, s1 * s1);
+            en[3] += wq_term<WQ>(qd, s2 * s2);
+            en[4] += wq_term<WQ>(qd, s1 * s2);
+        }
     }
     // all partial sums of the workgroup in one pass (the shuffle tree and wave order of k_head_pde / block_sum_256)
-    constexpr int K = 5;
+    constexpr int K = EN ? 10 : 5;
     __shared__ double redm[16 * K];
-    double vals[K] = {num[0], den[0], num[1], den[1], bse};
+    double vals[10] = {num[0], den[0], num[1], den[1], bse, en[0], en[1], en[2], en[3], en[4]};
     const int w = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
 #pragma unroll
     for (int k = 0; k < K; ++k) {
@@ -500,20 +522,35 @@ __global__ __launch_bounds__(1024) void k_head_mix(Phys ph, MixPhys mx, Pts x, c
         const int k = threadIdx.x;
         double r = 0.0;
         for (int i2 = 0; i2 < nw; ++i2) r += redm[i2 * K + k];
-        double* dst = k == 0 ? &sums[S_NUM] : k == 1 ? &sums[S_DEN] : k == 2 ? &sums[S_MIX_NUM2] : k == 3 ? &sums[S_MIX_DEN2] : &lsums[LS_BC_SE2];
+        double* dst = k == 0 ? &sums[S_NUM] : k == 1 ? &sums[S_DEN] : k == 2 ? &sums[S_MIX_NUM2] : k == 3 ? &sums[S_MIX_DEN2]
+                    : k == 4 ? &lsums[LS_BC_SE2] : &sums[S_MIX_T1 + (k - 5)];
         if (k != 4 || r != 0.0) atomicAdd(dst, r);
     }
 }
 
 // phase 2: mu_a = num_a / den_a (global sums), r_a = H_a u_a - mu_a u_a, sum (r_1^2 + r_2^2) -> sum_r2; Ob = dLoss/dO with mu_a constant
 // (their branch of the gradient vanishes: sum r_a u_a = 0).  The cross term rb_b 2 g_ab u_a u_b is d r_b / d u_a.  WQ as in k_seed_pde.
-template <int C, int E, bool WQ = false>
+// EN: the seeds of w_E E are added (include/gpe_hip.h) -- to the value channel and, through grad u_a kept by the head kernel, to the
+// first-derivative channels.  Thread 0 forms the coefficients once per workgroup, in double, from the all-reduced sums; the value seed of
+// a point is summed in double too and rounded once (near the minimiser its terms cancel against the gradient term's).
+template <int C, int E, bool WQ = false, bool EN = false>
 __global__ __launch_bounds__(1024) void k_seed_mix(Phys ph, MixPhys mx, Pts x, const float* __restrict__ Vpre, const float* __restrict__ u_in,
                                                   const float* __restrict__ Hu_in, const double* __restrict__ sums, float* __restrict__ Ob,
                                                   float* __restrict__ resid_out, double* __restrict__ sum_r2, int64_t N, int64_t ld,
-                                                  int want_seeds, const float* __restrict__ qw = nullptr) {
+                                                  int want_seeds, const float* __restrict__ qw = nullptr, const float* __restrict__ ux_in = nullptr) {
     constexpr int D = C - 1 - E;
     __shared__ double red[16];
+    __shared__ double s_en[7];                         // w_E (alpha_1, alpha_2, beta_11, beta_22, beta_12, delta_1, delta_2)
+    if constexpr (EN) {
+        if (threadIdx.x == 0) {
+            const MixEnergy me = mix_energy_of(mx.g, mx.n, (double)ph.dx, sums);
+            const double w = (double)mx.wE;
+            s_en[0] = w * me.alpha[0]; s_en[1] = w * me.alpha[1];
+            s_en[2] = w * me.beta[0]; s_en[3] = w * me.beta[1]; s_en[4] = w * me.beta[2];
+            s_en[5] = w * me.delta[0]; s_en[6] = w * me.delta[1];
+        }
+        __syncthreads();
+    }
     double sr2 = 0.0;
     const double den1 = sums[S_DEN], den2 = sums[S_MIX_DEN2];
     const float lam[2] = {(float)(sums[S_NUM] / den1), (float)(sums[S_MIX_NUM2] / den2)};
@@ -538,15 +575,23 @@ __global__ __launch_bounds__(1024) void k_seed_mix(Phys ph, MixPhys mx, Pts x, c
             const float V = potential_at(ph, xv, Vpre, m);
             const float s1 = u[0] * u[0], s2 = u[1] * u[1], g11 = mx.g[0], g22 = mx.g[1], g12 = mx.g[2];
             const float cross = 2.f * g12 * u[0] * u[1];
-            const float ub[2] = {rb[0] * (V + 3.f * g11 * s1 + g12 * s2 - lam[0]) + rb[1] * cross + cn[0] * u[0],
-                                 rb[1] * (V + 3.f * g22 * s2 + g12 * s1 - lam[1]) + rb[0] * cross + cn[1] * u[1]};
+            float ub[2] = {rb[0] * (V + 3.f * g11 * s1 + g12 * s2 - lam[0]) + rb[1] * cross + cn[0] * u[0],
+                           rb[1] * (V + 3.f * g22 * s2 + g12 * s1 - lam[1]) + rb[0] * cross + cn[1] * u[1]};
+            if constexpr (EN) {       // d(w_E E)/du_a = 2 alpha_a V u_a + 4 beta_aa u_a^3 + 2 beta_12 u_a u_b^2 + 2 delta_a u_a
+                const double Vd = (double)V, d1 = (double)s1, d2 = (double)s2;
+                ub[0] += (float)(2.0 * (double)u[0] * (s_en[0] * Vd + 2.0 * s_en[2] * d1 + s_en[4] * d2 + s_en[5]));
+                ub[1] += (float)(2.0 * (double)u[1] * (s_en[1] * Vd + 2.0 * s_en[3] * d2 + s_en[4] * d1 + s_en[6]));
+            }
             const float sc = ph.perturb_scale;
 #pragma unroll
             for (int o = 0; o < 2; ++o) {
                 float Ub[C];
                 Ub[0] = ub[o];
 #pragma unroll
-                for (int j = 0; j < D; ++j) Ub[1 + j] = 0.f;
+                for (int j = 0; j < D; ++j) {
+                    if constexpr (EN) Ub[1 + j] = (float)(2.0 * (double)ph.kin * s_en[o]) * ux_in[(int64_t)(o * D + j) * ld + m];      // 2 c alpha_a d_k u_a
+                    else Ub[1 + j] = 0.f;
+                }
 #pragma unroll
                 for (int j = 0; j < E; ++j) Ub[1 + D + j] = -ph.kin * rb[o];
 #pragma unroll

@@ -759,6 +759,21 @@ class Engine:
         self._chk(self.lib.gpe_mixture_scalars(self._h, out))
         return dict(zip(self.MIXTURE_FIELDS, [float(v) for v in out]))
 
+    MIXTURE_ENERGY_FIELDS = ("E", "T1", "T2", "Q11", "Q22", "Q12", "den1", "den2")
+
+    def set_mixture_energy(self, w: float):
+        """Weight w_E >= 0 of the mixture energy term from the next step on (include/gpe_hip.h: gpe_mixture_energy_weight): the loss gains
+        w_E E, E the energy of the state normalised to the target norms, and the step's record reports E as 'riesz'.  0 switches it off."""
+        self._chk(self.lib.gpe_mixture_energy_weight(self._h, float(w)))
+        self.mixture_energy_weight = float(w)
+
+    def mixture_energy(self) -> dict:
+        """E and the sums it is formed from (T_a, Q_ab, den_a) on the bound set at the current parameters, at any weight; forward-only,
+        synchronises, leaves parameters, optimiser state and the last record alone."""
+        out = (C.c_double * 8)()
+        self._chk(self.lib.gpe_mixture_energy(self._h, out))
+        return dict(zip(self.MIXTURE_ENERGY_FIELDS, [float(v) for v in out]))
+
     def set_power(self, p: int):
         self.cfg.p = int(p)
         self._chk(self.lib.gpe_set_power(self._h, int(p)))

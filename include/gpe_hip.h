@@ -143,12 +143,13 @@ typedef struct gpe_config {
      * Seeds at the output jets, rb_a = 2 w_pde r_a / N, b the other component, mu_a held constant (its branch of the gradient vanishes:
      * d loss / d mu_a = -2 w_pde / N sum r_a u_a = 0):
      *   d/du_a     = rb_a (V + 3 g_aa u_a^2 + g_ab u_b^2 - mu_a) + rb_b 2 g_ab u_a u_b + 4 w_norm (I_a - n_a) dx u_a
-     *   d/d(lap u_a) = -c rb_a ;  first-derivative seeds 0
+     *   d/d(lap u_a) = -c rb_a ;  first-derivative seeds 0 (the energy term adds to both: gpe_mixture_energy_weight, below)
      * gamma, complex_psi, omega_rot, base_mode, envelope, w_sym, w_orth, w_riesz, lambda_kind, the regularisers and residual blocks do
      * not combine with a mixture: gpe_create refuses them.  Quadrature weights, merged boundary rows, the samplers, the pre-training
      * step, gpe_run and the data-parallel entry points work as for any n_out = 2 network; (num_2, den_2) travel in slots 10, 11 of the
      * first exchange message.  gpe_scalars reports component 1 (mu, num, den, integral) and norm = sum_a (I_a - n_a)^2; component 2 is
-     * read with gpe_mixture_scalars.  The three fields were appended without a change of GPE_ABI_VERSION: a binding verifies its layout
+     * read with gpe_mixture_scalars.  w_riesz is the scalar problem's term; a mixture's own energy term is switched on for the live engine
+     * with gpe_mixture_energy_weight and needs no configuration field.  The three fields were appended without a change of GPE_ABI_VERSION: a binding verifies its layout
      * against gpe_sizeof_config(), and a zero-filled tail means "no mixture". */
     int32_t mixture;
     float mix_g[3];               /* g_11, g_22, g_12 */
@@ -497,6 +498,28 @@ int gpe_set_mixture(gpe_engine* e, float g11, float g22, float g12);
 /* synchronise; out = (mu_1, mu_2, I_1, I_2, num_1, den_1, num_2, den_2) of the last completed step or gpe_residual (the numbers its
  * gpe_scalars record was formed from; over all ranks in a data-parallel step).  GPE_ERR_STATE: not a mixture engine. */
 int gpe_mixture_scalars(gpe_engine* e, double out[8]);
+/* mixture engines: the energy term.  With q the quadrature weights (1 without), den_a = sum q u_a^2, I_a = dx den_a,
+ *   T_a = sum q (c |grad u_a|^2 + V u_a^2),   Q_ab = sum q u_a^2 u_b^2,
+ * the energy of the state normalised to the target norms, v_a = u_a sqrt(n_a / I_a), is
+ *   E = sum_a n_a T_a / den_a + 1/2 sum_ab g_ab n_a n_b Q_ab / (den_a den_b dx)            (g_21 = g_12: the 12 term counts twice)
+ *   loss += w_E E
+ * E does not change when a component is scaled; its stationary points under the two norm constraints are the solutions of
+ * H_a v_a = mu_a v_a and its minimiser is the ground state (at g_12 = 0, n = (1, 1) it is the sum of two GPE_RIESZ_VARIATIONAL energies
+ * at p = 3).  Seeds at the output jets (times q_i and perturb_scale as all seeds), with alpha_a = n_a / den_a,
+ * beta_aa = 1/2 g_aa n_a^2 / (den_a^2 dx), beta_12 = g_12 n_1 n_2 / (den_1 den_2 dx), b the other component:
+ *   delta_a    = -n_a T_a / den_a^2 - g_aa n_a^2 Q_aa / (den_a^3 dx) - g_12 n_1 n_2 Q_12 / (den_a^2 den_b dx)
+ *   d/du_a     = w_E (2 alpha_a V u_a + 4 beta_aa u_a^3 + 2 beta_12 u_a u_b^2 + 2 delta_a u_a)
+ *   d/d(d_k u_a) = w_E 2 c alpha_a d_k u_a ;   d/d(lap u_a) unchanged
+ * The five sums travel in slots 2-6 of the first exchange message, which a mixture engine leaves empty otherwise; the coefficients are
+ * formed in double from the all-reduced sums.
+ * gpe_mixture_energy_weight: w_E of the NEXT step, like gpe_set_mixture (a captured graph is rebuilt); a step with w_E != 0 runs the
+ * energy instances of the head and seed kernels, adds w_E E to the loss and reports E in gpe_scalars.riesz; w_E = 0 (the default) is the
+ * plain mixture step, kernel for kernel.  GPE_ERR_STATE: not a mixture engine; GPE_ERR_INVALID: a negative or non-finite weight.
+ * gpe_mixture_energy: forward-only evaluation on the bound set at the current parameters, at any w_E (0 included); synchronises;
+ * out = (E, T_1, T_2, Q_11, Q_22, Q_12, den_1, den_2), over all ranks when a communicator is up (every rank calls it).  Parameters,
+ * optimiser state and the last record are left as they were.  GPE_ERR_STATE: not a mixture engine, or nothing bound. */
+int gpe_mixture_energy_weight(gpe_engine* e, float w_E);
+int gpe_mixture_energy(gpe_engine* e, double out[8]);
 int gpe_set_power(gpe_engine* e, int p);
 int gpe_set_lr(gpe_engine* e, float lr);
 int gpe_set_perturb_scale(gpe_engine* e, float s);

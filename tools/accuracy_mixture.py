@@ -7,7 +7,10 @@ with phi the ground state of the scalar problem at g_eff = (g + g12) / 2 and mu_
 (mu_a, norms, overlap of the densities): no reference state is claimed for it.
 
 The network starts from a pre-training on the Gaussian of the linear problem (gpe_mse_step); then stages of plain steps, the couplings
-raised stage by stage with gpe_set_mixture.   usage: tools/accuracy_mixture.py [--out profiles/mixture/accuracy_mixture_1d.json]"""
+raised stage by stage with gpe_set_mixture.  --energy W trains with the mixture energy term at weight W (gpe_mixture_energy_weight) and
+records E of both runs (gpe_mixture_energy) next to the energies of the symmetric and the separated stationary state of the immiscible
+couplings from the fp64 gradient flow tests/mixture_flow_1d.py.
+usage: tools/accuracy_mixture.py [--energy W] [--out profiles/mixture_energy/accuracy_mixture_1d.json]"""
 import argparse, json, os, sys, time
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -24,6 +27,7 @@ ap.add_argument("--half", type=float, default=8.0)
 ap.add_argument("--stages", type=int, default=8)
 ap.add_argument("--steps", type=int, default=4000, help="steps per continuation stage")
 ap.add_argument("--pretrain", type=int, default=3000)
+ap.add_argument("--energy", type=float, default=0.0, help="weight of the mixture energy term (0: residual loss alone)")
 ap.add_argument("--out", default=None)
 a = ap.parse_args()
 
@@ -48,6 +52,7 @@ def train(g11, g22, g12_end, norms, tilt):
     for _ in range(a.pretrain):
         eng.mse_step()
     eng.reset_optimizer(1e-3)
+    eng.set_mixture_energy(a.energy)
     for s in range(1, a.stages + 1):
         f = s / a.stages
         eng.set_mixture(f * g11, f * g22, f * g12_end)
@@ -63,7 +68,7 @@ def state(eng):
     return sc, eng.mixture_scalars(), psi.cpu().numpy().astype(np.float64), res.cpu().numpy().astype(np.float64)
 
 
-rec = dict(tool="tools/accuracy_mixture.py", layers=layers, points=N, box=[-L, L], dx=dx, stages=a.stages, steps_per_stage=a.steps, pretrain=a.pretrain)
+rec = dict(tool="tools/accuracy_mixture.py", energy_weight=a.energy, layers=layers, points=N, box=[-L, L], dx=dx, stages=a.stages, steps_per_stage=a.steps, pretrain=a.pretrain)
 # ---- symmetric, miscible: against the scalar solver at g_eff ----
 g_eff = 0.5 * (a.g + a.g12)
 lam, states = gs.ground_state_1d([g_eff], c=0.5, vscale=0.5, half=12.0)
@@ -71,18 +76,22 @@ xs, phi = states[g_eff]
 phi_on_x = np.interp(x[:, 0], xs, phi)
 eng, secs = train(a.g, a.g, a.g12, (0.5, 0.5), 0.0)
 sc, m, u, r = state(eng)
+E_miscible = eng.mixture_energy()["E"]
 dens_ref = 0.5 * phi_on_x ** 2
 sym = dict(g=a.g, g12=a.g12, g_eff=g_eff, mu_ref=lam[g_eff], mu1=m["mu1"], mu2=m["mu2"], mu1_abs_err=abs(m["mu1"] - lam[g_eff]),
            mu2_abs_err=abs(m["mu2"] - lam[g_eff]), integral1=m["integral1"], integral2=m["integral2"], loss=sc["loss"], pde=sc["pde"],
            density_max_abs_err=[float(np.abs(u[:, k] ** 2 / (m[f"integral{k + 1}"] / 0.5) - dens_ref).max()) for k in range(2)],
            density_peak_ref=float(dens_ref.max()), residual_rms=[float(np.sqrt(dx * (r[:, k] ** 2).sum())) for k in range(2)], train_seconds=secs)
+sym["E"] = E_miscible
 rec["symmetric"] = sym
 eng.close()
 # ---- immiscible: reported, no bar ----
 eng, secs = train(a.g, a.g, a.g12_immiscible, (0.5, 0.5), 0.5)
 sc, m, u, r = state(eng)
+from tests import mixture_flow_1d as mf
+E_sym, E_sep = mf.sym_and_sep(a.g, a.g12_immiscible)
 d1, d2 = u[:, 0] ** 2, u[:, 1] ** 2
-rec["immiscible"] = dict(g=a.g, g12=a.g12_immiscible, mu1=m["mu1"], mu2=m["mu2"], integral1=m["integral1"], integral2=m["integral2"], loss=sc["loss"],
+rec["immiscible"] = dict(E=eng.mixture_energy()["E"], E_sym=E_sym, E_sep=E_sep, g=a.g, g12=a.g12_immiscible, mu1=m["mu1"], mu2=m["mu2"], integral1=m["integral1"], integral2=m["integral2"], loss=sc["loss"],
                          pde=sc["pde"], density_overlap=float(dx * np.sqrt(d1 * d2).sum() / np.sqrt(m["integral1"] * m["integral2"])),
                          centre_of_mass=[float((x[:, 0] * d).sum() / d.sum()) for d in (d1, d2)],
                          residual_rms=[float(np.sqrt(dx * (r[:, k] ** 2).sum())) for k in range(2)], train_seconds=secs)
