@@ -70,6 +70,22 @@ class gpe_observables(C.Structure):
         return {n: (list(getattr(self, n)) if n in ("mean_x", "var_x") else getattr(self, n)) for n, _ in self._fields_}
 
 
+class gpe_mixture_observables(C.Structure):
+    """include/gpe_hip.h: struct gpe_mixture_observables -- norms, energy parts, one chemical potential per component, overlap, moments and
+    residuals of a two-component state normalised to the target norms."""
+    _fields_ = [("n", C.c_double), ("dv", C.c_double), ("step", C.c_double), ("norm", C.c_double * 2), ("kin", C.c_double * 2),
+                ("pot", C.c_double * 2), ("inter", C.c_double * 3), ("energy", C.c_double), ("mu", C.c_double * 2), ("mu_lap", C.c_double * 2),
+                ("overlap", C.c_double), ("mean_x", (C.c_double * 3) * 2), ("var_x", (C.c_double * 3) * 2), ("peak_density", C.c_double * 2),
+                ("res_rms", C.c_double * 2), ("res_rms_total", C.c_double)]
+
+    def as_dict(self):
+        out = {}
+        for n, t in self._fields_:
+            v = getattr(self, n)
+            out[n] = v if t is C.c_double else ([list(r) for r in v] if n in ("mean_x", "var_x") else list(v))
+        return out
+
+
 class gpe_sampler_spec(C.Structure):
     """include/gpe_hip.h: gpe_sampler_spec -- the grid, clip box, seed, cell block and cadence of the device-side stratified sampler."""
     _fields_ = [("shape", C.c_int64 * 3), ("lo", C.c_float * 3), ("hi", C.c_float * 3), ("clip_lo", C.c_float * 3),
@@ -86,6 +102,7 @@ SYMBOLS = {
     "gpe_sizeof_config": (C.c_size_t, []),
     "gpe_sizeof_scalars": (C.c_size_t, []),
     "gpe_sizeof_observables": (C.c_size_t, []),
+    "gpe_sizeof_mixture_observables": (C.c_size_t, []),
     "gpe_sizeof_sampler_spec": (C.c_size_t, []),
     "gpe_exchange_dbl_count": (_i64, []),
     "gpe_use_external_exchange": (_int, [_vp, _vp, _i64, _vp, _i64]),
@@ -132,6 +149,11 @@ SYMBOLS = {
     "gpe_bind_keeper": (_int, [_vp, _int, C.c_double, _i64]),
     "gpe_keeper_read": (_int, [_vp, _vp, C.c_size_t, _P(gpe_observables), _P(_i64), _P(_i64), _P(_i64), _P(_int)]),
     "gpe_keeper_restore": (_int, [_vp]),
+    "gpe_mixture_observables": (_int, [_vp, _vp, _i64, _vp, _f, _P(gpe_mixture_observables)]),
+    "gpe_mixture_monitor": (_int, [_vp, _vp, _i64, _vp, _f, _i64, C.c_int32]),
+    "gpe_mixture_monitor_read": (_int, [_vp, _i64, _i64, _P(gpe_mixture_observables), _P(_i64)]),
+    "gpe_mixture_keeper": (_int, [_vp, _int, C.c_double, _i64]),
+    "gpe_mixture_keeper_read": (_int, [_vp, _vp, C.c_size_t, _P(gpe_mixture_observables), _P(_i64), _P(_i64), _P(_i64), _P(_int)]),
     "gpe_step_begin": (_int, [_vp]),
     "gpe_step_backward": (_int, [_vp]),
     "gpe_step_update": (_int, [_vp]),
@@ -193,6 +215,7 @@ def load():
         raise ImportError(f"{path}: ABI version {lib.gpe_abi_version()} != {GPE_ABI_VERSION}")
     if lib.gpe_sizeof_config() != C.sizeof(gpe_config) or lib.gpe_sizeof_scalars() != C.sizeof(gpe_scalars) or \
             lib.gpe_sizeof_observables() != C.sizeof(gpe_observables) or \
+            lib.gpe_sizeof_mixture_observables() != C.sizeof(gpe_mixture_observables) or \
             lib.gpe_sizeof_sampler_spec() != C.sizeof(gpe_sampler_spec):
         raise ImportError(f"{path}: struct layout mismatch between include/gpe_hip.h and _capi.py")
     _lib = lib

@@ -31,6 +31,7 @@ typedef enum { ncclFloat = 7, ncclDouble = 8 } ncclDataType_t;
 #include "gpe_common.h"
 #include "gpe_head.h"
 #include "gpe_observe.h"
+#include "gpe_observe_mix.h"
 #include "gpe_sampler.h"
 #include "gpe_generic.h"
 #include "gpe_fused.h"
@@ -642,7 +643,7 @@ struct gpe_engine {
     bool dp_inline = true;                            // synchronous step on the fused / wide sets: collectives on the compute stream (GPE_DP_INLINE=0: exchange stream)
     // ---- observables (gpe_observe.h) ----
     double* obs_buf = nullptr;                        // [pass-1 slab | pass-2 slab | raw totals], allocated on first use
-    struct gpe_observables* obs_out = nullptr;        // staging slot of gpe_observables
+    double* obs_out = nullptr;                        // staging slot of gpe_observables / gpe_mixture_observables: one record of the engine's kind
     // held-out monitor (gpe_bind_monitor): its own forward batch, sized at the bind -- gpe_run must neither allocate nor synchronise
     Batch mon;
     const float* mon_x = nullptr; const float* mon_V = nullptr;
@@ -650,7 +651,7 @@ struct gpe_engine {
     int64_t mon_n = 0, mon_every = 0;                 // every == 0: no monitor
     int64_t mon_steps = 0, mon_records = 0;           // steps enqueued / records appended since the bind
     int mon_cap = 0;
-    struct gpe_observables* mon_ring = nullptr;       // [mon_cap]
+    double* mon_ring = nullptr;                       // [mon_cap] records of the engine's kind (obs_rec_doubles each)
     // keeper (gpe_bind_keeper): the best parameters by one field of the monitor's records; both buffers allocated at the bind
     int keep_metric = GPE_KEEP_NONE;                  // GPE_KEEP_NONE: no keeper
     double keep_min_delta = 0.0;
@@ -1799,6 +1800,7 @@ int gpe_abi_version(void) { return GPE_ABI_VERSION; }
 size_t gpe_sizeof_config(void) { return sizeof(gpe_config); }
 size_t gpe_sizeof_scalars(void) { return sizeof(gpe_scalars); }
 size_t gpe_sizeof_observables(void) { return sizeof(struct gpe_observables); }
+size_t gpe_sizeof_mixture_observables(void) { return sizeof(struct gpe_mixture_observables); }
 size_t gpe_sizeof_sampler_spec(void) { return sizeof(gpe_sampler_spec); }
 int64_t gpe_exchange_dbl_count(void) { return S_COUNT + LS_COUNT + 4; }
 
@@ -2626,11 +2628,17 @@ int gpe_eval_density(gpe_engine* e, const float* d_x, int64_t n, float dx, int a
 
 
 // ---- observables of the current state (gpe_observe.h) --------------------------------------------------------------------
+// A scalar engine's records are struct gpe_observables, a mixture engine's struct gpe_mixture_observables (an engine is one or the other
+// for life): doubles per record, and per slab row of its reduction chain
+static int obs_rec_doubles(const gpe_engine* e) {
+    return (int)((e->cfg.mixture ? sizeof(struct gpe_mixture_observables) : sizeof(struct gpe_observables)) / sizeof(double));
+}
+static int obs_row(const gpe_engine* e) { return e->cfg.mixture ? MO_ROW : OB_ROW; }
 static int obs_ensure(gpe_engine* e) {
     if (e->obs_buf) return GPE_OK;
     int rc;
-    if ((rc = dev_alloc(e, (Batch*)nullptr, &e->obs_buf, (size_t)2 * OBS_MAX_WG * OB_ROW + OB_ROW))) return rc;
-    return dev_alloc(e, (Batch*)nullptr, &e->obs_out, 1);
+    if ((rc = dev_alloc(e, (Batch*)nullptr, &e->obs_buf, (size_t)2 * OBS_MAX_WG * obs_row(e) + obs_row(e)))) return rc;
+    return dev_alloc(e, (Batch*)nullptr, &e->obs_out, (size_t)obs_rec_doubles(e));
 }
 static bool precomputed_base(const gpe_engine* e) { return e->cfg.base_mode >= 0 && e->cfg.base_kind == GPE_BASE_PRECOMPUTED; }
 // which points an observables call / a monitor may look at: any, unless something exists on the bound points only
@@ -2686,7 +2694,54 @@ int gpe_observables(gpe_engine* e, const float* d_x, int64_t n, const float* d_V
     if ((rc = obs_check_points(e, "observables", d_x, n, d_V))) return rc;
     if ((rc = obs_ensure(e))) return rc;
     if ((rc = aux_forward(e, d_x, n, 1 + 2 * e->nd.dim, e->nd.dim))) return rc;       // full diagonal second derivatives, as gpe_forward_jets
-    if ((rc = launch_observe(e, e->aux, d_x, n, d_V, dv, e->obs_out, q))) return rc;
+    if ((rc = launch_observe(e, e->aux, d_x, n, d_V, dv, (struct gpe_observables*)e->obs_out, q))) return rc;
+    HIPCHK(e, hipMemcpyAsync(out, e->obs_out, sizeof *out, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    return GPE_OK;
+}
+
+// the mixture instances of the chain (gpe_observe_mix.h): same grid, same slab layout with rows of MO_ROW doubles; the couplings and
+// target norms are those in force now (e->oc.mix, by value)
+static int launch_observe_mix(gpe_engine* e, Batch& b, const float* x, int64_t n, const float* V, float dv, struct gpe_mixture_observables* dst,
+                              const float* q = nullptr) {
+    const unsigned g = (unsigned)std::min<int64_t>(cdiv(n, OBS_THREADS), OBS_MAX_WG);        // a function of n alone: fixed point -> thread map
+    double* slab1 = e->obs_buf;
+    double* slab2 = slab1 + (size_t)OBS_MAX_WG * MO_ROW;
+    double* raw = slab2 + (size_t)OBS_MAX_WG * MO_ROW;
+#define MIXOBS_CHAIN(DD, WW)                                                                                                              \
+    hipLaunchKernelGGL((k_mixobs_pass1<DD, WW>), dim3(g), dim3(OBS_THREADS), 0, e->stream, e->ph, x, V, (const float*)b.O, n, b.ld, slab1, q); \
+    hipLaunchKernelGGL(k_mixobs_reduce, dim3(1), dim3(OBS_THREADS), 0, e->stream, (const double*)slab1, (int)g, raw);                    \
+    hipLaunchKernelGGL((k_mixobs_pass2<DD, WW>), dim3(g), dim3(OBS_THREADS), 0, e->stream, e->ph, e->oc.mix, x, V, (const float*)b.O, n, b.ld, \
+                       (const double*)raw, (double)dv, slab2, q);
+    switch (e->nd.dim * 2 + (q ? 1 : 0)) {
+        case 2: MIXOBS_CHAIN(1, false) break;
+        case 3: MIXOBS_CHAIN(1, true) break;
+        case 4: MIXOBS_CHAIN(2, false) break;
+        case 5: MIXOBS_CHAIN(2, true) break;
+        case 6: MIXOBS_CHAIN(3, false) break;
+        default: MIXOBS_CHAIN(3, true) break;
+    }
+#undef MIXOBS_CHAIN
+    hipLaunchKernelGGL(k_mixobs_finish, dim3(1), dim3(OBS_THREADS), 0, e->stream, e->ph, e->oc.mix, (const double*)slab2, (int)g, (const double*)raw,
+                       (double)dv, (double)n, (const OptDev*)e->od, dst);
+    HIPCHK(e, hipGetLastError());
+    return GPE_OK;
+}
+
+int gpe_mixture_observables(gpe_engine* e, const float* d_x, int64_t n, const float* d_V, float dv, struct gpe_mixture_observables* out) {
+    if (!e || !out) return GPE_ERR_INVALID;
+    if (!e->cfg.mixture) FAIL(e, GPE_ERR_STATE, "mixture_observables: not a mixture engine (gpe_config.mixture; a scalar engine has gpe_observables)");
+    const float* q = nullptr;
+    if (!d_x) {
+        if (!e->ux) FAIL(e, GPE_ERR_STATE, "mixture_observables of the bound points before bind_points");
+        d_x = e->ux; n = e->n_pde; d_V = e->uV;
+        q = e->wq;                               // the bound set carries its bound weights; an explicit set and the monitor have none
+    }
+    int rc;
+    if ((rc = obs_check_points(e, "mixture_observables", d_x, n, d_V))) return rc;
+    if ((rc = obs_ensure(e))) return rc;
+    if ((rc = aux_forward(e, d_x, n, 1 + 2 * e->nd.dim, e->nd.dim))) return rc;       // full diagonal second derivatives, as gpe_forward_jets
+    if ((rc = launch_observe_mix(e, e->aux, d_x, n, d_V, dv, (struct gpe_mixture_observables*)e->obs_out, q))) return rc;
     HIPCHK(e, hipMemcpyAsync(out, e->obs_out, sizeof *out, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));
     return GPE_OK;
@@ -2707,7 +2762,10 @@ static int keeper_reset(gpe_engine* e, KeepDev* kd) {
     HIPCHK(e, hipStreamSynchronize(e->stream));
     return GPE_OK;
 }
-static int keeper_field(int metric) {                 // index of the chosen double in struct gpe_observables
+static int keeper_field(const gpe_engine* e, int metric) {      // index of the chosen double in the engine's kind of record
+    if (e->cfg.mixture)
+        return (int)((metric == GPE_KEEP_ENERGY ? offsetof(struct gpe_mixture_observables, energy)
+                                                : offsetof(struct gpe_mixture_observables, res_rms_total)) / sizeof(double));
     return (int)((metric == GPE_KEEP_ENERGY ? offsetof(struct gpe_observables, energy) : offsetof(struct gpe_observables, res_rms)) / sizeof(double));
 }
 static int keeper_state(gpe_engine* e, const char* who, KeepDev* h) {      // synchronises
@@ -2725,9 +2783,8 @@ static void monitor_clear(gpe_engine* e) {
     if (e->mon_ring) { (void)hipFree(e->mon_ring); e->mon_ring = nullptr; e->mon_cap = 0; }
 }
 
-int gpe_bind_monitor(gpe_engine* e, const float* d_x, int64_t n, const float* d_V, float dv, int64_t every, int32_t capacity) {
-    if (!e) return GPE_ERR_INVALID;
-    if (e->cfg.mixture && d_x && every > 0) FAIL(e, GPE_ERR_STATE, "monitor: its records are observables, which a mixture engine does not have");
+// gpe_bind_monitor / gpe_mixture_monitor: the ring holds records of the engine's kind
+static int monitor_bind(gpe_engine* e, const float* d_x, int64_t n, const float* d_V, float dv, int64_t every, int32_t capacity) {
     HIPCHK(e, hipStreamSynchronize(e->stream));
     if (!d_x || every <= 0) { monitor_clear(e); return GPE_OK; }
     // validate and allocate first, swap last: a bind that fails leaves the monitor that was there, records included
@@ -2735,10 +2792,11 @@ int gpe_bind_monitor(gpe_engine* e, const float* d_x, int64_t n, const float* d_
     if ((rc = obs_check_points(e, "monitor", d_x, n, d_V))) return rc;
     if ((rc = obs_ensure(e))) return rc;
     const int cap = capacity > 0 ? capacity : 4096;
-    struct gpe_observables* ring = e->mon_ring;
+    const size_t rec_bytes = (size_t)obs_rec_doubles(e) * sizeof(double);
+    double* ring = e->mon_ring;
     if (cap != e->mon_cap) {
         ring = nullptr;
-        if (hipMalloc((void**)&ring, (size_t)cap * sizeof(struct gpe_observables)) != hipSuccess) {
+        if (hipMalloc((void**)&ring, (size_t)cap * rec_bytes) != hipSuccess) {
             (void)hipGetLastError();
             FAIL(e, GPE_ERR_NOMEM, "monitor: no memory for a ring of %d records", cap);
         }
@@ -2753,7 +2811,7 @@ int gpe_bind_monitor(gpe_engine* e, const float* d_x, int64_t n, const float* d_
     free_batch(e->mon);
     e->mon = nb;
     if (ring != e->mon_ring) { if (e->mon_ring) (void)hipFree(e->mon_ring); e->mon_ring = ring; e->mon_cap = cap; }
-    HIPCHK(e, hipMemsetAsync(e->mon_ring, 0, (size_t)cap * sizeof(struct gpe_observables), e->stream));
+    HIPCHK(e, hipMemsetAsync(e->mon_ring, 0, (size_t)cap * rec_bytes, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));
     e->mon_x = d_x; e->mon_V = d_V; e->mon_n = n; e->mon_dv = dv; e->mon_every = every;
     e->mon_steps = 0; e->mon_records = 0;
@@ -2762,9 +2820,20 @@ int gpe_bind_monitor(gpe_engine* e, const float* d_x, int64_t n, const float* d_
     return GPE_OK;
 }
 
-int gpe_bind_keeper(gpe_engine* e, int metric, double min_delta, int64_t patience) {
+int gpe_bind_monitor(gpe_engine* e, const float* d_x, int64_t n, const float* d_V, float dv, int64_t every, int32_t capacity) {
     if (!e) return GPE_ERR_INVALID;
-    if (e->cfg.mixture && metric != GPE_KEEP_NONE) FAIL(e, GPE_ERR_STATE, "keeper: it judges monitor records, which a mixture engine does not have");
+    if (e->cfg.mixture && d_x && every > 0)
+        FAIL(e, GPE_ERR_STATE, "monitor: its records are struct gpe_observables, which a mixture engine does not have (gpe_mixture_monitor)");
+    return monitor_bind(e, d_x, n, d_V, dv, every, capacity);
+}
+int gpe_mixture_monitor(gpe_engine* e, const float* d_x, int64_t n, const float* d_V, float dv, int64_t every, int32_t capacity) {
+    if (!e) return GPE_ERR_INVALID;
+    if (!e->cfg.mixture) FAIL(e, GPE_ERR_STATE, "mixture_monitor: not a mixture engine (gpe_config.mixture; a scalar engine has gpe_bind_monitor)");
+    return monitor_bind(e, d_x, n, d_V, dv, every, capacity);
+}
+
+// gpe_bind_keeper / gpe_mixture_keeper: the field judged is one of the engine's kind of record (keeper_field)
+static int keeper_bind(gpe_engine* e, int metric, double min_delta, int64_t patience) {
     if (metric == GPE_KEEP_NONE) {
         HIPCHK(e, hipStreamSynchronize(e->stream));
         keeper_clear(e);
@@ -2800,8 +2869,20 @@ int gpe_bind_keeper(gpe_engine* e, int metric, double min_delta, int64_t patienc
     return GPE_OK;
 }
 
-int gpe_keeper_read(gpe_engine* e, float* h_flat, size_t n, struct gpe_observables* rec, int64_t* seen, int64_t* kept, int64_t* since_best, int* stopped) {
+int gpe_bind_keeper(gpe_engine* e, int metric, double min_delta, int64_t patience) {
     if (!e) return GPE_ERR_INVALID;
+    if (e->cfg.mixture && metric != GPE_KEEP_NONE)
+        FAIL(e, GPE_ERR_STATE, "keeper: it judges records of struct gpe_observables, which a mixture engine does not have (gpe_mixture_keeper)");
+    return keeper_bind(e, metric, min_delta, patience);
+}
+int gpe_mixture_keeper(gpe_engine* e, int metric, double min_delta, int64_t patience) {
+    if (!e) return GPE_ERR_INVALID;
+    if (!e->cfg.mixture) FAIL(e, GPE_ERR_STATE, "mixture_keeper: not a mixture engine (gpe_config.mixture; a scalar engine has gpe_bind_keeper)");
+    return keeper_bind(e, metric, min_delta, patience);
+}
+
+// gpe_keeper_read / gpe_mixture_keeper_read: rec takes the first rec_bytes of the kept record
+static int keeper_read(gpe_engine* e, float* h_flat, size_t n, void* rec, size_t rec_bytes, int64_t* seen, int64_t* kept, int64_t* since_best, int* stopped) {
     if (h_flat && (int64_t)n != e->P_user) FAIL(e, GPE_ERR_INVALID, "keeper_read: got %zu floats, model has %d", n, e->P_user);
     KeepDev h;
     int rc;
@@ -2812,12 +2893,24 @@ int gpe_keeper_read(gpe_engine* e, float* h_flat, size_t n, struct gpe_observabl
     if (stopped) *stopped = h.stopped;
     if (!h_flat && !rec) return GPE_OK;
     if (h.kept == 0) FAIL(e, GPE_ERR_INVALID, "keeper_read: nothing kept yet (%lld records judged, none finite)", (long long)h.seen);
-    if (rec) *rec = h.rec;
+    if (rec) memcpy(rec, h.rec, rec_bytes);
     if (h_flat) {
         if ((rc = flat_from_device(e, e->theta_best, h_flat))) return rc;
         HIPCHK(e, hipStreamSynchronize(e->stream));
     }
     return GPE_OK;
+}
+
+int gpe_keeper_read(gpe_engine* e, float* h_flat, size_t n, struct gpe_observables* rec, int64_t* seen, int64_t* kept, int64_t* since_best, int* stopped) {
+    if (!e) return GPE_ERR_INVALID;
+    if (e->cfg.mixture && rec) FAIL(e, GPE_ERR_STATE, "keeper_read: a mixture engine keeps a struct gpe_mixture_observables (gpe_mixture_keeper_read)");
+    return keeper_read(e, h_flat, n, rec, sizeof *rec, seen, kept, since_best, stopped);
+}
+int gpe_mixture_keeper_read(gpe_engine* e, float* h_flat, size_t n, struct gpe_mixture_observables* rec, int64_t* seen, int64_t* kept,
+                            int64_t* since_best, int* stopped) {
+    if (!e) return GPE_ERR_INVALID;
+    if (!e->cfg.mixture) FAIL(e, GPE_ERR_STATE, "mixture_keeper_read: not a mixture engine (gpe_config.mixture; a scalar engine has gpe_keeper_read)");
+    return keeper_read(e, h_flat, n, rec, sizeof *rec, seen, kept, since_best, stopped);
 }
 
 int gpe_keeper_restore(gpe_engine* e) {
@@ -2841,10 +2934,13 @@ static int monitor_after_steps(gpe_engine* e, int64_t k) {
     if (e->mon_steps % e->mon_every != 0) return GPE_OK;
     int rc;
     if ((rc = mlp_forward(e, e->mon, false))) return rc;
-    if ((rc = launch_observe(e, e->mon, e->mon_x, e->mon_n, e->mon_V, e->mon_dv, e->mon_ring + (e->mon_records % e->mon_cap)))) return rc;
+    double* slot = e->mon_ring + (size_t)(e->mon_records % e->mon_cap) * obs_rec_doubles(e);
+    if (e->cfg.mixture) rc = launch_observe_mix(e, e->mon, e->mon_x, e->mon_n, e->mon_V, e->mon_dv, (struct gpe_mixture_observables*)slot);
+    else rc = launch_observe(e, e->mon, e->mon_x, e->mon_n, e->mon_V, e->mon_dv, (struct gpe_observables*)slot);
+    if (rc) return rc;
     if (e->keep_metric != GPE_KEEP_NONE) {            // the record just written, judged and -- if it is the best so far -- theta set aside
-        hipLaunchKernelGGL(k_keep_decide, dim3(1), dim3(64), 0, e->stream, (const struct gpe_observables*)(e->mon_ring + (e->mon_records % e->mon_cap)),
-                           keeper_field(e->keep_metric), e->keep_min_delta, (long long)e->keep_patience, e->keep_dev, e->od);
+        hipLaunchKernelGGL(k_keep_decide, dim3(1), dim3(64), 0, e->stream, (const double*)slot, keeper_field(e, e->keep_metric), obs_rec_doubles(e),
+                           e->keep_min_delta, (long long)e->keep_patience, e->keep_dev, e->od);
         const unsigned g = (unsigned)std::min<int64_t>(cdiv((int64_t)cdiv(e->P, 4), KEEP_THREADS), KEEP_MAX_WG);       // a function of P alone
         hipLaunchKernelGGL(k_keep_copy, dim3(g), dim3(KEEP_THREADS), 0, e->stream, (const KeepDev*)e->keep_dev, (const float*)e->theta, e->theta_best, e->P);
         HIPCHK(e, hipGetLastError());
@@ -2853,8 +2949,9 @@ static int monitor_after_steps(gpe_engine* e, int64_t k) {
     return GPE_OK;
 }
 
-int gpe_read_monitor(gpe_engine* e, int64_t first, int64_t count, struct gpe_observables* out, int64_t* available) {
-    if (!e || first < 0 || count < 0 || (count > 0 && !out)) return GPE_ERR_INVALID;
+// gpe_read_monitor / gpe_mixture_monitor_read: out takes records of the engine's kind
+static int monitor_read(gpe_engine* e, int64_t first, int64_t count, void* out, int64_t* available) {
+    const size_t rec_bytes = (size_t)obs_rec_doubles(e) * sizeof(double);
     HIPCHK(e, hipStreamSynchronize(e->stream));
     if (available) *available = e->mon_records;
     if (count == 0) return GPE_OK;
@@ -2865,10 +2962,25 @@ int gpe_read_monitor(gpe_engine* e, int64_t first, int64_t count, struct gpe_obs
     for (int64_t i = 0; i < count;) {
         const int64_t slot = (first + i) % e->mon_cap;
         const int64_t run = std::min<int64_t>(count - i, e->mon_cap - slot);
-        HIPCHK(e, hipMemcpy(out + i, e->mon_ring + slot, run * sizeof(struct gpe_observables), hipMemcpyDeviceToHost));
+        HIPCHK(e, hipMemcpy((char*)out + i * rec_bytes, (const char*)e->mon_ring + slot * rec_bytes, run * rec_bytes, hipMemcpyDeviceToHost));
         i += run;
     }
     return GPE_OK;
+}
+int gpe_read_monitor(gpe_engine* e, int64_t first, int64_t count, struct gpe_observables* out, int64_t* available) {
+    if (!e || first < 0 || count < 0 || (count > 0 && !out)) return GPE_ERR_INVALID;
+    if (e->cfg.mixture) {                             // (a mixture engine never held a record of this kind: none available, none to read)
+        if (count > 0) FAIL(e, GPE_ERR_STATE, "read_monitor: a mixture engine's records are struct gpe_mixture_observables (gpe_mixture_monitor_read)");
+        HIPCHK(e, hipStreamSynchronize(e->stream));
+        if (available) *available = 0;
+        return GPE_OK;
+    }
+    return monitor_read(e, first, count, out, available);
+}
+int gpe_mixture_monitor_read(gpe_engine* e, int64_t first, int64_t count, struct gpe_mixture_observables* out, int64_t* available) {
+    if (!e || first < 0 || count < 0 || (count > 0 && !out)) return GPE_ERR_INVALID;
+    if (!e->cfg.mixture) FAIL(e, GPE_ERR_STATE, "mixture_monitor_read: not a mixture engine (gpe_config.mixture; a scalar engine has gpe_read_monitor)");
+    return monitor_read(e, first, count, out, available);
 }
 
 // ---- the step ------------------------------------------------------------------------------------------

@@ -131,14 +131,15 @@ __global__ __launch_bounds__(OBS_THREADS) void k_obs_pass1(Phys ph, float base_n
 }
 
 // rows of a slab added in index order by ONE workgroup: thread t takes rows t, t + 256, ..., then the workgroup tree
-template <int K>
+// (ROW: doubles per slab row -- the mixture chain of gpe_observe_mix.h has a longer row)
+template <int K, int ROW = OB_ROW>
 GPE_DEV double obs_slab_total(const double* __restrict__ slab, int rows, int nsum, double* lds) {
     double v[K];
 #pragma unroll
     for (int k = 0; k < K; ++k) v[k] = 0.0;
     for (int r = threadIdx.x; r < rows; r += OBS_THREADS) {
 #pragma unroll
-        for (int k = 0; k < K; ++k) { const double q = slab[(size_t)r * OB_ROW + k]; v[k] = k < nsum ? v[k] + q : fmax(v[k], q); }
+        for (int k = 0; k < K; ++k) { const double q = slab[(size_t)r * ROW + k]; v[k] = k < nsum ? v[k] + q : fmax(v[k], q); }
     }
     return obs_block_reduce<K>(v, nsum, lds);
 }
@@ -239,34 +240,37 @@ __global__ __launch_bounds__(OBS_THREADS) void k_obs_finish(Phys ph, const doubl
     *dst = o;
 }
 
-// ---- keeper (gpe_bind_keeper): the best parameters by one field of the monitor's records, kept on the device ------------------------------
+// ---- keeper (gpe_bind_keeper, gpe_mixture_keeper): the best parameters by one field of the monitor's records, kept on the device ------------
+// The record is struct gpe_observables or struct gpe_mixture_observables: all doubles, at most KEEP_REC_MAX of them, so the keeper
+// handles it as rec_doubles doubles, one per lane of its wave.
 // Two launches directly behind k_obs_finish on the engine's stream, never captured:
 //   k_keep_decide  one wave reads the ring slot just written, applies the rule (gpe_pinn/keeper.py restates it), files the record and
 //                  the counters, raises or clears the copy flag, and fires the optimiser's own stop (od->stopped) when patience runs out
 //   k_keep_copy    theta -> theta_best where the flag is raised.  A launch of its own: the stream orders it behind the decision, so no
 //                  workgroup can see a half-written flag; its grid is a function of P alone
+#define KEEP_REC_MAX 64
 struct KeepDev {
     double best;                  // metric of the kept record (+inf: nothing kept)
-    struct gpe_observables rec;   // the kept record
+    double rec[KEEP_REC_MAX];     // the kept record (its first rec_doubles doubles)
     long long seen, kept, since_best;      // records judged / records kept / records since the last one kept
     int copy;                     // this record improves: k_keep_copy copies
     int stopped;                  // the keeper's patience fired the stop
 };
-#define KEEP_REC_DOUBLES ((int)(sizeof(struct gpe_observables) / sizeof(double)))
+static_assert(sizeof(struct gpe_observables) <= KEEP_REC_MAX * sizeof(double) && sizeof(struct gpe_mixture_observables) <= KEEP_REC_MAX * sizeof(double),
+              "the keeper files one double of the record per lane");
 #define KEEP_THREADS 256
 #define KEEP_MAX_WG 256
 
 // field: index of the chosen double in the record.  Lower is better; a non-finite candidate is no improvement.
-__global__ __launch_bounds__(64) void k_keep_decide(const struct gpe_observables* __restrict__ slot, int field, double min_delta,
+__global__ __launch_bounds__(64) void k_keep_decide(const double* __restrict__ src, int field, int rec_doubles, double min_delta,
                                                     long long patience, KeepDev* __restrict__ kd, OptDev* __restrict__ od) {
     const int t = threadIdx.x;
-    const double* src = (const double*)slot;
     // every lane reads what the rule needs before any lane writes
     const double m = src[field], best = kd->best;
-    const double mine = t < KEEP_REC_DOUBLES ? src[t] : 0.0;
+    const double mine = t < rec_doubles ? src[t] : 0.0;
     const long long since = kd->since_best;
     const bool better = isfinite(m) && m < best - min_delta;
-    if (better && t < KEEP_REC_DOUBLES) ((double*)&kd->rec)[t] = mine;      // the record, one double per lane
+    if (better && t < rec_doubles) kd->rec[t] = mine;                        // the record, one double per lane
     if (t != 0) return;
     const long long since_new = better ? 0 : since + 1;
     if (better) { kd->best = m; kd->kept += 1; }

@@ -662,19 +662,21 @@ class Engine:
         self._keep.pop("mon_x", None); self._keep.pop("mon_V", None)
 
     def monitor_available(self) -> int:
-        """Records appended since bind_monitor (synchronises); the ring keeps the newest `capacity` of them."""
+        """Records appended since bind_monitor / bind_mixture_monitor (synchronises); the ring keeps the newest `capacity` of them."""
         n = C.c_int64()
-        self._chk(self.lib.gpe_read_monitor(self._h, 0, 0, None, C.byref(n)))
+        read = self.lib.gpe_mixture_monitor_read if self.cfg.mixture else self.lib.gpe_read_monitor
+        self._chk(read(self._h, 0, 0, None, C.byref(n)))
         return int(n.value)
 
-    def _read_monitor_raw(self, first, count):
+    def _read_monitor_raw(self, first, count, mixture=False):
         avail = self.monitor_available()
         if count is None:                                   # everything from `first` on that the ring still holds
             first = max(int(first), avail - getattr(self, "_mon_cap", 4096), 0)
             count = max(avail - first, 0)
-        arr = (capi.gpe_observables * max(int(count), 1))()
+        arr = ((capi.gpe_mixture_observables if mixture else capi.gpe_observables) * max(int(count), 1))()
         if count > 0:
-            self._chk(self.lib.gpe_read_monitor(self._h, int(first), int(count), arr, None))
+            read = self.lib.gpe_mixture_monitor_read if mixture else self.lib.gpe_read_monitor
+            self._chk(read(self._h, int(first), int(count), arr, None))
         return arr, int(count)
 
     def read_monitor(self, first: int = 0, count=None):
@@ -689,6 +691,56 @@ class Engine:
 
     # ---- keeper: the best parameters by the held-out monitor, kept on the device (include/gpe_hip.h: gpe_bind_keeper) -------------------
     KEEP_METRICS = {"res_rms": capi.KEEP_RES_RMS, "energy": capi.KEEP_ENERGY}
+
+    # ---- mixture engines: observables, held-out monitor (include/gpe_hip.h: struct gpe_mixture_observables) -------------------------------
+    MIXTURE_OBSERVABLE_FIELDS = ("n", "dv", "step", "norm1", "norm2", "kin1", "kin2", "pot1", "pot2", "inter11", "inter22", "inter12", "energy",
+                                 "mu1", "mu2", "mu_lap1", "mu_lap2", "overlap") + \
+        tuple(f"{k}{a}_{j}" for k in ("mean_x", "var_x") for a in (1, 2) for j in range(3)) + \
+        ("peak_density1", "peak_density2", "res_rms1", "res_rms2", "res_rms_total")
+
+    def mixture_observables(self, x=None, V=None, dv=None) -> dict:
+        """Norms, energy parts, mu_a, overlap, moments, peak densities and residuals of the two-component state normalised to the target
+        norms, on the points x (None: the bound collocation points with their bound potential and weights); dv: quadrature weight
+        (None: cfg.dx).  Two-entry lists per component, inter = [11, 22, 12], mean_x / var_x [component][axis].  What
+        tools/accuracy_mixture.py:state used to form on the host."""
+        out = capi.gpe_mixture_observables()
+        if x is None:
+            self._chk(self.lib.gpe_mixture_observables(self._h, None, 0, None, float(self.cfg.dx if dv is None else dv), C.byref(out)))
+        else:
+            x, Vt, dv = self._obs_args(x, V, dv, "obs")
+            self._chk(self.lib.gpe_mixture_observables(self._h, C.c_void_p(x.data_ptr()), x.shape[0],
+                                                       C.c_void_p(Vt.data_ptr()) if Vt is not None else None, dv, C.byref(out)))
+        return out.as_dict()
+
+    def bind_mixture_monitor(self, x, every: int, V=None, dv=None, capacity: int = 0):
+        """bind_monitor for a mixture engine: after every `every`-th step enqueued by step() / run() the mixture observables on x are
+        appended to a device ring (capacity 0: 4096 records) with no host synchronisation; read them with read_mixture_monitor()."""
+        if x is None or every <= 0:
+            return self.clear_monitor()
+        x, Vt, dv = self._obs_args(x, V, dv, "mon")
+        self._chk(self.lib.gpe_mixture_monitor(self._h, C.c_void_p(x.data_ptr()), x.shape[0],
+                                               C.c_void_p(Vt.data_ptr()) if Vt is not None else None, dv, int(every), int(capacity)))
+        self._mon_cap = int(capacity) if capacity > 0 else 4096
+
+    def read_mixture_monitor(self, first: int = 0, count=None):
+        """Mixture monitor records [first, first+count) (0-based since bind_mixture_monitor; count None: up to the newest) as dicts."""
+        arr, count = self._read_monitor_raw(first, count, mixture=True)
+        return [arr[i].as_dict() for i in range(count)]
+
+    def read_mixture_monitor_array(self, first: int = 0, count=None) -> np.ndarray:
+        """The same records as one float64 array [count, len(MIXTURE_OBSERVABLE_FIELDS)]."""
+        arr, count = self._read_monitor_raw(first, count, mixture=True)
+        return np.frombuffer(arr, dtype=np.float64).reshape(-1, len(self.MIXTURE_OBSERVABLE_FIELDS))[:count].copy()
+
+    def bind_mixture_keeper(self, metric: str = "res_rms", min_delta: float = 0.0, patience: int = 0):
+        """bind_keeper for a mixture engine: judges the mixture monitor's records by "res_rms" (res_rms_total) or "energy".  Needs
+        bind_mixture_monitor first; keeper_state(), best_params(), best_record() (the mixture record) and restore_best() serve it."""
+        if metric not in self.KEEP_METRICS:
+            raise ValueError(f"metric: one of {sorted(self.KEEP_METRICS)}")
+        self._chk(self.lib.gpe_mixture_keeper(self._h, self.KEEP_METRICS[metric], float(min_delta), int(patience)))
+
+    def _keeper_read(self, *args):
+        return (self.lib.gpe_mixture_keeper_read if self.cfg.mixture else self.lib.gpe_keeper_read)(self._h, *args)
 
     def bind_keeper(self, metric: str = "res_rms", min_delta: float = 0.0, patience: int = 0):
         """After every monitor record the engine compares `metric` ("res_rms" or "energy", lower is better) with the best so far and, on
@@ -706,19 +758,19 @@ class Engine:
         """dict(seen, kept, since_best, stopped): records judged, records kept, records since the last one kept, and whether the keeper's
         patience stopped the optimiser; synchronises."""
         seen, kept, since, stopped = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int()
-        self._chk(self.lib.gpe_keeper_read(self._h, None, 0, None, C.byref(seen), C.byref(kept), C.byref(since), C.byref(stopped)))
+        self._chk(self._keeper_read(None, 0, None, C.byref(seen), C.byref(kept), C.byref(since), C.byref(stopped)))
         return dict(seen=int(seen.value), kept=int(kept.value), since_best=int(since.value), stopped=bool(stopped.value))
 
     def best_params(self) -> np.ndarray:
         """The kept parameters (layout of get_params); GPEError while nothing is kept."""
         a = np.empty(self.n_params, dtype=np.float32)
-        self._chk(self.lib.gpe_keeper_read(self._h, a.ctypes.data_as(C.c_void_p), a.size, None, None, None, None, None))
+        self._chk(self._keeper_read(a.ctypes.data_as(C.c_void_p), a.size, None, None, None, None, None))
         return a
 
     def best_record(self) -> dict:
-        """The monitor record of the kept parameters, as read_monitor gives records."""
-        out = capi.gpe_observables()
-        self._chk(self.lib.gpe_keeper_read(self._h, None, 0, C.byref(out), None, None, None, None))
+        """The monitor record of the kept parameters, as read_monitor (a mixture engine: read_mixture_monitor) gives records."""
+        out = capi.gpe_mixture_observables() if self.cfg.mixture else capi.gpe_observables()
+        self._chk(self._keeper_read(None, 0, C.byref(out), None, None, None, None))
         return out.as_dict()
 
     def restore_best(self):

@@ -194,11 +194,40 @@ struct gpe_observables {
     double res_rms;              /* sqrt(dv * sum |H[phi] phi - mu phi|^2), phi = u / sqrt(I): the residual of the normalised state (two-pass) */
 };
 
+/* Observables of a two-component mixture state on a point set, formed on the device (gpe_mixture_observables, the mixture monitor's
+ * ring, the mixture keeper's record).  Replaces the host-side sums of tools/accuracy_mixture.py:state (jets copied to the host, numpy);
+ * the reference has no counterpart.  u_a are the two real order parameters as k_head_mix forms them (perturb_scale included),
+ * c = kinetic_coeff, dv the quadrature weight, (n_1, n_2) = mix_norm, (g_11, g_22, g_12) the couplings in force at the call.  Raw point
+ * sums (times q_i on the bound set under gpe_bind_weights):
+ *   s_a = sum u_a^2,  K_a = sum |grad u_a|^2,  P_a = sum V u_a^2,  L_a = sum u_a lap u_a,  Q_ab = sum u_a^2 u_b^2,   I_a = dv s_a
+ * Every field but `norm` describes the state NORMALISED TO THE TARGET NORMS, v_a = u_a sqrt(n_a / I_a) -- the convention of the mixture
+ * energy term (gpe_mixture_energy_weight): `energy` is that term's E with dx = dv, and no field changes when a component is scaled.
+ * All doubles, at most 64 of them (the keeper files one double per lane of a wave).  Sums in fp64 from the fp32 jets, added in a fixed
+ * order (no atomics): a record repeats bit for bit.  Single-rank semantics, as struct gpe_observables.
+ * (No typedef of its own name, for the reason given there: write `struct gpe_mixture_observables`.) */
+struct gpe_mixture_observables {
+    double n, dv, step;          /* points, quadrature weight, optimiser step of the parameters evaluated (device-side value) */
+    double norm[2];              /* I_a of the RAW state */
+    double kin[2];               /* c n_a K_a / s_a */
+    double pot[2];               /* n_a P_a / s_a */
+    double inter[3];             /* (11, 22, 12): 1/2 g_11 n_1^2 Q_11 / (s_1^2 dv), 1/2 g_22 n_2^2 Q_22 / (s_2^2 dv), g_12 n_1 n_2 Q_12 / (s_1 s_2 dv) */
+    double energy;               /* the sum of the seven fields above */
+    double mu[2];                /* c K_a/s_a + P_a/s_a + g_aa n_a Q_aa / (s_a^2 dv) + g_12 n_b Q_12 / (s_1 s_2 dv), b the other component;
+                                  * sum_a n_a mu_a = energy + inter[0] + inter[1] + inter[2] */
+    double mu_lap[2];            /* mu with the kinetic part taken as -c L_a / s_a */
+    double overlap;              /* Q_12 / sqrt(Q_11 Q_22): 0 when phase-separated, 1 when the densities are proportional */
+    double mean_x[2][3], var_x[2][3];   /* density-weighted centre and variance per component and axis (unused axes 0) */
+    double peak_density[2];      /* n_a max u_a^2 / I_a */
+    double res_rms[2];           /* sqrt(dv sum |H_a[v] v_a - mu_a v_a|^2): the residual of the normalised state (two-pass) */
+    double res_rms_total;        /* sqrt(res_rms[0]^2 + res_rms[1]^2) */
+};
+
 /* ---- lifetime ------------------------------------------------------------------------------ */
 int gpe_abi_version(void);
 size_t gpe_sizeof_config(void);   /* sizeof(gpe_config)  -- lets a foreign-language binding verify its struct layout */
 size_t gpe_sizeof_scalars(void);  /* sizeof(gpe_scalars) */
 size_t gpe_sizeof_observables(void);   /* sizeof(struct gpe_observables) */
+size_t gpe_sizeof_mixture_observables(void);   /* sizeof(struct gpe_mixture_observables) */
 /* replaces: GrossPitaevskiiPINN(...).to(device) + torch.optim.Adam(...) + scheduler construction
  * (refine/harmonic_pinn_simulation.py:295,309-314 ; nb c10:L63,L73-78) */
 int gpe_create(const gpe_config* cfg, int device, void* hip_stream, gpe_engine** out);
@@ -431,6 +460,28 @@ int gpe_keeper_read(gpe_engine* e, float* h_flat, size_t n, struct gpe_observabl
 /* The kept parameters become the engine's parameters (device copy, then as gpe_set_params: the packed weight copies are rebuilt
  * before their next use).  Adam moments, scheduler state and the stop flag stay as they are.  GPE_ERR_INVALID: nothing kept yet. */
 int gpe_keeper_restore(gpe_engine* e);
+
+/* ---- mixture engines: observables, held-out monitor and keeper (replaces tools/accuracy_mixture.py:state; no reference counterpart) ----
+ * The entry points above keep refusing a mixture engine (GPE_ERR_STATE): their record has one norm, one mu and reads two outputs as
+ * complex psi.  These five are their mixture instances -- same launch chain with a record of its own (csrc/gpe_observe_mix.h), same
+ * lifetime rules -- and return GPE_ERR_STATE on an engine that is not a mixture.  gpe_keeper_restore serves both kinds of engine; on a
+ * mixture engine gpe_read_monitor with count > 0 and gpe_keeper_read with rec != NULL return GPE_ERR_STATE (the records are of the other type).
+ * gpe_mixture_observables: as gpe_observables (d_x == NULL: the bound collocation points, their bound potential and, under
+ * gpe_bind_weights, their weights in every sum -- peak_density stays the plain maximum; an explicit set is unweighted).  The couplings
+ * and target norms are read at the launch: a gpe_set_mixture between two records shows in the next one. */
+int gpe_mixture_observables(gpe_engine* e, const float* d_x, int64_t n, const float* d_V, float dv, struct gpe_mixture_observables* out);
+/* Held-out monitor of a mixture engine: gpe_bind_monitor's cadence, ring, graph cutting in gpe_run and validate-then-swap rules, with
+ * records of struct gpe_mixture_observables (unweighted).  d_x == NULL or every <= 0 clears it (and disarms the keeper). */
+int gpe_mixture_monitor(gpe_engine* e, const float* d_x, int64_t n, const float* d_V, float dv, int64_t every, int32_t capacity);
+/* as gpe_read_monitor */
+int gpe_mixture_monitor_read(gpe_engine* e, int64_t first, int64_t count, struct gpe_mixture_observables* out, int64_t* available);
+/* Keeper of a mixture engine: gpe_bind_keeper's rule, counters, patience stop, refusals (GPE_ERR_INVALID: no monitor bound, an unknown
+ * metric, min_delta < 0 or not finite, patience < 0, an engine with a communicator) and lifetime (a re-bind of the monitor restarts an
+ * armed keeper from "nothing kept").  The field judged: GPE_KEEP_RES_RMS res_rms_total, GPE_KEEP_ENERGY energy. */
+int gpe_mixture_keeper(gpe_engine* e, int metric, double min_delta, int64_t patience);
+/* as gpe_keeper_read, with the mixture record */
+int gpe_mixture_keeper_read(gpe_engine* e, float* h_flat, size_t n, struct gpe_mixture_observables* rec, int64_t* seen, int64_t* kept,
+                            int64_t* since_best, int* stopped);
 
 /* ---- training step: the epoch body refine/...:328-361 ; nb c10:L84-103 ------------------------------ */
 /* phase 1: forward jets + local sums  -> exchange buffer "sums" */
