@@ -170,6 +170,11 @@ SYMBOLS = {
     "gpe_mse_update": (_int, [_vp]),
     "gpe_mse_step": (_int, [_vp, _P(gpe_scalars)]),
     "gpe_mse_loss_grad": (_int, [_vp, _P(C.c_double)]),
+    "gpe_lbfgs_config": (_int, [_vp, C.c_double, _int, C.c_double, C.c_double, C.c_double]),
+    "gpe_lbfgs_update": (_int, [_vp]),
+    "gpe_lbfgs_run": (_int, [_vp, _i64, _int]),
+    "gpe_lbfgs_read": (_int, [_vp, _P(C.c_double)]),
+    "gpe_lbfgs_history": (_int, [_vp, _vp, _vp, _vp, _vp, C.c_size_t, _P(_int)]),
     "gpe_set_gamma": (_int, [_vp, _f]),
     "gpe_set_mixture": (_int, [_vp, _f, _f, _f]),
     "gpe_mixture_scalars": (_int, [_vp, _P(C.c_double)]),

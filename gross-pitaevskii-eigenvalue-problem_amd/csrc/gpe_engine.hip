@@ -37,6 +37,7 @@ typedef enum { ncclFloat = 7, ncclDouble = 8 } ncclDataType_t;
 #include "gpe_fused.h"
 #include "gpe_wide_api.h"
 #include "gpe_env.h"
+#include "gpe_lbfgs.h"
 
 static thread_local std::string g_create_error;
 
@@ -680,6 +681,15 @@ struct gpe_engine {
     double wq_local = 0.0, wq_total = 0.0;            // sum of this rank's weights / W over all ranks
     float mix_wE = 0.f;                               // mixture energy term (gpe_mixture_energy_weight): its weight, 0 = the plain mixture step
     double* wq_red = nullptr;                         // [2] output of k_weight_total, allocated at the first bind
+    // device-resident L-BFGS (gpe_lbfgs.h): every buffer allocated by gpe_lbfgs_config, freed with the engine
+    struct Lbfgs {
+        bool on = false;
+        LbfgsCfg cfg = {};
+        int ld = 0, n_part = 0;
+        float *S = nullptr, *Y = nullptr, *g_prev = nullptr, *d = nullptr;      // rings [m][ld]; [P] each
+        double *part = nullptr, *SY = nullptr, *YY = nullptr, *ro = nullptr, *coef = nullptr;
+        LbfgsDev* st = nullptr;
+    } lb;
     StepState st;
     std::string err;
     double* sums() { return dbl; }
@@ -1468,6 +1478,23 @@ static void fill_phys(gpe_engine* e) {
     mx.wE = c.mixture ? e->mix_wE : 0.f;
 }
 
+// device-resident L-BFGS (gpe_lbfgs.h): its state is reset with the optimiser and whenever the parameters are replaced
+static int lbfgs_reset(gpe_engine* e) {
+    if (!e->lb.st) return GPE_OK;
+    LbfgsDev h;
+    memset(&h, 0, sizeof h);
+    h.H_diag = 1.0; h.prev_loss = INFINITY;
+    HIPCHK(e, hipMemcpyAsync(e->lb.st, &h, sizeof h, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    return GPE_OK;
+}
+
+static void lbfgs_free(gpe_engine* e) {
+    void* ps[] = {e->lb.S, e->lb.Y, e->lb.g_prev, e->lb.d, e->lb.part, e->lb.SY, e->lb.YY, e->lb.ro, e->lb.coef, e->lb.st};
+    for (void* p : ps) if (p) (void)hipFree(p);
+    e->lb = gpe_engine::Lbfgs();
+}
+
 static int reset_opt(gpe_engine* e, float lr) {
     OptDev h;
     memset(&h, 0, sizeof h);
@@ -1477,7 +1504,7 @@ static int reset_opt(gpe_engine* e, float lr) {
     HIPCHK(e, hipMemsetAsync(e->am, 0, (size_t)e->P * sizeof(float), e->stream));
     HIPCHK(e, hipMemsetAsync(e->av, 0, (size_t)e->P * sizeof(float), e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));
-    return GPE_OK;
+    return lbfgs_reset(e);
 }
 
 // ---- engine creation, phase by phase (gpe_create calls each once, in this order) -------------------------------------------------------
@@ -1925,6 +1952,7 @@ void gpe_destroy(gpe_engine* e) {
     if (e->ext_exchange) { e->grad = nullptr; e->dbl = nullptr; }
     void* ps[] = {e->theta, e->am, e->av, e->grad, e->dbl, e->od, e->hist, e->last, (void*)e->orth_dev, e->Wpk, e->WpkT, e->gslab, e->gslab_bc, e->grad_bc, (void*)e->upd_snap, (void*)e->head_slots, (void*)e->upd_ticket, (void*)e->upd_snap_small, (void*)e->obs_buf, (void*)e->obs_out, (void*)e->mon_ring, (void*)e->smp_x, (void*)e->theta_best, (void*)e->keep_dev, (void*)e->smp_edges, (void*)e->smp_q, (void*)e->wq_red, (void*)e->smp_ad.mass, (void*)e->smp_ad.count, (void*)e->smp_ad.off, (void*)e->smp_ad.share, (void*)e->smp_vol, (void*)e->smp_resid};
     for (void* p : ps) if (p) (void)hipFree(p);
+    lbfgs_free(e);
     delete e;
 }
 
@@ -1961,7 +1989,7 @@ int gpe_set_params(gpe_engine* e, const float* h, size_t n) {
     if (rc) return rc;
     HIPCHK(e, hipStreamSynchronize(e->stream));
     e->packed_dirty = true;
-    return GPE_OK;
+    return lbfgs_reset(e);                        // new parameters: the curvature pairs belong to the old ones
 }
 int gpe_get_params(gpe_engine* e, float* h, size_t n) {
     if (!e || !h) return GPE_ERR_INVALID;
@@ -2922,7 +2950,7 @@ int gpe_keeper_restore(gpe_engine* e) {
     HIPCHK(e, hipMemcpyAsync(e->theta, e->theta_best, (size_t)e->P * 4, hipMemcpyDeviceToDevice, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));
     e->packed_dirty = true;                           // as gpe_set_params: the packed weight copies are rebuilt before their next use
-    return GPE_OK;
+    return lbfgs_reset(e);
 }
 
 // k steps were just enqueued (never past a monitor step: gpe_run cuts there).  On a monitor step: forward of the monitor points with the
@@ -3254,6 +3282,116 @@ int gpe_mse_loss_grad(gpe_engine* e, double* loss) {
     HIPCHK(e, hipMemcpyAsync(&sc, e->last, sizeof sc, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));
     if (loss) *loss = sc.loss;
+    return GPE_OK;
+}
+
+
+// ---- device-resident L-BFGS (gpe_lbfgs.h; torch.optim.LBFGS without a line search, flattened) ---------------------------------------
+// One iteration = the evaluation the caller enqueued (gpe_step_begin + gpe_step_backward, or gpe_mse_begin) + the record launch (the
+// update kernel with do_update = 0: the loss L-BFGS sees IS the one k_update records, the step sums are consumed, Adam's state is not
+// touched) + k_lbfgs_dots, k_lbfgs_coef, k_lbfgs_apply.  Nothing synchronises.  The packed weight copies are refreshed as after the
+// multi-workgroup Adam update: the next step's k_begin repacks (packed_dirty).
+int gpe_lbfgs_config(gpe_engine* e, double lr, int history, double tolerance_grad, double tolerance_change, double stop_loss) {
+    if (!e) return GPE_ERR_INVALID;
+    if (history < 1 || history > LBFGS_MAX_HISTORY) FAIL(e, GPE_ERR_INVALID, "lbfgs_config: history must be in [1,%d], got %d", LBFGS_MAX_HISTORY, history);
+    if (!(__builtin_isfinite(lr) && lr > 0.0)) FAIL(e, GPE_ERR_INVALID, "lbfgs_config: lr must be finite and positive");
+    if (!(__builtin_isfinite(tolerance_grad) && tolerance_grad >= 0.0) || !(__builtin_isfinite(tolerance_change) && tolerance_change >= 0.0) ||
+        !(__builtin_isfinite(stop_loss) && stop_loss >= 0.0))
+        FAIL(e, GPE_ERR_INVALID, "lbfgs_config: tolerance_grad, tolerance_change and stop_loss must be finite and not negative");
+    if (e->cfg.world_size > 1 || e->comm) FAIL(e, GPE_ERR_INVALID, "lbfgs_config: a data-parallel engine has no L-BFGS (the history is per rank)");
+    if (!e->lb.st || e->lb.cfg.m != history) {
+        HIPCHK(e, hipStreamSynchronize(e->stream));
+        lbfgs_free(e);
+        const int m = history;
+        e->lb.ld = (int)round_up(e->P, 64);
+        e->lb.n_part = lbfgs_grid(e->P);
+        int rc;
+        if ((rc = dev_alloc(e, nullptr, &e->lb.S, (size_t)m * e->lb.ld)) || (rc = dev_alloc(e, nullptr, &e->lb.Y, (size_t)m * e->lb.ld)) ||
+            (rc = dev_alloc(e, nullptr, &e->lb.g_prev, (size_t)e->lb.ld)) || (rc = dev_alloc(e, nullptr, &e->lb.d, (size_t)e->lb.ld)) ||
+            (rc = dev_alloc(e, nullptr, &e->lb.part, (size_t)e->lb.n_part * lbfgs_row(m))) ||
+            (rc = dev_alloc(e, nullptr, &e->lb.SY, (size_t)m * m)) || (rc = dev_alloc(e, nullptr, &e->lb.YY, (size_t)m * m)) ||
+            (rc = dev_alloc(e, nullptr, &e->lb.ro, (size_t)m)) || (rc = dev_alloc(e, nullptr, &e->lb.coef, (size_t)2 * m + 1)) ||
+            (rc = dev_alloc(e, nullptr, &e->lb.st, (size_t)1))) { lbfgs_free(e); return rc; }
+    }
+    e->lb.cfg = LbfgsCfg{lr, tolerance_grad, tolerance_change, stop_loss, history};
+    e->lb.on = true;
+    return lbfgs_reset(e);
+}
+
+static int lbfgs_refusals(gpe_engine* e, const char* who) {
+    if (!e->lb.on) FAIL(e, GPE_ERR_STATE, "%s: L-BFGS is not configured (gpe_lbfgs_config)", who);
+    if (e->smp_every > 0) FAIL(e, GPE_ERR_STATE, "%s: a sampler with every > 0 is bound, the objective would change under the history", who);
+    if (e->comm) FAIL(e, GPE_ERR_STATE, "%s: the engine has a communicator, L-BFGS is single-rank", who);
+    return GPE_OK;
+}
+
+int gpe_lbfgs_update(gpe_engine* e) {
+    if (!e) return GPE_ERR_INVALID;
+    int rc;
+    if ((rc = lbfgs_refusals(e, "lbfgs_update"))) return rc;
+    if (e->st.phase != 2 && e->st.phase != 3) FAIL(e, GPE_ERR_STATE, "lbfgs_update without step_backward or mse_begin");
+    const int mse = e->st.phase == 3;
+    StepScope seq{e};               // the step ends here
+    launch_update(e, e->grad, e->sums(), e->lsums(), mse ? 0.0 : bc_count(e), /*do_update=*/0, mse, nullptr);
+    HIPCHK(e, hipGetLastError());
+    const int m = e->lb.cfg.m;
+    hipLaunchKernelGGL(k_lbfgs_dots, dim3(e->lb.n_part), dim3(64), 0, e->stream, e->P, e->lb.ld, m, (const float*)e->grad, (const float*)e->lb.g_prev,
+                       (const float*)e->lb.d, (const float*)e->lb.S, (const float*)e->lb.Y, (const LbfgsDev*)e->lb.st, e->lb.part);
+    hipLaunchKernelGGL(k_lbfgs_coef, dim3(1), dim3(256), 0, e->stream, m, e->lb.n_part, e->lb.cfg, e->lb.st, (const double*)e->lb.part, e->lb.SY,
+                       e->lb.YY, e->lb.ro, e->lb.coef, (const gpe_scalars*)e->last);
+    hipLaunchKernelGGL(k_lbfgs_apply, dim3(cdiv(e->P, 256)), dim3(256), 0, e->stream, e->P, e->lb.ld, m, (const float*)e->grad, e->lb.g_prev, e->lb.d,
+                       e->lb.S, e->lb.Y, e->theta, (const LbfgsDev*)e->lb.st, (const double*)e->lb.coef);
+    HIPCHK(e, hipGetLastError());
+    after_update(e);
+    e->packed_dirty = e->path == GPE_PATH_FUSED;      // theta moved behind the record launch's repack: the next k_begin repacks
+    return GPE_OK;
+}
+
+int gpe_lbfgs_run(gpe_engine* e, int64_t n_iters, int mse) {
+    if (!e || n_iters < 0) return GPE_ERR_INVALID;
+    int rc;
+    if ((rc = lbfgs_refusals(e, "lbfgs_run"))) return rc;
+    for (int64_t i = 0; i < n_iters; ++i) {
+        if (mse) rc = gpe_mse_begin(e);
+        else if (!(rc = step_begin(e, StepOpts{}))) rc = step_backward(e, StepOpts{});
+        if (!rc) rc = gpe_lbfgs_update(e);
+        if (rc) return rc;
+    }
+    return GPE_OK;
+}
+
+int gpe_lbfgs_read(gpe_engine* e, double out[16]) {
+    if (!e || !out) return GPE_ERR_INVALID;
+    if (!e->lb.on) FAIL(e, GPE_ERR_STATE, "lbfgs_read: L-BFGS is not configured (gpe_lbfgs_config)");
+    static_assert(LBR_FIELDS == 16, "gpe_lbfgs_read record");
+    LbfgsDev h;
+    HIPCHK(e, hipMemcpyAsync(&h, e->lb.st, sizeof h, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    memcpy(out, h.rec, sizeof h.rec);
+    // the state as it stands (a reset clears it; the record fields of the last iteration would be stale then)
+    out[LBR_N_ITER] = (double)h.n_iter; out[LBR_COUNT] = h.count; out[LBR_FROZEN] = h.frozen; out[LBR_HEAD] = h.head; out[LBR_H_DIAG] = h.H_diag;
+    out[LBR_T] = h.t; out[LBR_PREV_LOSS] = h.prev_loss;
+    return GPE_OK;
+}
+
+int gpe_lbfgs_history(gpe_engine* e, float* h_S, float* h_Y, float* h_g_prev, float* h_d, size_t n, int* count) {
+    if (!e) return GPE_ERR_INVALID;
+    if (!e->lb.on) FAIL(e, GPE_ERR_STATE, "lbfgs_history: L-BFGS is not configured (gpe_lbfgs_config)");
+    if ((int64_t)n != e->P_user) FAIL(e, GPE_ERR_INVALID, "lbfgs_history: rows of %zu floats, model has %d", n, e->P_user);
+    LbfgsDev h;
+    HIPCHK(e, hipMemcpyAsync(&h, e->lb.st, sizeof h, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    const int m = e->lb.cfg.m;
+    int rc;
+    for (int a = 0; a < h.count; ++a) {               // age order: row 0 is the oldest pair
+        const int j = (h.head - h.count + a + m) % m;
+        if (h_S && (rc = flat_from_device(e, e->lb.S + (size_t)j * e->lb.ld, h_S + (size_t)a * n))) return rc;
+        if (h_Y && (rc = flat_from_device(e, e->lb.Y + (size_t)j * e->lb.ld, h_Y + (size_t)a * n))) return rc;
+    }
+    if (h_g_prev && (rc = flat_from_device(e, e->lb.g_prev, h_g_prev))) return rc;
+    if (h_d && (rc = flat_from_device(e, e->lb.d, h_d))) return rc;
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    if (count) *count = h.count;
     return GPE_OK;
 }
 

@@ -793,6 +793,46 @@ class Engine:
         self._chk(self.lib.gpe_mse_loss_grad(self._h, C.byref(loss)))
         return loss.value, self.get_grad()
 
+    # ---- device-resident L-BFGS (torch.optim.LBFGS without a line search, flattened: include/gpe_hip.h) -----------------------
+    LBFGS_FIELDS = ("loss", "grad_max", "grad_l1", "t", "gtd", "n_iter", "count", "frozen", "skipped", "pushed", "ys", "H_diag", "head",
+                    "prev_loss")
+
+    def lbfgs_config(self, lr: float, history: int = 100, tolerance_grad: float = 1e-7, tolerance_change: float = 1e-9,
+                     stop_loss: float = 0.0):
+        """Configure (torch's defaults) and reset the L-BFGS state.  The state freezes for good at max|g| <= tolerance_grad, on a
+        non-finite loss or gradient, or at loss < stop_loss."""
+        self._chk(self.lib.gpe_lbfgs_config(self._h, float(lr), int(history), float(tolerance_grad), float(tolerance_change),
+                                            float(stop_loss)))
+        self._lbfgs_history = int(history)
+
+    def lbfgs_update(self):
+        """One L-BFGS iteration behind step_backward() (or the engine's mse begin phase), in place of step_update()."""
+        self._chk(self.lib.gpe_lbfgs_update(self._h))
+
+    def lbfgs_run(self, n_iters: int, mse: bool = False):
+        """n_iters iterations "evaluate, iterate" enqueued back to back; no host synchronisation.  mse: the pre-training loss
+        (bind_target).  The monitor and the keeper are not served."""
+        self._chk(self.lib.gpe_lbfgs_run(self._h, int(n_iters), 1 if mse else 0))
+
+    def lbfgs_read(self) -> dict:
+        out = (C.c_double * 16)()
+        self._chk(self.lib.gpe_lbfgs_read(self._h, out))
+        r = dict(zip(self.LBFGS_FIELDS, out))
+        for k in ("n_iter", "count", "frozen", "skipped", "pushed", "head"):
+            r[k] = int(r[k])
+        return r
+
+    def lbfgs_history(self):
+        """(S, Y, g_prev, d): the pairs held, oldest first ([count, P]), the previous gradient and the direction ([P]); fp32."""
+        m, P = getattr(self, "_lbfgs_history", 0), self.n_params
+        S = np.zeros((max(m, 1), P), np.float32)
+        Y = np.zeros((max(m, 1), P), np.float32)
+        gp, d = np.zeros(P, np.float32), np.zeros(P, np.float32)
+        n = C.c_int()
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        self._chk(self.lib.gpe_lbfgs_history(self._h, vp(S), vp(Y), vp(gp), vp(d), P, C.byref(n)))
+        return S[:n.value].copy(), Y[:n.value].copy(), gp, d
+
     # ---- continuation knobs --------------------------------------------------------------------------------------------
     def set_gamma(self, g: float):
         self.cfg.gamma = float(g)

@@ -664,10 +664,17 @@ def _refine_advanced_initialization(m, mode):
         m._engine.set_params(m._flat)
 
 
-def _refine_pretrain(model, mode, X_train, epochs=5000, lr=1e-3, verbose=False):
+def _refine_pretrain(model, mode, X_train, epochs=5000, lr=1e-3, verbose=False, lbfgs="host"):
     """pretrain_on_analytical_solution (refine/harmonic_pinn_simulation.py:650-701): fit the network output to phi_mode(x).
     Adam phase (epochs-500 iterations, plain Adam, no clipping) on the engine; then the reference's L-BFGS tail
-    (torch.optim.LBFGS(lr*0.1, max_iter=20), 500 outer iterations) driven host-side on the engine's loss/gradient."""
+    (torch.optim.LBFGS(lr*0.1, max_iter=20), 500 outer iterations).  lbfgs="host" (default): torch's optimiser driven host-side on
+    the engine's loss/gradient.  lbfgs="device": the same iteration on the device (Engine.lbfgs_run: 20 flat iterations per outer
+    iteration, torch's default history and tolerances, no host round trip); the stop at loss < 1e-12 is then checked at EVERY
+    iteration, not once per 20, and freezes the parameters where it fires.
+    model.pretrain_loss is stale by one update on either path: "host" reports torch's return value, the loss of the FIRST evaluation of the
+    last outer call (up to 20 updates old); "device" reports the record of the last iteration, the loss evaluated before its update."""
+    if lbfgs not in ("host", "device"):
+        raise ValueError(f"lbfgs must be 'host' or 'device', got {lbfgs!r}")
     X = _as_np(X_train).astype(np.float32)
     dev = _device()
     X_dev = torch.as_tensor(X, device=dev)
@@ -685,7 +692,11 @@ def _refine_pretrain(model, mode, X_train, epochs=5000, lr=1e-3, verbose=False):
             print(f"  Pre-training epoch {epoch}, loss: {loss:.2e}")
         if loss < 1e-12:
             break
-    if loss >= 1e-12 and epochs > n_adam:
+    if loss >= 1e-12 and epochs > n_adam and lbfgs == "device":
+        eng.lbfgs_config(lr * 0.1, history=100, tolerance_grad=1e-7, tolerance_change=1e-9, stop_loss=1e-12)
+        eng.lbfgs_run(20 * (epochs - n_adam), mse=True)
+        loss = eng.lbfgs_read()["loss"]
+    elif loss >= 1e-12 and epochs > n_adam:
         theta = torch.tensor(eng.get_params(), dtype=torch.float32, requires_grad=True)
         opt = torch.optim.LBFGS([theta], lr=lr * 0.1, max_iter=20)
 

@@ -541,6 +541,37 @@ int gpe_mse_update(gpe_engine* e);                   /* Adam on the exchanged gr
 int gpe_mse_step(gpe_engine* e, gpe_scalars* out);   /* begin + update + synchronise; out->loss = the MSE */
 int gpe_mse_loss_grad(gpe_engine* e, double* loss);
 
+/* ---- device-resident L-BFGS: torch.optim.LBFGS without a line search (the tail of pretrain_on_analytical_solution, refine/...:672-687,
+ * and of the 2D hybrid driver), with no host round trip per evaluation.  Without a line search torch's outer / inner loop is the flat
+ * sequence "evaluate loss and gradient, iterate": `max_iter` and `tolerance_change` only end an outer call, and the next call
+ * re-evaluates at the same parameters and carries on.  One iteration here is that pair: the evaluation's launches, then
+ *   y = g - g_prev, s = t d;  the pair is pushed only if y.s > 1e-10 (the oldest leaves at `history`), H = y.s / y.y;
+ *   d = -g, t = min(1, 1/|g|_1) lr on the first iteration; afterwards d = -H_k g by the two-loop recursion, t = lr;
+ *   no parameter update (everything else proceeds) if g.d > -tolerance_change;  theta += t d otherwise.
+ * The state FREEZES for good -- no byte of the parameters or of the L-BFGS state changes any more -- once max|g| <= tolerance_grad,
+ * the loss or the gradient is not finite, or loss < stop_loss (0: never).  The loss is the one the Adam update records: the physics
+ * total, or the MSE in pre-training mode.  Rings and directions are fp32, every reduction and the recursion fp64; results are the same
+ * bits from run to run.  Adam's moments, step count, schedulers and history are neither read nor written.
+ * gpe_lbfgs_config: allocates (first call, or a new `history`) and resets the L-BFGS state.  GPE_ERR_INVALID: history outside [1, 128],
+ *   lr not finite or <= 0, a tolerance or stop_loss negative or not finite, a data-parallel engine (world_size > 1 or a communicator).
+ * gpe_lbfgs_update: the third phase behind gpe_step_backward or gpe_mse_begin, in place of gpe_step_update / gpe_mse_update; reads the
+ *   gradient exchange buffer and its tail exactly as those do.
+ * gpe_lbfgs_run: n_iters iterations (mse != 0: of the pre-training loss, which needs gpe_bind_target) enqueued back to back with plain
+ *   launches; no host synchronisation, no graph capture.  The held-out monitor and the keeper are NOT served by it.
+ * gpe_lbfgs_read: synchronise; out = (loss, max|g|, |g|_1, t, g.d, n_iter, pairs held, frozen (0 no, 1 tolerance_grad, 2 non-finite,
+ *   3 stop_loss), skipped, pushed, y.s, H_diag, ring head, prev_loss, 0, 0): loss, the gradient norms, g.d, skipped, pushed and y.s are
+ *   the last iteration's, the rest the state as it stands.
+ * gpe_lbfgs_history: synchronise; the pairs held, oldest first, as rows of h_S / h_Y [history][n], g_prev and d [n], in the caller's
+ *   parameter layout (n = gpe_param_count); any pointer may be NULL.
+ * gpe_reset_optimizer, gpe_set_params and gpe_keeper_restore reset the L-BFGS state (the configuration stays).
+ * GPE_ERR_STATE (update, run): not configured; a sampler with every > 0 bound (the objective would change under the history);
+ * gpe_comm_init done.  (read, history): not configured. */
+int gpe_lbfgs_config(gpe_engine* e, double lr, int history, double tolerance_grad, double tolerance_change, double stop_loss);
+int gpe_lbfgs_update(gpe_engine* e);
+int gpe_lbfgs_run(gpe_engine* e, int64_t n_iters, int mse);
+int gpe_lbfgs_read(gpe_engine* e, double out[16]);
+int gpe_lbfgs_history(gpe_engine* e, float* h_S, float* h_Y, float* h_g_prev, float* h_d, size_t n, int* count);
+
 /* ---- continuation knobs: the gamma / perturbation loop of refine/...:289-340 -------------------------- */
 int gpe_set_gamma(gpe_engine* e, float gamma);
 /* mixture engines: the coupling matrix (g_11, g_22, g_12) of the NEXT step (gamma-continuation), like gpe_set_gamma: takes effect at the
