@@ -689,6 +689,9 @@ struct gpe_engine {
         float *S = nullptr, *Y = nullptr, *g_prev = nullptr, *d = nullptr;      // rings [m][ld]; [P] each
         double *part = nullptr, *SY = nullptr, *YY = nullptr, *ro = nullptr, *coef = nullptr;
         LbfgsDev* st = nullptr;
+        LsCfg ls = {};                                                            // strong-Wolfe line search (gpe_lbfgs_line_search); kind 0: none
+        float* ls_buf = nullptr;                                                  // [4][ld]: three trial-gradient slots, theta0
+        double* ls_part = nullptr;                                                // [n_part][LSD_COUNT]
     } lb;
     StepState st;
     std::string err;
@@ -1479,18 +1482,25 @@ static void fill_phys(gpe_engine* e) {
 }
 
 // device-resident L-BFGS (gpe_lbfgs.h): its state is reset with the optimiser and whenever the parameters are replaced
-static int lbfgs_reset(gpe_engine* e) {
+// theta_to_start: the caller does not rewrite theta, so a running line search is ended by putting theta back to its start point
+static int lbfgs_reset(gpe_engine* e, bool theta_to_start = false) {
     if (!e->lb.st) return GPE_OK;
+    if (theta_to_start && e->lb.ls.kind && e->lb.ls_buf) {
+        hipLaunchKernelGGL(k_ls_restore, dim3(cdiv(e->P, 256)), dim3(256), 0, e->stream, e->P, e->theta, (const LbfgsDev*)e->lb.st);
+        HIPCHK(e, hipGetLastError());
+        e->packed_dirty = true;
+    }
     LbfgsDev h;
     memset(&h, 0, sizeof h);
     h.H_diag = 1.0; h.prev_loss = INFINITY;
+    if (e->lb.ls_buf) { h.ls.slots = e->lb.ls_buf; h.ls.theta0 = e->lb.ls_buf + (size_t)LS_SLOTS * e->lb.ld; }
     HIPCHK(e, hipMemcpyAsync(e->lb.st, &h, sizeof h, hipMemcpyHostToDevice, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));
     return GPE_OK;
 }
 
 static void lbfgs_free(gpe_engine* e) {
-    void* ps[] = {e->lb.S, e->lb.Y, e->lb.g_prev, e->lb.d, e->lb.part, e->lb.SY, e->lb.YY, e->lb.ro, e->lb.coef, e->lb.st};
+    void* ps[] = {e->lb.S, e->lb.Y, e->lb.g_prev, e->lb.d, e->lb.part, e->lb.SY, e->lb.YY, e->lb.ro, e->lb.coef, e->lb.st, e->lb.ls_buf, e->lb.ls_part};
     for (void* p : ps) if (p) (void)hipFree(p);
     e->lb = gpe_engine::Lbfgs();
 }
@@ -1504,7 +1514,7 @@ static int reset_opt(gpe_engine* e, float lr) {
     HIPCHK(e, hipMemsetAsync(e->am, 0, (size_t)e->P * sizeof(float), e->stream));
     HIPCHK(e, hipMemsetAsync(e->av, 0, (size_t)e->P * sizeof(float), e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));
-    return lbfgs_reset(e);
+    return lbfgs_reset(e, /*theta_to_start=*/true);
 }
 
 // ---- engine creation, phase by phase (gpe_create calls each once, in this order) -------------------------------------------------------
@@ -3301,7 +3311,11 @@ int gpe_lbfgs_config(gpe_engine* e, double lr, int history, double tolerance_gra
     if (e->cfg.world_size > 1 || e->comm) FAIL(e, GPE_ERR_INVALID, "lbfgs_config: a data-parallel engine has no L-BFGS (the history is per rank)");
     if (!e->lb.st || e->lb.cfg.m != history) {
         HIPCHK(e, hipStreamSynchronize(e->stream));
+        const LsCfg ls = e->lb.ls;                    // the line search does not depend on `history`: it and its buffers stay
+        float* ls_buf = e->lb.ls_buf; double* ls_part = e->lb.ls_part;
+        e->lb.ls_buf = nullptr; e->lb.ls_part = nullptr;
         lbfgs_free(e);
+        e->lb.ls = ls; e->lb.ls_buf = ls_buf; e->lb.ls_part = ls_part;
         const int m = history;
         e->lb.ld = (int)round_up(e->P, 64);
         e->lb.n_part = lbfgs_grid(e->P);
@@ -3335,11 +3349,28 @@ int gpe_lbfgs_update(gpe_engine* e) {
     launch_update(e, e->grad, e->sums(), e->lsums(), mse ? 0.0 : bc_count(e), /*do_update=*/0, mse, nullptr);
     HIPCHK(e, hipGetLastError());
     const int m = e->lb.cfg.m;
-    hipLaunchKernelGGL(k_lbfgs_dots, dim3(e->lb.n_part), dim3(64), 0, e->stream, e->P, e->lb.ld, m, (const float*)e->grad, (const float*)e->lb.g_prev,
+    if (e->lb.ls.kind) {                                // one tick: the same five launches whatever the decision is
+        hipLaunchKernelGGL(k_ls_dots, dim3(e->lb.n_part), dim3(64), 0, e->stream, e->P, e->lb.ld, (const float*)e->grad, (const float*)e->lb.d,
+                           (const LbfgsDev*)e->lb.st, e->lb.ls_part);
+        hipLaunchKernelGGL(k_ls_decide, dim3(1), dim3(64), 0, e->stream, e->lb.n_part, e->lb.cfg, e->lb.ls, e->lb.st, (const double*)e->lb.ls_part,
+                           (const gpe_scalars*)e->last);
+        hipLaunchKernelGGL(k_lbfgs_dots<true>, dim3(e->lb.n_part), dim3(64), 0, e->stream, e->P, e->lb.ld, m, (const float*)e->grad,
+                           (const float*)e->lb.g_prev, (const float*)e->lb.d, (const float*)e->lb.S, (const float*)e->lb.Y, (const LbfgsDev*)e->lb.st,
+                           e->lb.part);
+        hipLaunchKernelGGL(k_lbfgs_coef<true>, dim3(1), dim3(256), 0, e->stream, m, e->lb.n_part, e->lb.cfg, e->lb.st, (const double*)e->lb.part,
+                           e->lb.SY, e->lb.YY, e->lb.ro, e->lb.coef, (const gpe_scalars*)e->last);
+        hipLaunchKernelGGL(k_lbfgs_apply<true>, dim3(cdiv(e->P, 256)), dim3(256), 0, e->stream, e->P, e->lb.ld, m, (const float*)e->grad,
+                           e->lb.g_prev, e->lb.d, e->lb.S, e->lb.Y, e->theta, (const LbfgsDev*)e->lb.st, (const double*)e->lb.coef);
+        HIPCHK(e, hipGetLastError());
+        after_update(e);
+        e->packed_dirty = e->path == GPE_PATH_FUSED;
+        return GPE_OK;
+    }
+    hipLaunchKernelGGL(k_lbfgs_dots<false>, dim3(e->lb.n_part), dim3(64), 0, e->stream, e->P, e->lb.ld, m, (const float*)e->grad, (const float*)e->lb.g_prev,
                        (const float*)e->lb.d, (const float*)e->lb.S, (const float*)e->lb.Y, (const LbfgsDev*)e->lb.st, e->lb.part);
-    hipLaunchKernelGGL(k_lbfgs_coef, dim3(1), dim3(256), 0, e->stream, m, e->lb.n_part, e->lb.cfg, e->lb.st, (const double*)e->lb.part, e->lb.SY,
+    hipLaunchKernelGGL(k_lbfgs_coef<false>, dim3(1), dim3(256), 0, e->stream, m, e->lb.n_part, e->lb.cfg, e->lb.st, (const double*)e->lb.part, e->lb.SY,
                        e->lb.YY, e->lb.ro, e->lb.coef, (const gpe_scalars*)e->last);
-    hipLaunchKernelGGL(k_lbfgs_apply, dim3(cdiv(e->P, 256)), dim3(256), 0, e->stream, e->P, e->lb.ld, m, (const float*)e->grad, e->lb.g_prev, e->lb.d,
+    hipLaunchKernelGGL(k_lbfgs_apply<false>, dim3(cdiv(e->P, 256)), dim3(256), 0, e->stream, e->P, e->lb.ld, m, (const float*)e->grad, e->lb.g_prev, e->lb.d,
                        e->lb.S, e->lb.Y, e->theta, (const LbfgsDev*)e->lb.st, (const double*)e->lb.coef);
     HIPCHK(e, hipGetLastError());
     after_update(e);
@@ -3371,6 +3402,44 @@ int gpe_lbfgs_read(gpe_engine* e, double out[16]) {
     // the state as it stands (a reset clears it; the record fields of the last iteration would be stale then)
     out[LBR_N_ITER] = (double)h.n_iter; out[LBR_COUNT] = h.count; out[LBR_FROZEN] = h.frozen; out[LBR_HEAD] = h.head; out[LBR_H_DIAG] = h.H_diag;
     out[LBR_T] = h.t; out[LBR_PREV_LOSS] = h.prev_loss;
+    return GPE_OK;
+}
+
+int gpe_lbfgs_line_search(gpe_engine* e, int kind, double c1, double c2, int max_ls) {
+    if (!e) return GPE_ERR_INVALID;
+    if (kind != 0 && kind != 1) FAIL(e, GPE_ERR_INVALID, "lbfgs_line_search: kind must be 0 (none) or 1 (strong Wolfe), got %d", kind);
+    if (!(__builtin_isfinite(c1) && __builtin_isfinite(c2))) FAIL(e, GPE_ERR_INVALID, "lbfgs_line_search: c1 and c2 must be finite");
+    if (!(0.0 < c1 && c1 < c2 && c2 < 1.0)) FAIL(e, GPE_ERR_INVALID, "lbfgs_line_search: 0 < c1 < c2 < 1 required, got %g, %g", c1, c2);
+    if (max_ls < 1 || max_ls > 64) FAIL(e, GPE_ERR_INVALID, "lbfgs_line_search: max_ls must be in [1,64], got %d", max_ls);
+    if (!e->lb.on) FAIL(e, GPE_ERR_STATE, "lbfgs_line_search: L-BFGS is not configured (gpe_lbfgs_config)");
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    if (kind && !e->lb.ls_buf) {
+        int rc;
+        if ((rc = dev_alloc(e, nullptr, &e->lb.ls_buf, (size_t)(LS_SLOTS + 1) * e->lb.ld)) ||
+            (rc = dev_alloc(e, nullptr, &e->lb.ls_part, (size_t)e->lb.n_part * LSD_COUNT))) return rc;
+    }
+    // a search of the previous setting may be running: theta goes back to its start point before the state is cleared
+    int rc = lbfgs_reset(e, /*theta_to_start=*/true);
+    e->lb.ls = LsCfg{kind, c1, c2, max_ls};
+    return rc;
+}
+
+int gpe_lbfgs_ls_read(gpe_engine* e, double out[24]) {
+    if (!e || !out) return GPE_ERR_INVALID;
+    if (!e->lb.on) FAIL(e, GPE_ERR_STATE, "lbfgs_ls_read: L-BFGS is not configured (gpe_lbfgs_config)");
+    static_assert(LSR_FIELDS == 24, "gpe_lbfgs_ls_read record");
+    LbfgsDev h;
+    HIPCHK(e, hipMemcpyAsync(&h, e->lb.st, sizeof h, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    const LsDev& ls = h.ls;
+    out[LSR_PHASE] = ls.did; out[LSR_LS_ITER] = ls.ls_iter; out[LSR_LS_EVALS] = ls.ls_evals; out[LSR_EVALS_TOTAL] = (double)ls.evals_total;
+    out[LSR_T] = ls.t; out[LSR_T_PREV] = ls.state == LS_BRACKET ? ls.b[0] : 0.0;
+    out[LSR_B0] = ls.b[0]; out[LSR_B1] = ls.b[1]; out[LSR_BF0] = ls.bf[0]; out[LSR_BF1] = ls.bf[1];
+    out[LSR_BGTD0] = ls.bgtd[0]; out[LSR_BGTD1] = ls.bgtd[1]; out[LSR_LOW_POS] = ls.low_pos;
+    out[LSR_F0] = ls.f0; out[LSR_GTD0] = ls.gtd0; out[LSR_DNORM] = ls.dnorm;
+    out[LSR_ACCEPTED] = (double)ls.accepted; out[LSR_END_MAX_LS] = (double)ls.end_max_ls; out[LSR_END_WIDTH] = (double)ls.end_width;
+    out[LSR_END_CURV] = (double)ls.end_curv; out[LSR_STALLED] = (double)ls.stalled; out[LSR_INSUF] = ls.insuf;
+    out[LSR_BSLOTS] = ls.bslot[0] + 4 * ls.bslot[1]; out[LSR_SLOT_NEW] = ls.slot_new;
     return GPE_OK;
 }
 

@@ -797,13 +797,35 @@ class Engine:
     LBFGS_FIELDS = ("loss", "grad_max", "grad_l1", "t", "gtd", "n_iter", "count", "frozen", "skipped", "pushed", "ys", "H_diag", "head",
                     "prev_loss")
 
+    LBFGS_LS_FIELDS = ("phase", "ls_iter", "ls_evals", "evals_total", "t", "t_prev", "b0", "b1", "bf0", "bf1", "bgtd0", "bgtd1", "low_pos",
+                       "f0", "gtd0", "dnorm", "accepted", "end_max_ls", "end_width", "end_curv", "stalled", "insuf_progress", "bslots",
+                       "slot_new")
+    LBFGS_LS_PHASES = ("none", "bracket", "zoom", "accepted", "frozen")
+
     def lbfgs_config(self, lr: float, history: int = 100, tolerance_grad: float = 1e-7, tolerance_change: float = 1e-9,
-                     stop_loss: float = 0.0):
+                     stop_loss: float = 0.0, line_search=None, c1: float = 1e-4, c2: float = 0.9, max_ls: int = 25):
         """Configure (torch's defaults) and reset the L-BFGS state.  The state freezes for good at max|g| <= tolerance_grad, on a
-        non-finite loss or gradient, or at loss < stop_loss."""
+        non-finite loss or gradient, or at loss < stop_loss.  line_search: None (a fixed step lr) or "strong_wolfe" (torch's line search
+        on the device; lbfgs_update() is then one TICK and lbfgs_run(n) spends n EVALUATIONS)."""
+        if line_search not in (None, "strong_wolfe"):
+            raise ValueError(f"line_search must be None or 'strong_wolfe', got {line_search!r}")
         self._chk(self.lib.gpe_lbfgs_config(self._h, float(lr), int(history), float(tolerance_grad), float(tolerance_change),
                                             float(stop_loss)))
         self._lbfgs_history = int(history)
+        if line_search is not None or getattr(self, "_lbfgs_ls", False):      # (never made for an engine that never asked for one)
+            self._chk(self.lib.gpe_lbfgs_line_search(self._h, 0 if line_search is None else 1, float(c1), float(c2), int(max_ls)))
+            self._lbfgs_ls = line_search is not None
+
+    def lbfgs_ls_read(self) -> dict:
+        """The line search's record after the last tick (LBFGS_LS_FIELDS; phase as one of LBFGS_LS_PHASES); synchronises."""
+        out = (C.c_double * len(self.LBFGS_LS_FIELDS))()
+        self._chk(self.lib.gpe_lbfgs_ls_read(self._h, out))
+        r = dict(zip(self.LBFGS_LS_FIELDS, out))
+        for k in ("ls_iter", "ls_evals", "evals_total", "low_pos", "accepted", "end_max_ls", "end_width", "end_curv", "stalled",
+                  "insuf_progress", "bslots", "slot_new"):
+            r[k] = int(r[k])
+        r["phase"] = self.LBFGS_LS_PHASES[int(r["phase"])]
+        return r
 
     def lbfgs_update(self):
         """One L-BFGS iteration behind step_backward() (or the engine's mse begin phase), in place of step_update()."""
@@ -811,7 +833,7 @@ class Engine:
 
     def lbfgs_run(self, n_iters: int, mse: bool = False):
         """n_iters iterations "evaluate, iterate" enqueued back to back; no host synchronisation.  mse: the pre-training loss
-        (bind_target).  The monitor and the keeper are not served."""
+        (bind_target).  With a line search n_iters counts evaluations ("evaluate, tick").  The monitor and the keeper are not served."""
         self._chk(self.lib.gpe_lbfgs_run(self._h, int(n_iters), 1 if mse else 0))
 
     def lbfgs_read(self) -> dict:

@@ -556,7 +556,7 @@ int gpe_mse_loss_grad(gpe_engine* e, double* loss);
  *   lr not finite or <= 0, a tolerance or stop_loss negative or not finite, a data-parallel engine (world_size > 1 or a communicator).
  * gpe_lbfgs_update: the third phase behind gpe_step_backward or gpe_mse_begin, in place of gpe_step_update / gpe_mse_update; reads the
  *   gradient exchange buffer and its tail exactly as those do.
- * gpe_lbfgs_run: n_iters iterations (mse != 0: of the pre-training loss, which needs gpe_bind_target) enqueued back to back with plain
+ * gpe_lbfgs_run: n_iters iterations (evaluations, with a line search on: see gpe_lbfgs_line_search) (mse != 0: of the pre-training loss, which needs gpe_bind_target) enqueued back to back with plain
  *   launches; no host synchronisation, no graph capture.  The held-out monitor and the keeper are NOT served by it.
  * gpe_lbfgs_read: synchronise; out = (loss, max|g|, |g|_1, t, g.d, n_iter, pairs held, frozen (0 no, 1 tolerance_grad, 2 non-finite,
  *   3 stop_loss), skipped, pushed, y.s, H_diag, ring head, prev_loss, 0, 0): loss, the gradient norms, g.d, skipped, pushed and y.s are
@@ -571,6 +571,36 @@ int gpe_lbfgs_update(gpe_engine* e);
 int gpe_lbfgs_run(gpe_engine* e, int64_t n_iters, int mse);
 int gpe_lbfgs_read(gpe_engine* e, double out[16]);
 int gpe_lbfgs_history(gpe_engine* e, float* h_S, float* h_Y, float* h_g_prev, float* h_d, size_t n, int* count);
+
+/* ---- strong-Wolfe line search for the device-resident L-BFGS: torch.optim.LBFGS(line_search_fn="strong_wolfe"), flattened.  With it the
+ * flat sequence is "evaluate, TICK": a tick is a line-search decision on the evaluation at the trial point theta0 + t d (torch's
+ * `_strong_wolfe` in its order of tests: sufficient decrease / not below the previous trial, curvature, g.d >= 0; extrapolation by cubic
+ * interpolation within (t + 0.01 (t - t_prev), 10 t); at max_ls the bracket [0, t]; the zoom loop with its bracket-width break against
+ * tolerance_change / max|d|, the 10 % rule and the low / high updates), followed by the L-BFGS iteration ONLY if the decision accepts a
+ * point.  The accepted point is the bracket's low end with the loss and gradient STORED for it -- not necessarily the last one evaluated
+ * -- and the iteration runs on those; no evaluation is spent on it.  Every tick is the same launch sequence; the host never reads a
+ * decision and nothing synchronises.  Rules beyond torch's: the freezes of gpe_lbfgs_config apply at accepted points; a non-finite loss or
+ * gradient at a TRIAL puts the parameters back to the best point the bracket holds (its low end, or the start point before a bracket
+ * exists) and freezes with code 2, so a frozen run never leaves the parameters at a trial point; `stalled` counts accepted steps with
+ * t = 0 (parameters unchanged, no pair pushed) and is not a stop: the evaluation budget bounds the run.
+ * gpe_lbfgs_line_search: kind 0 = none (the machine of gpe_lbfgs_update as it is without this call, the same bits), 1 = strong Wolfe.
+ *   Needs gpe_lbfgs_config first; allocates on first use (the start point and three trial-gradient slots) and resets the L-BFGS state.
+ *   The choice stays across later gpe_lbfgs_config calls.  GPE_ERR_INVALID: unknown kind, c1 or c2 not finite or not 0 < c1 < c2 < 1,
+ *   max_ls outside [1, 64].  GPE_ERR_STATE: L-BFGS not configured.
+ * With a line search on, gpe_lbfgs_update is ONE TICK and gpe_lbfgs_run's n_iters counts EVALUATIONS (ticks), not iterations.
+ *   gpe_lbfgs_read / gpe_lbfgs_history keep their layout and report the last completed iteration: t is then the first trial step of the
+ *   new direction, loss the accepted loss, g_prev the gradient at the search's start point.
+ * gpe_lbfgs_ls_read: synchronise; out = (phase: what the last tick did, 0 nothing yet, 1 bracket phase went on, 2 zoom went on, 3 a point
+ *   was accepted, 4 frozen; ls_iter; evaluations in this search; evaluations in all; t of the next trial; t_prev; bracket ends (2), their
+ *   losses (2) and g.d (2) -- after an accepted tick end 0 is the new start point and end 1 the point the search just ended accepted: its
+ *   step, loss and g.d along the old direction --; low_pos; loss and g.d at the start point; max|d|; searches accepted; ended by max_ls; by the width break; by
+ *   the curvature test; stalled; insuf_progress; the ends' gradient slots (end 0 + 4 * end 1; 3 = the start gradient); the slot of the
+ *   next gradient).
+ * Every reset of the L-BFGS state ends a running search.  gpe_reset_optimizer and gpe_lbfgs_line_search do not rewrite the parameters:
+ *   they put them back to the search's start point first.  gpe_set_params and gpe_keeper_restore overwrite them; a new gpe_lbfgs_config
+ *   starts from the parameters as they stand.  The refusals of gpe_lbfgs_update / gpe_lbfgs_run are unchanged. */
+int gpe_lbfgs_line_search(gpe_engine* e, int kind, double c1, double c2, int max_ls);
+int gpe_lbfgs_ls_read(gpe_engine* e, double out[24]);
 
 /* ---- continuation knobs: the gamma / perturbation loop of refine/...:289-340 -------------------------- */
 int gpe_set_gamma(gpe_engine* e, float gamma);
