@@ -177,6 +177,8 @@ SYMBOLS = {
     "gpe_lbfgs_history": (_int, [_vp, _vp, _vp, _vp, _vp, C.c_size_t, _P(_int)]),
     "gpe_lbfgs_line_search": (_int, [_vp, _int, C.c_double, C.c_double, _int]),
     "gpe_lbfgs_ls_read": (_int, [_vp, _P(C.c_double)]),
+    "gpe_lbfgs_monitor": (_int, [_vp, _int]),
+    "gpe_lbfgs_point": (_int, [_vp, _vp, C.c_size_t]),
     "gpe_set_gamma": (_int, [_vp, _f]),
     "gpe_set_mixture": (_int, [_vp, _f, _f, _f]),
     "gpe_mixture_scalars": (_int, [_vp, _P(C.c_double)]),

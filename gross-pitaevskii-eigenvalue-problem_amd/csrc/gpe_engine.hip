@@ -692,6 +692,8 @@ struct gpe_engine {
         LsCfg ls = {};                                                            // strong-Wolfe line search (gpe_lbfgs_line_search); kind 0: none
         float* ls_buf = nullptr;                                                  // [4][ld]: three trial-gradient slots, theta0
         double* ls_part = nullptr;                                                // [n_part][LSD_COUNT]
+        bool mon = false;                                                         // gpe_lbfgs_monitor: gpe_lbfgs_run serves the monitor
+        float* view_buf = nullptr;                                                // [ld]: theta, set aside during a monitor tick
     } lb;
     StepState st;
     std::string err;
@@ -1500,7 +1502,8 @@ static int lbfgs_reset(gpe_engine* e, bool theta_to_start = false) {
 }
 
 static void lbfgs_free(gpe_engine* e) {
-    void* ps[] = {e->lb.S, e->lb.Y, e->lb.g_prev, e->lb.d, e->lb.part, e->lb.SY, e->lb.YY, e->lb.ro, e->lb.coef, e->lb.st, e->lb.ls_buf, e->lb.ls_part};
+    void* ps[] = {e->lb.S, e->lb.Y, e->lb.g_prev, e->lb.d, e->lb.part, e->lb.SY, e->lb.YY, e->lb.ro, e->lb.coef, e->lb.st, e->lb.ls_buf, e->lb.ls_part,
+                  e->lb.view_buf};
     for (void* p : ps) if (p) (void)hipFree(p);
     e->lb = gpe_engine::Lbfgs();
 }
@@ -2966,10 +2969,15 @@ int gpe_keeper_restore(gpe_engine* e) {
 // k steps were just enqueued (never past a monitor step: gpe_run cuts there).  On a monitor step: forward of the monitor points with the
 // parameters that step left behind -- on the fused path through the packed weight copies the update refreshed, or ensure_packed
 // refreshes here, the path gpe_forward between two gpe_run calls takes -- the reduction chain, one record into the ring.
+static int monitor_record(gpe_engine* e);
 static int monitor_after_steps(gpe_engine* e, int64_t k) {
     if (e->mon_every <= 0) return GPE_OK;
     e->mon_steps += k;
     if (e->mon_steps % e->mon_every != 0) return GPE_OK;
+    return monitor_record(e);
+}
+// the chain of one record, of theta as it stands (gpe_lbfgs_run puts the judged point there first: lbfgs_monitor_tick)
+static int monitor_record(gpe_engine* e) {
     int rc;
     if ((rc = mlp_forward(e, e->mon, false))) return rc;
     double* slot = e->mon_ring + (size_t)(e->mon_records % e->mon_cap) * obs_rec_doubles(e);
@@ -3313,9 +3321,12 @@ int gpe_lbfgs_config(gpe_engine* e, double lr, int history, double tolerance_gra
         HIPCHK(e, hipStreamSynchronize(e->stream));
         const LsCfg ls = e->lb.ls;                    // the line search does not depend on `history`: it and its buffers stay
         float* ls_buf = e->lb.ls_buf; double* ls_part = e->lb.ls_part;
-        e->lb.ls_buf = nullptr; e->lb.ls_part = nullptr;
+        const bool mon = e->lb.mon;                   // nor does gpe_lbfgs_monitor
+        float* view_buf = e->lb.view_buf;
+        e->lb.ls_buf = nullptr; e->lb.ls_part = nullptr; e->lb.view_buf = nullptr;
         lbfgs_free(e);
         e->lb.ls = ls; e->lb.ls_buf = ls_buf; e->lb.ls_part = ls_part;
+        e->lb.mon = mon; e->lb.view_buf = view_buf;
         const int m = history;
         e->lb.ld = (int)round_up(e->P, 64);
         e->lb.n_part = lbfgs_grid(e->P);
@@ -3378,6 +3389,25 @@ int gpe_lbfgs_update(gpe_engine* e) {
     return GPE_OK;
 }
 
+// gpe_lbfgs_monitor: one tick of gpe_lbfgs_run is one step of the monitor's cadence.  On a monitor tick the judged point (gpe_lbfgs.h)
+// stands in theta's place for the length of the monitor chain -- on the fused path mlp_forward repacks the weight copies from it -- and
+// theta comes back behind it, so the run goes on from the bits it would have had; the next evaluation repacks, as after every tick.
+static int lbfgs_monitor_tick(gpe_engine* e) {
+    if (!e->lb.mon || e->mon_every <= 0) return GPE_OK;
+    e->mon_steps += 1;
+    if (e->mon_steps % e->mon_every != 0) return GPE_OK;
+    const unsigned g = lbfgs_view_grid(e->P);
+    hipLaunchKernelGGL(k_lbfgs_view, dim3(g), dim3(LBV_THREADS), 0, e->stream, e->P, e->theta, e->lb.view_buf, e->lb.st);
+    HIPCHK(e, hipGetLastError());
+    e->packed_dirty = e->path == GPE_PATH_FUSED;
+    const int rc = monitor_record(e);
+    hipLaunchKernelGGL(k_lbfgs_unview, dim3(g), dim3(LBV_THREADS), 0, e->stream, e->P, e->theta, (const float*)e->lb.view_buf, e->lb.st,
+                       (const KeepDev*)(e->keep_metric != GPE_KEEP_NONE ? e->keep_dev : nullptr));
+    HIPCHK(e, hipGetLastError());
+    e->packed_dirty = e->path == GPE_PATH_FUSED;
+    return rc;
+}
+
 int gpe_lbfgs_run(gpe_engine* e, int64_t n_iters, int mse) {
     if (!e || n_iters < 0) return GPE_ERR_INVALID;
     int rc;
@@ -3386,8 +3416,37 @@ int gpe_lbfgs_run(gpe_engine* e, int64_t n_iters, int mse) {
         if (mse) rc = gpe_mse_begin(e);
         else if (!(rc = step_begin(e, StepOpts{}))) rc = step_backward(e, StepOpts{});
         if (!rc) rc = gpe_lbfgs_update(e);
+        if (!rc) rc = lbfgs_monitor_tick(e);
         if (rc) return rc;
     }
+    return GPE_OK;
+}
+
+int gpe_lbfgs_monitor(gpe_engine* e, int on) {
+    if (!e) return GPE_ERR_INVALID;
+    if (on != 0 && on != 1) FAIL(e, GPE_ERR_INVALID, "lbfgs_monitor: on must be 0 or 1, got %d", on);
+    if (!e->lb.on) FAIL(e, GPE_ERR_STATE, "lbfgs_monitor: L-BFGS is not configured (gpe_lbfgs_config)");
+    if (on && !e->lb.view_buf) {
+        int rc;
+        if ((rc = dev_alloc(e, nullptr, &e->lb.view_buf, (size_t)e->lb.ld))) return rc;
+    }
+    e->lb.mon = on != 0;
+    return GPE_OK;
+}
+
+int gpe_lbfgs_point(gpe_engine* e, float* h_flat, size_t n) {
+    if (!e) return GPE_ERR_INVALID;
+    if (!h_flat) FAIL(e, GPE_ERR_INVALID, "lbfgs_point: no output array");
+    if ((int64_t)n != e->P_user) FAIL(e, GPE_ERR_INVALID, "lbfgs_point: got %zu floats, model has %d", n, e->P_user);
+    if (!e->lb.on) FAIL(e, GPE_ERR_STATE, "lbfgs_point: L-BFGS is not configured (gpe_lbfgs_config)");
+    LbfgsDev h;
+    HIPCHK(e, hipMemcpyAsync(&h, e->lb.st, sizeof h, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    // the rule of k_lbfgs_view, on a copy of the state: this reader synchronises anyway, and it writes nothing on the device
+    const bool at_start = !h.frozen && h.ls.state != LS_IDLE && h.ls.theta0 != nullptr;
+    int rc = flat_from_device(e, at_start ? h.ls.theta0 : e->theta, h_flat);
+    if (rc) return rc;
+    HIPCHK(e, hipStreamSynchronize(e->stream));
     return GPE_OK;
 }
 

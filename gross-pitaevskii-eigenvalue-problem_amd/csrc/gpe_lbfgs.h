@@ -49,7 +49,7 @@
 enum { LBD_YS = 0, LBD_YY, LBD_SG, LBD_YG, LBD_GG, LBD_G1, LBD_GMAX, LBD_BASE_COUNT = 8 };
 enum { LBR_LOSS = 0, LBR_GMAX, LBR_G1, LBR_T, LBR_GTD, LBR_N_ITER, LBR_COUNT, LBR_FROZEN, LBR_SKIPPED, LBR_PUSHED, LBR_YS, LBR_H_DIAG,
        LBR_HEAD, LBR_PREV_LOSS, LBR_FIELDS = 16 };
-enum { LBFGS_LIVE = 0, LBFGS_FROZEN_GRAD = 1, LBFGS_FROZEN_NONFINITE = 2, LBFGS_FROZEN_LOSS = 3 };
+enum { LBFGS_LIVE = 0, LBFGS_FROZEN_GRAD = 1, LBFGS_FROZEN_NONFINITE = 2, LBFGS_FROZEN_LOSS = 3, LBFGS_FROZEN_KEEPER = 4 };
 
 // line search: what the NEXT evaluation is for / what this tick's decision asks of the kernels behind it / what the tick did (the record)
 enum { LS_IDLE = 0, LS_BRACKET = 1, LS_ZOOM = 2 };      // IDLE: taken at theta0 itself (the first one, or the one after a g.d skip)
@@ -79,6 +79,7 @@ struct LbfgsDev {
     int push, push_slot, skip;                  // this iteration's decisions, for k_lbfgs_apply
     double rec[LBR_FIELDS];
     LsDev ls;                                   // all zero with the line search off
+    int view;                                   // k_lbfgs_view put the search's start point in theta's place (until k_lbfgs_unview)
 };
 
 static inline int lbfgs_grid(int P) { const int g = (P + LBFGS_TILE - 1) / LBFGS_TILE; return g < LBFGS_MAX_WG ? g : LBFGS_MAX_WG; }
@@ -489,4 +490,58 @@ __global__ __launch_bounds__(256) void k_ls_restore(int P, float* __restrict__ t
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= P || st->frozen || st->ls.state == LS_IDLE || !st->ls.theta0) return;
     theta[i] = st->ls.theta0[i];
+}
+
+// ---- the judged point: what the held-out monitor and the keeper look at in a gpe_lbfgs_run (gpe_lbfgs_monitor, gpe_lbfgs_point) -----------
+// While a strong-Wolfe search runs theta sits at a trial point; the one parameter set an observer may see is the search's START point
+// (LsDev::theta0: the last accepted point, or where the run started).  Without a line search, with the search idle (the evaluation is
+// taken at theta0 itself) and in every frozen state theta is that point already.  The choice is read from the state on the device:
+//   k_lbfgs_view    in front of the monitor chain: theta is set aside and the start point takes its place where the rule says so; the
+//                   choice is filed in LbfgsDev::view for the kernel behind the chain (which must not read what it rewrites)
+//   k_lbfgs_unview  behind the chain: theta comes back -- unless the keeper's patience fired (KeepDev::stopped, k_keep_decide): then theta
+//                   stays at the judged point, a running search is ended and the run freezes for good with code LBFGS_FROZEN_KEEPER
+// Both are grid-strided over P, 16 bytes per access where the three pointers allow it (as k_keep_copy), grid a function of P alone.
+#define LBV_THREADS 256
+#define LBV_MAX_WG 256
+static inline unsigned lbfgs_view_grid(int P) {
+    const int g = ((P + 3) / 4 + LBV_THREADS - 1) / LBV_THREADS;
+    return (unsigned)(g < 1 ? 1 : g < LBV_MAX_WG ? g : LBV_MAX_WG);
+}
+GPE_DEV bool lbfgs_judged_at_start(const LbfgsDev* st) { return !st->frozen && st->ls.state != LS_IDLE && st->ls.theta0 != nullptr; }
+
+// dst = src over P floats; ASIDE: `keep` takes dst's old values first
+template <bool ASIDE>
+GPE_DEV void lbfgs_view_copy(int P, float* __restrict__ dst, const float* __restrict__ src, float* __restrict__ keep) {
+    const bool wide = ((((uintptr_t)dst) | ((uintptr_t)src) | ((uintptr_t)keep)) & 15) == 0;
+    const int n4 = wide ? P / 4 : 0;
+    float4* d4 = (float4*)dst; const float4* s4 = (const float4*)src; float4* k4 = (float4*)keep;
+    for (int i = blockIdx.x * LBV_THREADS + threadIdx.x; i < n4; i += gridDim.x * LBV_THREADS) {
+        if constexpr (ASIDE) k4[i] = d4[i];
+        d4[i] = s4[i];
+    }
+    for (int i = 4 * n4 + blockIdx.x * LBV_THREADS + threadIdx.x; i < P; i += gridDim.x * LBV_THREADS) {
+        if constexpr (ASIDE) keep[i] = dst[i];
+        dst[i] = src[i];
+    }
+}
+
+__global__ __launch_bounds__(LBV_THREADS) void k_lbfgs_view(int P, float* __restrict__ theta, float* __restrict__ aside, LbfgsDev* st) {
+    const bool at_start = lbfgs_judged_at_start(st);                // (no thread writes a field this reads)
+    if (blockIdx.x == 0 && threadIdx.x == 0) st->view = at_start ? 1 : 0;
+    if (!at_start) return;
+    lbfgs_view_copy<true>(P, theta, st->ls.theta0, aside);
+}
+
+// kd == NULL: no keeper bound
+__global__ __launch_bounds__(LBV_THREADS) void k_lbfgs_unview(int P, float* __restrict__ theta, const float* __restrict__ aside, LbfgsDev* st,
+                                                               const KeepDev* __restrict__ kd) {
+    const bool stop = kd != nullptr && kd->stopped != 0;
+    const bool viewed = st->view != 0;                              // (written by k_lbfgs_view only)
+    if (blockIdx.x == 0 && threadIdx.x == 0 && stop && !st->frozen) {      // `frozen` is read and written by this thread alone
+        st->frozen = LBFGS_FROZEN_KEEPER; st->push = 0; st->skip = 1;
+        st->rec[LBR_FROZEN] = LBFGS_FROZEN_KEEPER;
+        if (st->ls.theta0) { st->ls.state = LS_IDLE; st->ls.action = LS_ACT_NONE; st->ls.did = LS_DID_FROZEN; }
+    }
+    if (!viewed || stop) return;                                    // a viewed state is never a frozen one: `stop` freezes it here
+    lbfgs_view_copy<false>(P, theta, aside, nullptr);
 }

@@ -801,6 +801,7 @@ class Engine:
                        "f0", "gtd0", "dnorm", "accepted", "end_max_ls", "end_width", "end_curv", "stalled", "insuf_progress", "bslots",
                        "slot_new")
     LBFGS_LS_PHASES = ("none", "bracket", "zoom", "accepted", "frozen")
+    LBFGS_FROZEN = ("live", "tolerance_grad", "nonfinite", "stop_loss", "keeper")      # lbfgs_read()["frozen"] indexes this
 
     def lbfgs_config(self, lr: float, history: int = 100, tolerance_grad: float = 1e-7, tolerance_change: float = 1e-9,
                      stop_loss: float = 0.0, line_search=None, c1: float = 1e-4, c2: float = 0.9, max_ls: int = 25):
@@ -833,10 +834,26 @@ class Engine:
 
     def lbfgs_run(self, n_iters: int, mse: bool = False):
         """n_iters iterations "evaluate, iterate" enqueued back to back; no host synchronisation.  mse: the pre-training loss
-        (bind_target).  With a line search n_iters counts evaluations ("evaluate, tick").  The monitor and the keeper are not served."""
+        (bind_target).  With a line search n_iters counts evaluations ("evaluate, tick").  The monitor and the keeper are served
+        after lbfgs_monitor(True), at the judged point (lbfgs_point) only."""
         self._chk(self.lib.gpe_lbfgs_run(self._h, int(n_iters), 1 if mse else 0))
 
+    def lbfgs_monitor(self, on: bool = True):
+        """Opt in (or out): every tick of lbfgs_run counts as one step of the bound monitor's `every`, and a monitor tick records -- and a
+        bound keeper judges and keeps -- the JUDGED POINT: the parameters as they stand without a line search or once frozen, the start
+        point of the running search (the last accepted point) under strong Wolfe.  The run itself goes on from the same bits.  The
+        keeper's patience freezes the run for good with frozen code 4 ("keeper"), the parameters at the judged point of that record."""
+        self._chk(self.lib.gpe_lbfgs_monitor(self._h, 1 if on else 0))
+
+    def lbfgs_point(self) -> np.ndarray:
+        """The judged point (see lbfgs_monitor) as get_params() would give it; synchronises, writes nothing on the device."""
+        out = np.empty(self.n_params, np.float32)
+        self._chk(self.lib.gpe_lbfgs_point(self._h, out.ctypes.data_as(C.c_void_p), out.size))
+        return out
+
     def lbfgs_read(self) -> dict:
+        """The last iteration's record and the state as it stands (LBFGS_FIELDS); `frozen` is a code: LBFGS_FROZEN[code] names it
+        (0 live, 1 tolerance_grad, 2 nonfinite, 3 stop_loss, 4 keeper: the keeper's patience, lbfgs_monitor); synchronises."""
         out = (C.c_double * 16)()
         self._chk(self.lib.gpe_lbfgs_read(self._h, out))
         r = dict(zip(self.LBFGS_FIELDS, out))

@@ -664,7 +664,7 @@ def _refine_advanced_initialization(m, mode):
         m._engine.set_params(m._flat)
 
 
-def _refine_pretrain(model, mode, X_train, epochs=5000, lr=1e-3, verbose=False, lbfgs="host", lbfgs_line_search=None):
+def _refine_pretrain(model, mode, X_train, epochs=5000, lr=1e-3, verbose=False, lbfgs="host", lbfgs_line_search=None, lbfgs_monitor=False):
     """pretrain_on_analytical_solution (refine/harmonic_pinn_simulation.py:650-701): fit the network output to phi_mode(x).
     Adam phase (epochs-500 iterations, plain Adam, no clipping) on the engine; then the reference's L-BFGS tail
     (torch.optim.LBFGS(lr*0.1, max_iter=20), 500 outer iterations).  lbfgs="host" (default): torch's optimiser driven host-side on
@@ -672,13 +672,16 @@ def _refine_pretrain(model, mode, X_train, epochs=5000, lr=1e-3, verbose=False, 
     iteration, torch's default history and tolerances, no host round trip); the stop at loss < 1e-12 is then checked at EVERY
     iteration, not once per 20, and freezes the parameters where it fires.  lbfgs_line_search="strong_wolfe" (device path only): the
     same budget of 20 evaluations per outer iteration spent by torch's strong-Wolfe line search on the device; the stop is then checked
-    at every accepted point.
+    at every accepted point.  lbfgs_monitor=True (device path only): the tail's ticks count for a monitor bound on the engine, and a bound
+    keeper judges the tail's accepted points (Engine.lbfgs_monitor).
     model.pretrain_loss is stale by one update on either path: "host" reports torch's return value, the loss of the FIRST evaluation of the
     last outer call (up to 20 updates old); "device" reports the record of the last iteration, the loss evaluated before its update."""
     if lbfgs not in ("host", "device"):
         raise ValueError(f"lbfgs must be 'host' or 'device', got {lbfgs!r}")
     if lbfgs_line_search is not None and lbfgs != "device":
         raise ValueError("lbfgs_line_search needs lbfgs='device'")
+    if lbfgs_monitor and lbfgs != "device":
+        raise ValueError("lbfgs_monitor needs lbfgs='device'")
     X = _as_np(X_train).astype(np.float32)
     dev = _device()
     X_dev = torch.as_tensor(X, device=dev)
@@ -698,6 +701,7 @@ def _refine_pretrain(model, mode, X_train, epochs=5000, lr=1e-3, verbose=False, 
             break
     if loss >= 1e-12 and epochs > n_adam and lbfgs == "device":
         eng.lbfgs_config(lr * 0.1, history=100, tolerance_grad=1e-7, tolerance_change=1e-9, stop_loss=1e-12, line_search=lbfgs_line_search)
+        eng.lbfgs_monitor(bool(lbfgs_monitor))
         eng.lbfgs_run(20 * (epochs - n_adam), mse=True)
         loss = eng.lbfgs_read()["loss"]
     elif loss >= 1e-12 and epochs > n_adam:

@@ -557,9 +557,11 @@ int gpe_mse_loss_grad(gpe_engine* e, double* loss);
  * gpe_lbfgs_update: the third phase behind gpe_step_backward or gpe_mse_begin, in place of gpe_step_update / gpe_mse_update; reads the
  *   gradient exchange buffer and its tail exactly as those do.
  * gpe_lbfgs_run: n_iters iterations (evaluations, with a line search on: see gpe_lbfgs_line_search) (mse != 0: of the pre-training loss, which needs gpe_bind_target) enqueued back to back with plain
- *   launches; no host synchronisation, no graph capture.  The held-out monitor and the keeper are NOT served by it.
+ *   launches; no host synchronisation, no graph capture.  The held-out monitor and the keeper are served by it once gpe_lbfgs_monitor
+ *   says so, and then see the JUDGED POINT only: the parameters as they stand without a line search and in every frozen state, the start
+ *   point of the running search (the last accepted point) under strong Wolfe -- never a trial point.
  * gpe_lbfgs_read: synchronise; out = (loss, max|g|, |g|_1, t, g.d, n_iter, pairs held, frozen (0 no, 1 tolerance_grad, 2 non-finite,
- *   3 stop_loss), skipped, pushed, y.s, H_diag, ring head, prev_loss, 0, 0): loss, the gradient norms, g.d, skipped, pushed and y.s are
+ *   3 stop_loss, 4 the keeper's patience: gpe_lbfgs_monitor), skipped, pushed, y.s, H_diag, ring head, prev_loss, 0, 0): loss, the gradient norms, g.d, skipped, pushed and y.s are
  *   the last iteration's, the rest the state as it stands.
  * gpe_lbfgs_history: synchronise; the pairs held, oldest first, as rows of h_S / h_Y [history][n], g_prev and d [n], in the caller's
  *   parameter layout (n = gpe_param_count); any pointer may be NULL.
@@ -601,6 +603,29 @@ int gpe_lbfgs_history(gpe_engine* e, float* h_S, float* h_Y, float* h_g_prev, fl
  *   starts from the parameters as they stand.  The refusals of gpe_lbfgs_update / gpe_lbfgs_run are unchanged. */
 int gpe_lbfgs_line_search(gpe_engine* e, int kind, double c1, double c2, int max_ls);
 int gpe_lbfgs_ls_read(gpe_engine* e, double out[24]);
+
+/* ---- L-BFGS under the held-out monitor and the keeper (opt-in; off, gpe_lbfgs_run is what it is without these two calls, the same
+ * launches and the same bits).  The JUDGED POINT is the one parameter set an observer of an L-BFGS run may look at:
+ *   no line search: the parameters as they stand after the tick;  strong Wolfe, search running: the search's start point -- the last
+ *   accepted point, or the parameters the run started from (after an accepting tick the parameters are already the first trial of the
+ *   next direction);  search idle, or frozen with any code: the parameters as they stand (a frozen run never sits at a trial point).
+ * The state that decides this lives on the device and the choice is made there (csrc/gpe_lbfgs.h: k_lbfgs_view, k_lbfgs_unview).
+ * gpe_lbfgs_monitor: on = 1: every tick of gpe_lbfgs_run (one evaluation, with or without a line search, mse or not) counts as one step
+ *   of the bound monitor's `every`, on the counter gpe_run uses, so an Adam run followed by an L-BFGS tail keeps one rhythm.  On a monitor
+ *   tick the judged point takes the parameters' place, the monitor's chain runs as behind an Adam step (record into the ring; with a
+ *   keeper: judged, and the judged point copied aside if it is the best), and the parameters come back: the run goes on from the bits it
+ *   would have had.  Nothing synchronises.  The record's `step` is what the chain writes: the Adam step count, which L-BFGS does not
+ *   advance.  When the keeper's patience fires the run FREEZES for good with code 4: the parameters stay at the judged point of that
+ *   record, a running search is ended, gpe_stop_state reports the stop as after gpe_run.  What clears it is what resets the L-BFGS
+ *   state and the stop (gpe_reset_optimizer); re-arm the keeper to start a new count.  Records go on being written after any freeze, of
+ *   the parameters as they stand.  on = 0 (the default): ticks do not count.  With no monitor bound the flag does nothing.  It stays
+ *   across gpe_lbfgs_config and gpe_lbfgs_line_search calls; gpe_lbfgs_update alone ignores the monitor, as the three-phase entry
+ *   points do.  Allocates one parameter vector at the first on = 1.  GPE_ERR_INVALID: on is not 0 or 1.  GPE_ERR_STATE: L-BFGS not
+ *   configured.
+ * gpe_lbfgs_point: synchronise; the judged point in the caller's parameter layout (n = gpe_param_count).  Writes nothing on the device:
+ *   a running search goes on from the same bits.  GPE_ERR_INVALID: h_flat NULL or a wrong n.  GPE_ERR_STATE: L-BFGS not configured. */
+int gpe_lbfgs_monitor(gpe_engine* e, int on);
+int gpe_lbfgs_point(gpe_engine* e, float* h_flat, size_t n);
 
 /* ---- continuation knobs: the gamma / perturbation loop of refine/...:289-340 -------------------------- */
 int gpe_set_gamma(gpe_engine* e, float gamma);

@@ -51,6 +51,13 @@ ap.add_argument("--adaptive-share", type=float, default=0.5, help="--adaptive: t
 ap.add_argument("--big-grid", default="", help="e.g. 64,128,64: after the schedule, continue on THIS grid (BASELINE's per-GPU size) for --big-epochs epochs "
                                                "at the low end of the learning-rate ladder, and evaluate mu there (same weights, fresh Adam)")
 ap.add_argument("--big-epochs", type=int, default=3000)
+ap.add_argument("--lbfgs-tail", type=int, default=0, metavar="TICKS", help="after the Adam schedule: TICKS evaluations of the device-resident L-BFGS on the "
+                "regular grid under the held-out monitor (Engine.lbfgs_monitor; the cell centres of the grid, every --lbfgs-every ticks); records |mu - mu_ref| "
+                "of the last and of the kept parameters")
+ap.add_argument("--lbfgs-line-search", default=None, choices=["strong_wolfe"])
+ap.add_argument("--lbfgs-lr", type=float, default=1.0, help="torch.optim.LBFGS's default")
+ap.add_argument("--lbfgs-every", type=int, default=10)
+ap.add_argument("--keeper", default="res_rms", choices=["res_rms", "energy"], help="--lbfgs-tail: the field the keeper judges")
 ap.add_argument("--out", default="")
 a = ap.parse_args()
 cs = CASES[a.case]
@@ -269,6 +276,48 @@ out = dict(case=a.case, workload=cs["workload"], layers=cs["layers"], points=int
                          scheduler="constant lr per stage, fresh Adam per stage; last stage lr x (1, 0.3, 0.1, 0.03, 0.01, 0.003, 0.001)"),
            energy=rows[-1]["riesz"], energy_ref=truth["energy"], big_grid=big, kept=kept,
            observables={k: _obs[k] for k in ("norm", "kin", "pot", "inter", "energy", "mu", "mu_lap", "var_x", "peak_density", "res_rms")})
+# ---- L-BFGS tail under the monitor and the keeper (everything above describes the state the Adam schedule left) ----
+if a.lbfgs_tail > 0:
+    from gpe_pinn import keeper as keeper_rule
+    if a.big_grid:
+        ap.error("--lbfgs-tail continues the small-grid engine: not with --big-grid")
+    eng.bind_points(xd)                                          # fixed points (clears a sampler: the objective must not change under the history)
+    if weighted:
+        eng.bind_weights(torch.full((X.shape[0],), dv, device="cuda"))
+    centres = [0.5 * (ax[1:] + ax[:-1]) for ax in axes]          # held-out: no training point among them
+    XM = np.stack([m.ravel() for m in np.meshgrid(*centres, indexing="ij")], axis=1).astype(np.float32)
+    xm = torch.as_tensor(XM, device="cuda")
+    eng.lbfgs_config(a.lbfgs_lr, history=100, line_search=a.lbfgs_line_search)
+    eng.lbfgs_monitor(True)
+    eng.bind_monitor(xm, every=a.lbfgs_every, dv=dv)
+    eng.bind_keeper(a.keeper)
+    tt = time.time()
+    left = a.lbfgs_tail
+    while left > 0:
+        k = min(left, 200)
+        eng.lbfgs_run(k)
+        left -= k
+        st = eng.lbfgs_read()
+        print(f"   L-BFGS tail: loss {st['loss']:.6e} n_iter {st['n_iter']} frozen {eng.LBFGS_FROZEN[st['frozen']]} ({time.time() - t0:.0f} s)", flush=True)
+    st, ks = eng.lbfgs_read(), eng.keeper_state()
+    col = eng.read_monitor_array()[:, eng.OBSERVABLE_FIELDS.index(a.keeper)]
+    last_point = eng.lbfgs_point()                               # (under a line search theta itself may be a trial point)
+    eng.set_params(last_point)
+    obs_last = eng.observables()
+    tail = dict(ticks=a.lbfgs_tail, lr=a.lbfgs_lr, line_search=a.lbfgs_line_search, every=a.lbfgs_every, keeper=a.keeper, seconds=time.time() - tt,
+                monitor_points=int(XM.shape[0]), records=int(col.size), record_kept=keeper_rule.select(col)[0], records_improved=ks["kept"],
+                frozen=bool(st["frozen"]), frozen_why=eng.LBFGS_FROZEN[st["frozen"]], n_iter=st["n_iter"], loss_last=st["loss"],
+                mu_before=mu_normalised, mu_before_abs_err=abs(mu_normalised - mu_ref),
+                mu_last=obs_last["mu"], mu_last_abs_err=abs(obs_last["mu"] - mu_ref), res_rms_last=obs_last["res_rms"],
+                mu_kept=None, mu_kept_abs_err=None, res_rms_kept=None)
+    if ks["kept"] > 0:
+        eng.restore_best()
+        obs_kept = eng.observables()                             # on the regular grid, as mu_last
+        tail.update(mu_kept=obs_kept["mu"], mu_kept_abs_err=abs(obs_kept["mu"] - mu_ref), res_rms_kept=obs_kept["res_rms"],
+                    kept_record_res_rms=eng.best_record()["res_rms"])
+    out["lbfgs_tail"] = tail
+    print(f"L-BFGS tail ({a.lbfgs_tail} ticks, {tail['records']} records, kept record {tail['record_kept']}, frozen: {tail['frozen_why']}): |mu - mu_ref| before "
+          f"{tail['mu_before_abs_err']:.2e}, last {tail['mu_last_abs_err']:.2e}, kept {tail['mu_kept_abs_err'] if tail['mu_kept_abs_err'] is not None else float('nan'):.2e}", flush=True)
 path = a.out or os.path.join(ROOT, "gpurun_out", f"accuracy_{cs['workload']}.json")
 os.makedirs(os.path.dirname(path), exist_ok=True)
 json.dump(out, open(path, "w"), indent=1)
