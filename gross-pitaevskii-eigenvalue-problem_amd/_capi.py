@@ -134,6 +134,8 @@ SYMBOLS = {
     "gpe_sampler_adaptive": (_int, [_vp, _P(gpe_sampler_spec), _vp, _vp, _vp, _i64, C.c_int32, C.c_int32]),
     "gpe_sampler_adaptive_state": (_int, [_vp, _vp, _P(C.c_double), _vp, _P(_i64)]),
     "gpe_sampler_adaptive_blocks": (_int, [_vp, _P(_i64), _P(_i64)]),
+    "gpe_sampler_cells": (_int, [_vp, _P(gpe_sampler_spec), _vp, _i64, _vp, _vp, _vp]),
+    "gpe_sampler_cells_read": (_int, [_vp, _P(_vp), _P(_i64), _P(_i64)]),
     "gpe_bind_boundary": (_int, [_vp, _vp, _i64, _vp]),
     "gpe_bind_orth": (_int, [_vp, _int, _vp]),
     "gpe_bind_orth_state": (_int, [_vp, _int, _vp, C.c_size_t, _int, _f, _f]),

@@ -676,6 +676,9 @@ struct gpe_engine {
     AdaptiveDev smp_ad = {};                          // mass [B + 1], count [B], off [B + 1], vol [B] and the allocation's constants
     float* smp_vol = nullptr;                         // (smp_ad.vol, writable)
     float* smp_resid = nullptr;                       // [smp_n][n_out]: the residual of the set held, written by the detour before a redraw
+    // cell-subset sampler (gpe_sampler_cells): the uniform or the graded sampler on rows [smp_first, smp_first + smp_n) of a cell list
+    int64_t* smp_cells = nullptr;                     // [smp_cells_n] strictly ascending row-major cell indices; NULL: row j is cell smp_first + j
+    int64_t smp_cells_n = 0;
     // per-point quadrature weights (gpe_bind_weights): every collocation sum takes q_i, every N of a mean becomes W (Phys::n_global)
     const float* wq = nullptr;                        // [n_pde]: the caller's array, or smp_q; NULL: unweighted
     double wq_local = 0.0, wq_total = 0.0;            // sum of this rank's weights / W over all ranks
@@ -2135,9 +2138,14 @@ static void graded_free(gpe_engine* e) {         // the graded sampler's edges a
     e->smp_ad = AdaptiveDev{};
     e->smp_adaptive = false;
 }
+static void cells_free(gpe_engine* e) {          // the cell list of gpe_sampler_cells (the stream is idle)
+    if (e->smp_cells) { (void)hipFree(e->smp_cells); e->smp_cells = nullptr; }
+    e->smp_cells_n = 0;
+}
 static void sampler_clear(gpe_engine* e) {       // the stream is idle (callers synchronise first)
     if (e->smp_x) { (void)hipFree(e->smp_x); e->smp_x = nullptr; }
     graded_free(e);
+    cells_free(e);
     e->smp_n = 0; e->smp_every = 0; e->smp_steps = 0; e->smp_draw0 = 0; e->smp_held = 0; e->smp_first = 0;
 }
 
@@ -2150,6 +2158,15 @@ static int sampler_launch(gpe_engine* e, int64_t draw, bool with_weights = false
         hipLaunchKernelGGL(k_sampler_draw_adaptive, dim3(cdiv(e->smp_n, SMP_THREADS)), dim3(SMP_THREADS), 0, e->stream, e->smp_grid,
                            ed + e->smp_edge_off[0], ed + e->smp_edge_off[1], ed + e->smp_edge_off[2], e->smp_ad, (uint64_t)draw,
                            e->smp_x, e->smp_q);
+    } else if (e->smp_cells && e->smp_graded) {  // (smp_first + smp_n <= smp_cells_n and every entry < prod shape: checked at the bind)
+        const float* ed = e->smp_edges;
+        hipLaunchKernelGGL(k_sampler_draw_graded_cells, dim3(cdiv(e->smp_n, SMP_THREADS)), dim3(SMP_THREADS), 0, e->stream, e->smp_grid,
+                           ed + e->smp_edge_off[0], ed + e->smp_edge_off[1], ed + e->smp_edge_off[2], (const int64_t*)e->smp_cells,
+                           e->smp_first, e->smp_n, (uint64_t)draw, e->smp_x, with_weights ? e->smp_q : (float*)nullptr);
+    } else if (e->smp_cells) {
+        float* xs = (e->cfg.w_sym != 0.f && e->sym.n == 2 * e->smp_n) ? e->sym.xown : nullptr;
+        hipLaunchKernelGGL(k_sampler_draw_cells, dim3(cdiv(e->smp_n, SMP_THREADS)), dim3(SMP_THREADS), 0, e->stream, e->smp_grid,
+                           (const int64_t*)e->smp_cells, e->smp_first, e->smp_n, (uint64_t)draw, e->smp_x, xs);
     } else if (e->smp_graded) {
         const float* ed = e->smp_edges;
         hipLaunchKernelGGL(k_sampler_draw_graded, dim3(cdiv(e->smp_n, SMP_THREADS)), dim3(SMP_THREADS), 0, e->stream, e->smp_grid,
@@ -2217,8 +2234,11 @@ static int weights_total(gpe_engine* e, const float* d_q, int64_t n, double* tot
 // edges == NULL: the uniform grid of gpe_bind_sampler; else the graded grid of gpe_bind_sampler_graded (one host array per used axis)
 struct AdaptiveArgs { int64_t n_points; int32_t n_min, s; };
 // ad != NULL (with edges): the residual-adaptive sampler of gpe_sampler_adaptive -- the cells are blocks, the buffer holds ad->n_points rows
-static int bind_sampler_impl(gpe_engine* e, const gpe_sampler_spec* sp, const float* const* edges, const AdaptiveArgs* ad = nullptr) {
-    const char* who = ad ? "sampler_adaptive" : edges ? "bind_sampler_graded" : "bind_sampler";
+// cl != NULL (with or without edges): the cell-subset sampler of gpe_sampler_cells -- first_cell / n_local index the list, not the grid
+struct CellsArgs { const int64_t* h_cells; int64_t n_cells; };
+static int bind_sampler_impl(gpe_engine* e, const gpe_sampler_spec* sp, const float* const* edges, const AdaptiveArgs* ad = nullptr,
+                             const CellsArgs* cl = nullptr) {
+    const char* who = cl ? "sampler_cells" : ad ? "sampler_adaptive" : edges ? "bind_sampler_graded" : "bind_sampler";
     if (ad && e->comm) FAIL(e, GPE_ERR_STATE, "%s: the engine has a communicator, and a data-parallel allocation needs a mass exchange", who);
     const int dim = e->nd.dim;
     if (e->cfg.potential == GPE_POT_PRECOMPUTED) FAIL(e, GPE_ERR_INVALID, "%s: a precomputed potential lives on fixed points", who);
@@ -2237,7 +2257,21 @@ static int bind_sampler_impl(gpe_engine* e, const gpe_sampler_spec* sp, const fl
         if (!(sp->clip_hi[k] >= sp->clip_lo[k])) FAIL(e, GPE_ERR_INVALID, "%s: clip_hi < clip_lo on axis %d", who, k);
         cells *= (double)sp->shape[k];
     }
-    if (sp->first_cell < 0 || sp->n_local <= 0 || (double)sp->first_cell + (double)sp->n_local > cells)
+    if (cl) {                                    // the list: strictly ascending cells of this grid; the rows: a block of the list
+        unsigned __int128 total = 1;             // (up to 2^72 cells: beyond int64, and a double would round the last cell onto the bound)
+        for (int k = 0; k < dim; ++k) total *= (unsigned __int128)sp->shape[k];
+        for (int64_t i = 0; i < cl->n_cells; ++i) {
+            const int64_t c = cl->h_cells[i];
+            if (c < 0 || (unsigned __int128)c >= total)
+                FAIL(e, GPE_ERR_INVALID, "%s: cells[%lld] = %lld outside the grid's %.0f cells", who, (long long)i, (long long)c, cells);
+            if (i > 0 && !(c > cl->h_cells[i - 1]))
+                FAIL(e, GPE_ERR_INVALID, "%s: the list is not strictly ascending at position %lld (%lld after %lld)", who, (long long)i,
+                     (long long)c, (long long)cl->h_cells[i - 1]);
+        }
+        if (sp->first_cell < 0 || sp->n_local <= 0 || sp->n_local > cl->n_cells || sp->first_cell > cl->n_cells - sp->n_local)
+            FAIL(e, GPE_ERR_INVALID, "%s: rows [%lld, %lld + %lld) outside the list's %lld", who, (long long)sp->first_cell, (long long)sp->first_cell,
+                 (long long)sp->n_local, (long long)cl->n_cells);
+    } else if (sp->first_cell < 0 || sp->n_local <= 0 || (double)sp->first_cell + (double)sp->n_local > cells)
         FAIL(e, GPE_ERR_INVALID, "%s: cells [%lld, %lld + %lld) outside the grid's %.0f", who, (long long)sp->first_cell, (long long)sp->first_cell, (long long)sp->n_local, cells);
     const int64_t n_rows = ad ? ad->n_points : sp->n_local;
     if (ad) {
@@ -2268,6 +2302,20 @@ static int bind_sampler_impl(gpe_engine* e, const gpe_sampler_spec* sp, const fl
             n_edges += sp->shape[k] + 1;
         }
     }
+    // ... of the WHOLE list under gpe_sampler_cells: the fp64 sum, in list order, of the fp32 cell volumes as k_sampler_draw_graded_cells
+    // forms them (fp32 widths, rounded fp32 products in axis order).  Keep this loop BEHIND both validations above: the list scan bounds
+    // every cell by prod shape (so ik[k] < shape[k]) and the edge scan found shape[k] + 1 entries per used axis -- the reads of
+    // edges[k][ik[k] + 1] below check nothing themselves.
+    if (edges && cl) {
+        w_grid = 0.0;
+        for (int64_t i = 0; i < cl->n_cells; ++i) {
+            int64_t rest = cl->h_cells[i], ik[3] = {0, 0, 0};
+            for (int k = dim - 1; k >= 0; --k) { ik[k] = rest % sp->shape[k]; rest /= sp->shape[k]; }
+            float v = edges[0][ik[0] + 1] - edges[0][ik[0]];
+            for (int k = 1; k < dim; ++k) { const float w = edges[k][ik[k] + 1] - edges[k][ik[k]]; v = v * w; }
+            w_grid += (double)v;
+        }
+    }
     // adaptive: the block volumes as k_sampler_draw_graded forms a cell's (fp32 widths, rounded fp32 products in axis order), and the
     // volume shares must not all truncate to zero (K_B > 0 in k_adaptive_alloc)
     std::vector<float> vol;
@@ -2288,16 +2336,31 @@ static int bind_sampler_impl(gpe_engine* e, const gpe_sampler_spec* sp, const fl
     }
     HIPCHK(e, hipStreamSynchronize(e->stream));
     if (e->side) HIPCHK(e, hipStreamSynchronize(e->side));
+    int64_t* d_cells = nullptr;                  // the engine's copy of the list, made before anything of the engine changes
+    if (cl) {
+        if (hipMalloc((void**)&d_cells, (size_t)cl->n_cells * sizeof(int64_t) + 256) != hipSuccess) {
+            (void)hipGetLastError();
+            FAIL(e, GPE_ERR_NOMEM, "%s: no memory for the list of %lld cells", who, (long long)cl->n_cells);
+        }
+        if (hipMemcpy(d_cells, cl->h_cells, (size_t)cl->n_cells * sizeof(int64_t), hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipGetLastError();
+            (void)hipFree(d_cells);
+            FAIL(e, GPE_ERR_HIP, "%s: upload of the cell list failed", who);
+        }
+    }
     if (e->smp_n != n_rows || !e->smp_x) {      // same size: the buffer (and a captured graph's pointers) stay
         float* p = nullptr;
         if (hipMalloc((void**)&p, (size_t)n_rows * dim * sizeof(float) + 256) != hipSuccess) {
             (void)hipGetLastError();
+            if (d_cells) (void)hipFree(d_cells);
             FAIL(e, GPE_ERR_NOMEM, "%s: no memory for %lld points", who, (long long)n_rows);
         }
         sampler_clear(e);
         e->smp_x = p;
     }
     graded_free(e);                              // edges and weights of an earlier graded bind
+    cells_free(e);                               // ... and the list of an earlier cell-subset bind
+    e->smp_cells = d_cells; e->smp_cells_n = cl ? cl->n_cells : 0;
     SamplerGrid& g = e->smp_grid;
     memset(&g, 0, sizeof g);
     g.dim = dim; g.key0 = (uint32_t)sp->seed; g.key1 = (uint32_t)(sp->seed >> 32);
@@ -2402,6 +2465,28 @@ int gpe_sampler_adaptive(gpe_engine* e, const gpe_sampler_spec* sp, const float*
     const float* edges[3] = {h_edges0, h_edges1, h_edges2};
     const AdaptiveArgs ad{n_points, n_min, uniform_per_1024};
     return bind_sampler_impl(e, sp, edges, &ad);
+}
+
+int gpe_sampler_cells(gpe_engine* e, const gpe_sampler_spec* sp, const int64_t* h_cells, int64_t n_cells,
+                      const float* h_edges0, const float* h_edges1, const float* h_edges2) {
+    if (!e) return GPE_ERR_INVALID;
+    if (!sp) FAIL(e, GPE_ERR_INVALID, "sampler_cells: no spec (gpe_bind_sampler(NULL) clears a sampler of any kind)");
+    if (!h_cells || n_cells <= 0) FAIL(e, GPE_ERR_INVALID, "sampler_cells: need a list of n_cells > 0 cells (n_cells = %lld)", (long long)n_cells);
+    const float* edges[3] = {h_edges0, h_edges1, h_edges2};
+    bool graded = false;                         // edges on any used axis: graded, and bind_sampler_impl wants them on every used axis
+    for (int k = 0; k < e->nd.dim && k < 3; ++k) graded = graded || edges[k] != nullptr;
+    const CellsArgs cl{h_cells, n_cells};
+    return bind_sampler_impl(e, sp, graded ? edges : nullptr, nullptr, &cl);
+}
+
+int gpe_sampler_cells_read(gpe_engine* e, const int64_t** d_cells, int64_t* n_cells, int64_t* first) {
+    if (!e) return GPE_ERR_INVALID;
+    if (e->smp_every <= 0 || !e->smp_cells) FAIL(e, GPE_ERR_STATE, "sampler_cells_read: no cell-subset sampler bound");
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    if (d_cells) *d_cells = e->smp_cells;
+    if (n_cells) *n_cells = e->smp_cells_n;
+    if (first) *first = e->smp_first;
+    return GPE_OK;
 }
 
 int gpe_sampler_adaptive_blocks(gpe_engine* e, int64_t* n_blocks, int64_t* n_points) {

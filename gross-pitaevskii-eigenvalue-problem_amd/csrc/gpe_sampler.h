@@ -129,6 +129,85 @@ __global__ __launch_bounds__(SMP_THREADS) void k_sampler_draw_graded(SamplerGrid
     if (qw) qw[j] = qv;
 }
 
+// ---- a subset of the cells (gpe_sampler_cells) ----------------------------------------------------------------------------------------
+// The same two draws with one indirection: row j of the buffer is cell cells[first + j] of the grid instead of cell first_cell + j.
+// `cells` is the engine-owned copy of the caller's strictly ascending list (a disk, a ball, any mask: gpe_pinn/sampler.py ball_cells /
+// mask_cells); the bind checked every entry against [0, prod shape), so the per-axis index stays below shape[k] and the edge reads stay
+// inside their arrays.  Everything behind the load is k_sampler_draw / k_sampler_draw_graded statement for statement, so row j holds the
+// bits row cells[first + j] of the full grid's set holds: sampler.py cells_points is stratified_points(...)[cells] by construction.
+// One thread per row; the 8-byte index loads of a wave are consecutive (one coalesced global_load_dwordx2 each); plain vector stores only.
+__global__ __launch_bounds__(SMP_THREADS) void k_sampler_draw_cells(SamplerGrid g, const int64_t* __restrict__ cells, int64_t first, int64_t n,
+                                                                    uint64_t draw, float* __restrict__ x, float* __restrict__ xs) {
+    const int64_t j = (int64_t)blockIdx.x * SMP_THREADS + threadIdx.x;
+    if (j >= n) return;
+    const uint64_t cell = (uint64_t)cells[first + j];
+    uint32_t r[4];
+    philox4x32_10((uint32_t)cell, (uint32_t)(cell >> 32), (uint32_t)draw, (uint32_t)(draw >> 32), g.key0, g.key1, r);
+    uint64_t rest = cell;
+    float v[3];
+#pragma unroll
+    for (int k = 2; k >= 0; --k) {
+        if (k >= g.dim) continue;
+        const uint64_t s = (uint64_t)g.shape[k];
+        const uint64_t q = rest / s;
+        const float ik = (float)(uint32_t)(rest - q * s);
+        rest = q;
+        const float u = (float)(r[k] >> 8) * 0x1p-24f;
+        const float t = ik + u;
+        float xv = smp_mul_then_add(g.lo[k], t, g.h[k]);
+        xv = xv < g.clip_lo[k] ? g.clip_lo[k] : xv;
+        xv = xv > g.clip_hi[k] ? g.clip_hi[k] : xv;
+        v[k] = xv;
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        if (k >= g.dim) continue;
+        x[j * g.dim + k] = v[k];
+        if (xs) { xs[j * g.dim + k] = v[k]; xs[(n + j) * g.dim + k] = -v[k]; }
+    }
+}
+
+__global__ __launch_bounds__(SMP_THREADS) void k_sampler_draw_graded_cells(SamplerGrid g, const float* __restrict__ e0, const float* __restrict__ e1,
+                                                                           const float* __restrict__ e2, const int64_t* __restrict__ cells,
+                                                                           int64_t first, int64_t n, uint64_t draw, float* __restrict__ x,
+                                                                           float* __restrict__ qw) {
+    const int64_t j = (int64_t)blockIdx.x * SMP_THREADS + threadIdx.x;
+    if (j >= n) return;
+    const uint64_t cell = (uint64_t)cells[first + j];
+    uint32_t r[4];
+    philox4x32_10((uint32_t)cell, (uint32_t)(cell >> 32), (uint32_t)draw, (uint32_t)(draw >> 32), g.key0, g.key1, r);
+    uint64_t rest = cell;
+    float v[3], w[3];
+#pragma unroll
+    for (int k = 2; k >= 0; --k) {
+        if (k >= g.dim) continue;
+        const float* __restrict__ ed = k == 0 ? e0 : (k == 1 ? e1 : e2);
+        const uint64_t s = (uint64_t)g.shape[k];
+        const uint64_t q = rest / s;
+        const uint32_t ik = (uint32_t)(rest - q * s);         // < shape[k]: edges_k holds shape[k] + 1 entries
+        rest = q;
+        const float a = ed[ik], b = ed[ik + 1];
+        const float u = (float)(r[k] >> 8) * 0x1p-24f;
+        w[k] = b - a;
+        float xv = smp_mul_then_add(a, u, w[k]);
+        xv = xv < g.clip_lo[k] ? g.clip_lo[k] : xv;
+        xv = xv > g.clip_hi[k] ? g.clip_hi[k] : xv;
+        v[k] = xv;
+    }
+    float qv = w[0];
+#pragma unroll
+    for (int k = 1; k < 3; ++k) {
+        if (k >= g.dim) continue;
+        qv = qv * w[k];
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        if (k >= g.dim) continue;
+        x[j * g.dim + k] = v[k];
+    }
+    if (qw) qw[j] = qv;
+}
+
 // ---- residual-adaptive allocation (gpe_sampler_adaptive) -------------------------------------------------------------------------------
 // The cells of a graded grid become BLOCKS that hold a varying number of rows: block b (row-major, last axis fastest) holds rows
 // [off[b], off[b + 1]) of a buffer of fixed length N, every one of them a uniformly placed point of the block with weight v_b / n_b.

@@ -132,8 +132,8 @@ class GPEConfig:
 class _DeviceArrayView:
     """A float32 device buffer the engine owns, described by the CUDA array interface so that torch can read it in place."""
 
-    def __init__(self, ptr: int, shape):
-        self.__cuda_array_interface__ = dict(shape=tuple(shape), typestr="<f4", data=(int(ptr), False), version=2, strides=None)
+    def __init__(self, ptr: int, shape, typestr: str = "<f4"):
+        self.__cuda_array_interface__ = dict(shape=tuple(shape), typestr=typestr, data=(int(ptr), False), version=2, strides=None)
 
 
 def _check_dev_f32(t: torch.Tensor, name: str):
@@ -460,6 +460,48 @@ class Engine:
         self._keep["x"], self._keep["V"] = None, None
         self._keep.pop("q", None)
         self.n_local = int(n_points)
+
+    def bind_sampler_cells(self, cells, lo, hi, shape, every: int, seed: int = 0, clip=None, edges=None, first: int = 0, n_local=None,
+                           draw0: int = 0):
+        """Cell-subset sampler: bind_sampler (edges None) or bind_sampler_graded (edges: one array per axis, whose end values are lo / hi)
+        on the cells of the strictly ascending int64 list `cells` alone -- a disk, a ball, any mask (sampler.ball_cells / mask_cells) --
+        so the rows outside are never launched.  This engine holds rows first .. first + n_local - 1 of the list (n_local None: the rest).
+        Uniform: set cfg.dx to the cell volume and n_global to len(cells); graded: the rows carry their cell volumes as weights with
+        total = sampler.cells_total(cells, edges), so set cfg.dx = 1.  sampler.cells_points / cells_weights rebuild points and weights
+        on the CPU, bit for bit."""
+        from . import sampler
+        c = np.ascontiguousarray(np.asarray(cells).ravel(), dtype=np.int64)
+        if c.size == 0:
+            raise ValueError("bind_sampler_cells: the list of cells is empty")
+        shp = [int(v) for v in np.atleast_1d(np.asarray(shape)).ravel()]
+        d = len(shp)
+        if not 1 <= d <= capi.GPE_MAX_DIM:
+            raise ValueError(f"shape: 1 to {capi.GPE_MAX_DIM} axes")
+        lo32, hi32 = sampler._per_axis(lo, d, "lo"), sampler._per_axis(hi, d, "hi")
+        clo, chi = (lo32, hi32) if clip is None else (sampler._per_axis(clip[0], d, "clip[0]"), sampler._per_axis(clip[1], d, "clip[1]"))
+        ed = None if edges is None else sampler._edges(edges)
+        if ed is not None and [a.size - 1 for a in ed] != shp:
+            raise ValueError("edges: shape[k] + 1 values per axis")
+        sp = capi.gpe_sampler_spec()          # what the engine cannot honour it refuses itself (GPE_ERR_INVALID): nothing else is judged here
+        for k in range(d):
+            sp.shape[k] = shp[k]
+            sp.lo[k], sp.hi[k], sp.clip_lo[k], sp.clip_hi[k] = float(lo32[k]), float(hi32[k]), float(clo[k]), float(chi[k])
+        sp.seed = int(seed) & (2 ** 64 - 1)
+        sp.first_cell = int(first)
+        sp.n_local = c.size - int(first) if n_local is None else int(n_local)
+        sp.draw0, sp.every = int(draw0), int(every)
+        ptrs = [ed[k].ctypes.data_as(C.c_void_p) if ed is not None and k < d else None for k in range(3)]
+        self._chk(self.lib.gpe_sampler_cells(self._h, C.byref(sp), c.ctypes.data_as(C.c_void_p), c.size, *ptrs))
+        self._keep["x"], self._keep["V"] = None, None
+        self._keep.pop("q", None)
+        self.n_local = int(sp.n_local)
+
+    def sampler_cells(self):
+        """(copy of the list of cells the engine holds as an int64 numpy array, this engine's first row in it); synchronises."""
+        p, n, f = C.c_void_p(), C.c_int64(), C.c_int64()
+        self._chk(self.lib.gpe_sampler_cells_read(self._h, C.byref(p), C.byref(n), C.byref(f)))
+        view = _DeviceArrayView(p.value, (int(n.value),), "<i8")
+        return torch.as_tensor(view, device=f"cuda:{self.device}").cpu().numpy().copy(), int(f.value)
 
     def adaptive_state(self) -> dict:
         """dict(mass, total, counts, draw): the block masses (float64 [B]) and their total that produced the counts (int32 [B]) of the

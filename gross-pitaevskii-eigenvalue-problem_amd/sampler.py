@@ -74,14 +74,24 @@ def stratified_points(lo, hi, shape, seed, draw, first_cell: int = 0, n=None, cl
     n = total - first_cell if n is None else int(n)
     if first_cell < 0 or n <= 0 or first_cell + n > total:
         raise ValueError(f"cells [{first_cell}, {first_cell + n}) outside the grid's {total}")
+    return _uniform_rows(np.arange(first_cell, first_cell + n, dtype=np.uint64), shape, lo, h, clo, chi, seed, draw)
+
+
+def _words(cell, seed, draw):
+    """The four Philox words of every cell (uint64 [n]) of draw `draw`: counter (cell lo, cell hi, draw lo, draw hi), key (seed lo, seed hi)."""
     seed, draw = int(seed) & (2 ** 64 - 1), int(draw) & (2 ** 64 - 1)
-    cell = np.arange(first_cell, first_cell + n, dtype=np.uint64)
-    ctr = np.empty((n, 4), dtype=np.uint64)
+    ctr = np.empty((cell.size, 4), dtype=np.uint64)
     ctr[:, 0], ctr[:, 1] = cell & _MASK, cell >> _S32
     ctr[:, 2], ctr[:, 3] = draw & 0xFFFFFFFF, draw >> 32
-    r = philox4x32(ctr, np.array([seed & 0xFFFFFFFF, seed >> 32], dtype=np.uint64))
+    return philox4x32(ctr, np.array([seed & 0xFFFFFFFF, seed >> 32], dtype=np.uint64))
+
+
+def _uniform_rows(cell, shape, lo, h, clo, chi, seed, draw):
+    """One row per entry of `cell` (uint64 row-major indices of the grid, any order, any subset): stratified_points and cells_points."""
+    d = shape.size
+    r = _words(cell, seed, draw)
     idx = np.unravel_index(cell.astype(np.int64), tuple(int(s) for s in shape))          # row-major: last axis fastest
-    x = np.empty((n, d), dtype=np.float32)
+    x = np.empty((cell.size, d), dtype=np.float32)
     for k in range(d):
         u = (r[:, k] >> np.uint32(8)).astype(np.float32) * np.float32(2.0 ** -24)
         t = idx[k].astype(np.float32) + u
@@ -141,11 +151,13 @@ def graded_points(edges, seed, draw, first_cell: int = 0, n=None, clip=None) -> 
     chi = np.array([a[-1] for a in ed], np.float32) if clip is None else _per_axis(clip[1], d, "clip[1]")
     if np.any(chi < clo):
         raise ValueError("clip[1] < clip[0]")
-    seed, draw = int(seed) & (2 ** 64 - 1), int(draw) & (2 ** 64 - 1)
-    ctr = np.empty((cell.size, 4), dtype=np.uint64)
-    ctr[:, 0], ctr[:, 1] = cell & _MASK, cell >> _S32
-    ctr[:, 2], ctr[:, 3] = draw & 0xFFFFFFFF, draw >> 32
-    r = philox4x32(ctr, np.array([seed & 0xFFFFFFFF, seed >> 32], dtype=np.uint64))
+    return _graded_rows(ed, cell, idx, clo, chi, seed, draw)
+
+
+def _graded_rows(ed, cell, idx, clo, chi, seed, draw):
+    """One row per entry of `cell` (uint64, with its per-axis indices idx): graded_points and cells_points."""
+    d = len(ed)
+    r = _words(cell, seed, draw)
     x = np.empty((cell.size, d), dtype=np.float32)
     for k in range(d):
         u = (r[:, k] >> np.uint32(8)).astype(np.float32) * np.float32(2.0 ** -24)
@@ -191,6 +203,113 @@ def sinh_edges(half, cells, stretch):
     e = (half * r).astype(np.float32) * np.sign(t).astype(np.float32)
     e[0], e[-1] = -np.float32(half), np.float32(half)
     return e
+
+
+# ---- a subset of the cells (csrc/gpe_sampler.h: k_sampler_draw_cells / k_sampler_draw_graded_cells, include/gpe_hip.h: gpe_sampler_cells) ----
+# Row j of the set is cell cells[j] of the grid, everything else as above: cells_points is stratified_points(...)[cells] (edges None) or
+# graded_points(...)[cells], computed from the listed cells alone -- the same helper functions on another index array -- so a grid far too
+# large to build is fine.  The weights of the graded form are the listed cells' volumes, their total W the fp64 sum in list order.
+
+def _cell_list(cells, shape):
+    c = np.asarray(cells)
+    if c.size and not np.issubdtype(c.dtype, np.integer):
+        raise ValueError("cells: integers")
+    c = c.astype(np.int64).ravel()
+    total = 1
+    for s in shape:
+        total *= int(s)
+    if c.size and (int(c.min()) < 0 or int(c.max()) >= total):
+        raise ValueError(f"cells: outside the grid's {total}")
+    if np.any(c[1:] <= c[:-1]):
+        raise ValueError(f"cells: not strictly ascending at position {int(np.flatnonzero(c[1:] <= c[:-1])[0]) + 1}")
+    return c
+
+
+def cells_points(cells, lo, hi, shape, seed, draw, clip=None, edges=None) -> np.ndarray:
+    """Draw `draw` of the set Engine.bind_sampler_cells holds with the whole list: float32 [len(cells), d], row j the point of cell
+    cells[j].  edges None: the uniform grid of `shape` cells over [lo, hi]; else the graded grid bounded by `edges` (lo, hi are its end
+    edges and are not read).  clip as for stratified_points / graded_points.  A block of rows is a slice of the result."""
+    if edges is None:
+        shape, lo, hi, h, clo, chi = grid_spec(lo, hi, shape, clip)
+        c = _cell_list(cells, shape)
+        return _uniform_rows(c.astype(np.uint64), shape, lo, h, clo, chi, seed, draw)
+    ed = _edges(edges)
+    d = len(ed)
+    shp = tuple(a.size - 1 for a in ed)
+    if tuple(int(s) for s in np.atleast_1d(np.asarray(shape)).ravel()) != shp:
+        raise ValueError("edges: shape[k] + 1 values per axis")
+    c = _cell_list(cells, shp)
+    clo = np.array([a[0] for a in ed], np.float32) if clip is None else _per_axis(clip[0], d, "clip[0]")
+    chi = np.array([a[-1] for a in ed], np.float32) if clip is None else _per_axis(clip[1], d, "clip[1]")
+    if np.any(chi < clo):
+        raise ValueError("clip[1] < clip[0]")
+    return _graded_rows(ed, c.astype(np.uint64), np.unravel_index(c, shp), clo, chi, seed, draw)
+
+
+def cells_weights(cells, edges) -> np.ndarray:
+    """The volumes of the listed cells, float32 [len(cells)]: graded_weights(edges)[cells], from the listed cells alone."""
+    ed = _edges(edges)
+    shp = tuple(a.size - 1 for a in ed)
+    idx = np.unravel_index(_cell_list(cells, shp), shp)
+    q = None
+    for k in range(len(ed)):
+        w = ed[k][idx[k] + 1] - ed[k][idx[k]]
+        q = w if q is None else q * w
+    return q.astype(np.float32)
+
+
+def cells_total(cells, edges) -> float:
+    """W of the graded cell-subset sampler: the fp64 sum, in list order, of cells_weights (0.0 for an empty list)."""
+    q = cells_weights(cells, edges).astype(np.float64)
+    return float(np.cumsum(q)[-1]) if q.size else 0.0          # (cumsum adds in list order; np.sum adds pairwise)
+
+
+def cell_centres(lo, hi, shape, edges=None):
+    """[float64 array of cell centres per axis].  Uniform grid: ((shape - i - 1/2) lo + (i + 1/2) hi) / shape with lo, hi as the engine
+    holds them (rounded to float32 first) -- a form that maps i -> shape - 1 - i onto c -> -c exactly when lo = -hi; graded: the
+    midpoints of the float32 edges."""
+    if edges is not None:
+        return [(a[:-1].astype(np.float64) + a[1:].astype(np.float64)) / 2 for a in _edges(edges)]
+    shape, lo, hi, _, _, _ = grid_spec(lo, hi, shape)
+    out = []
+    for k in range(shape.size):
+        i = np.arange(int(shape[k]), dtype=np.float64)
+        out.append(((float(shape[k]) - i - 0.5) * float(lo[k]) + (i + 0.5) * float(hi[k])) / float(shape[k]))
+    return out
+
+
+def mask_cells(lo, hi, shape, predicate, edges=None) -> np.ndarray:
+    """The cells whose centre satisfies `predicate` -- called with a float64 [n, d] array of centres, returning n booleans -- as the
+    ascending int64 list bind_sampler_cells takes.  Host-only; the grid is walked in slabs along its first axis, never built whole."""
+    cen = cell_centres(lo, hi, shape, edges)
+    shp = [a.size for a in cen]
+    d = len(shp)
+    rest = np.stack([g.ravel() for g in np.meshgrid(*cen[1:], indexing="ij")], axis=1) if d > 1 else np.zeros((1, 0))
+    out = []
+    for i in range(shp[0]):
+        x = np.concatenate([np.full((rest.shape[0], 1), cen[0][i]), rest], axis=1)
+        keep = np.asarray(predicate(x), dtype=bool).ravel()
+        if keep.size != rest.shape[0]:
+            raise ValueError("predicate: one boolean per centre")
+        out.append(np.flatnonzero(keep).astype(np.int64) + i * rest.shape[0])
+    return np.concatenate(out) if out else np.zeros(0, np.int64)
+
+
+def ball_cells(lo, hi, shape, radius, centre=None, edges=None) -> np.ndarray:
+    """The cells whose CENTRE lies within `radius` of `centre` (default the origin): sum_k (c_k - centre_k)^2 <= radius^2 in float64,
+    the squares added in axis order.  An interval, a disk or a ball by the grid's dimension; ascending int64.  radius <= 0 keeps nothing."""
+    d = len(cell_centres(lo, hi, shape, edges))
+    c0 = np.zeros(d) if centre is None else np.asarray(centre, dtype=np.float64).ravel()
+    if c0.size != d:
+        raise ValueError(f"centre: one value per axis ({d})")
+    r2 = float(radius) ** 2
+
+    def inside(x):
+        s = np.zeros(x.shape[0])
+        for k in range(d):
+            s = s + (x[:, k] - c0[k]) ** 2
+        return s <= r2 if radius > 0 else np.zeros(x.shape[0], dtype=bool)
+    return mask_cells(lo, hi, shape, inside, edges)
 
 
 # ---- residual-adaptive allocation (csrc/gpe_sampler.h: k_adaptive_alloc / k_sampler_draw_adaptive, include/gpe_hip.h: gpe_sampler_adaptive)

@@ -398,6 +398,42 @@ int gpe_sampler_adaptive_state(gpe_engine* e, double* h_mass /*[B]*/, double* ma
  * the bind); either pointer may be NULL.  GPE_ERR_STATE: no adaptive sampler bound.
  * Replaces: the caller remembering prod(shape) of its own bind. */
 int gpe_sampler_adaptive_blocks(gpe_engine* e, int64_t* n_blocks, int64_t* n_points);
+/* Cell-subset sampler: the uniform or the graded stratified sampler on a SUBSET of the grid's cells -- a disk, a ball, an annulus, any
+ * mask -- so that rows which would carry nothing are never launched.  spec.shape / lo / hi / clip_* / seed / draw0 / every mean what they
+ * mean for gpe_bind_sampler; h_cells [n_cells]: HOST array, the global list of kept cells as row-major indices of that grid (last axis
+ * fastest), strictly ascending, copied to the device here and owned by the engine (its pointer stays until the next bind of a sampler
+ * or of points).  spec.first_cell / n_local index the LIST: this engine holds rows [first_cell, first_cell + n_local) of it, so ranks
+ * holding contiguous blocks of the list hold, together, the world-1 set.
+ *   rows    row j of the local batch is cell c = h_cells[first_cell + j]
+ *   point   Philox4x32-10, counter (c & 0xffffffff, c >> 32, draw & 0xffffffff, draw >> 32), key (seed & 0xffffffff, seed >> 32), output
+ *           word k for axis k; everything behind it exactly as gpe_bind_sampler (all h_edges NULL: the uniform grid) or as
+ *           gpe_bind_sampler_graded (h_edges{k} given for every used axis): the row holds the bits row c of the full grid's set holds
+ *   uniform no weights are bound and the step runs on the kernels of gpe_bind_sampler (gpe_active_kernels is unchanged); the caller sets
+ *           gpe_config.dx to the cell volume and n_global to n_cells
+ *   graded  the rows get their cells' fp32 volumes as weights, as gpe_bind_sampler_graded binds them (set dx = 1): w_local = the fp64 sum
+ *           over this engine's rows; w_total = W = the fp64 sum, in list order, over the WHOLE list of the same fp32 volumes, formed on
+ *           the host at the bind.  gpe_weights reports both
+ *   when    draw0 at the bind; the redraw is enqueued before the first kernel of step m * every, counted on the host since the bind, as
+ *           for gpe_bind_sampler
+ * gpe_pinn/sampler.py (cells_points, cells_weights, cells_total; ball_cells / mask_cells build lists) restates all of it, bit for bit.
+ * gpe_step, gpe_run and its graph cutting, gpe_step_begin, gpe_step_dp / gpe_run_dp, gpe_sampler_points, the refill of frozen
+ * orthogonality states behind every redraw, the monitor, the keeper and the mixture engines behave as with the uniform / graded
+ * sampler.  It replaces a sampler of any other kind and any other replaces it; gpe_bind_sampler(NULL) and gpe_bind_points clear it, list and
+ * weights included.  While it is bound gpe_bind_orth with an array, gpe_bind_target, the gpe_mse_* and gpe_lbfgs_* entry points and
+ * gpe_bind_weights answer as for any sampler with every > 0.
+ * GPE_ERR_INVALID, each leaving the engine as it was: whatever gpe_bind_sampler refuses (with first_cell + n_local held to n_cells);
+ * h_cells NULL or n_cells <= 0; a list that is not strictly ascending (the message names the first offending position); a cell outside
+ * [0, prod shape); edges given for some used axes but not all; whatever gpe_bind_sampler_graded refuses of edges, lo / hi and w_sym.
+ * Replaces: the corner cells of tools/accuracy_nd.py's box, which a radially trapped state leaves empty (--ball), and, for any problem
+ * whose potential the engine evaluates itself, a host-side draw on a disk like the reference's prepare_training_data
+ * (src/gross_pitaevskii_2D.py).  Not the 2D classes of gpe_pinn/surface.py themselves: their two-dimensional Gaussian potential is fed as
+ * GPE_POT_PRECOMPUTED (GPE_POT_GAUSSIAN is the notebook's exp(-(x - a)^2) along x), which every sampler refuses. */
+int gpe_sampler_cells(gpe_engine* e, const gpe_sampler_spec* spec, const int64_t* h_cells, int64_t n_cells,
+                      const float* h_edges0, const float* h_edges1, const float* h_edges2);
+/* synchronise; the engine-owned DEVICE copy of the list, its length and this engine's first row in it.  Any out pointer may be NULL.
+ * GPE_ERR_STATE: no cell-subset sampler bound.
+ * Replaces: the caller keeping its own copy of the list it bound. */
+int gpe_sampler_cells_read(gpe_engine* e, const int64_t** d_cells, int64_t* n_cells, int64_t* first);
 
 /* ---- forward-only entry points ---------------------------------------------------------------- */
 /* model.forward(x) (refine/...:121-125): d_out [n, out] row-major */

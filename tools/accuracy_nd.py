@@ -48,6 +48,9 @@ ap.add_argument("--adaptive", type=int, nargs="?", const=32, default=None, metav
                 help="with --device-sampler: train on the residual-ADAPTIVE sampler (Engine.bind_sampler_adaptive) -- BLOCKS blocks per axis over the box "
                      "(np.linspace edges, or with --graded STRETCH its sinh_edges), the grid's point count shared out among them anew at every redraw")
 ap.add_argument("--adaptive-share", type=float, default=0.5, help="--adaptive: the share of the rows always allocated by volume (uniform_share)")
+ap.add_argument("--ball", type=float, default=None, metavar="R",
+                help="with --device-sampler: train on the cells of the case's grid whose centre lies within R of the origin alone "
+                     "(Engine.bind_sampler_cells on sampler.ball_cells; with --graded on the graded grid's cells), boundary points on the sphere of radius R")
 ap.add_argument("--big-grid", default="", help="e.g. 64,128,64: after the schedule, continue on THIS grid (BASELINE's per-GPU size) for --big-epochs epochs "
                                                "at the low end of the learning-rate ladder, and evaluate mu there (same weights, fresh Adam)")
 ap.add_argument("--big-epochs", type=int, default=3000)
@@ -81,6 +84,16 @@ else:
             cols.insert(ax, np.full(cols[0].shape, side))
             faces.append(np.stack(cols, axis=1))
     xb = np.concatenate(faces).astype(np.float32)
+if a.ball is not None:                      # the boundary of the ball instead: as many points as the faces carry
+    if d == 1:
+        xb = np.array([[-a.ball], [a.ball]], np.float32)
+    elif d == 2:
+        phi = 2.0 * np.pi * np.arange(xb.shape[0]) / xb.shape[0]
+        xb = (a.ball * np.stack([np.cos(phi), np.sin(phi)], axis=1)).astype(np.float32)
+    else:                                   # Fibonacci lattice on the sphere
+        i = np.arange(xb.shape[0]) + 0.5
+        z, phi = 1.0 - 2.0 * i / xb.shape[0], np.pi * (1.0 + 5.0 ** 0.5) * i
+        xb = (a.ball * np.stack([np.sqrt(1.0 - z * z) * np.cos(phi), np.sqrt(1.0 - z * z) * np.sin(phi), z], axis=1)).astype(np.float32)
 
 truth = json.load(open(os.path.join(ROOT, "oracle", "gp_ground_truth.json")))[cs["truth"]]
 mu_ref = truth["mu"]
@@ -108,6 +121,8 @@ if a.graded is not None and not device_sampler:
     ap.error("--graded needs --device-sampler and --resample")
 if adaptive and not device_sampler:
     ap.error("--adaptive needs --device-sampler and --resample")
+if a.ball is not None and (not device_sampler or adaptive or not a.ball > 0):
+    ap.error("--ball R > 0 needs --device-sampler and --resample, and does not combine with --adaptive")
 if a.resample > 0 and not device_sampler:
     rng = np.random.default_rng(1234 + a.seed)
     for _ in range(a.sets):
@@ -144,7 +159,7 @@ for i in range(a.pretrain):
     elif i % 500 == 0:
         print(f"pretrain {i}: mse {sc['loss']:.3e}", flush=True)
 eng.bind_target(None)
-edges = None
+edges, cells = None, None
 if adaptive:
     from gpe_pinn.sampler import sinh_edges
     ax_edges = sinh_edges(half, a.adaptive, a.graded) if a.graded is not None else np.linspace(-half, half, a.adaptive + 1).astype(np.float32)
@@ -153,12 +168,22 @@ if adaptive:
 elif graded:
     from gpe_pinn.sampler import sinh_edges
     edges = [sinh_edges(half, n, a.graded)] * d
-    eng.bind_sampler_graded(edges, every=a.resample, seed=1234 + a.seed)
+    if a.ball is not None:
+        from gpe_pinn.sampler import ball_cells
+        cells = ball_cells([-half] * d, [half] * d, (n,) * d, a.ball, edges=edges)
+        eng.bind_sampler_cells(cells, [-half] * d, [half] * d, (n,) * d, every=a.resample, seed=1234 + a.seed, edges=edges)
+    else:
+        eng.bind_sampler_graded(edges, every=a.resample, seed=1234 + a.seed)
 elif device_sampler:
     # cells centred on the grid nodes (so the quadrature weight stays the cell volume dv), points kept inside the physical box
     from gpe_pinn.sampler import node_centred
     s_lo, s_hi, s_clip = node_centred([half] * d, [n] * d)
-    eng.bind_sampler(s_lo, s_hi, (n,) * d, every=a.resample, seed=1234 + a.seed, clip=s_clip)
+    if a.ball is not None:                  # the same grid, draws and clip box; the rows outside the ball are never launched (N of the means: the rows held)
+        from gpe_pinn.sampler import ball_cells
+        cells = ball_cells(s_lo, s_hi, (n,) * d, a.ball)
+        eng.bind_sampler_cells(cells, s_lo, s_hi, (n,) * d, every=a.resample, seed=1234 + a.seed, clip=s_clip)
+    else:
+        eng.bind_sampler(s_lo, s_hi, (n,) * d, every=a.resample, seed=1234 + a.seed, clip=s_clip)
 # ---- gamma continuation ----
 gam = [cs["g"] * (k / a.stages) ** 2 for k in range(a.stages + 1)]            # quadratic ramp: small steps where the state changes fastest
 rows = []
@@ -272,6 +297,7 @@ out = dict(case=a.case, workload=cs["workload"], layers=cs["layers"], points=int
                          sampler=("device_adaptive" if adaptive else "device_graded" if graded else "device" if device_sampler else "host_cycle") if a.resample > 0 else "fixed_grid",
                          adaptive=(dict(blocks_per_axis=a.adaptive, n_points=n ** d, n_min=1, uniform_share=a.adaptive_share,
                                         uniform_per_1024=int(round(1024 * a.adaptive_share))) if adaptive else None),
+                         ball=(None if cells is None else dict(radius=a.ball, rows_per_step=int(cells.size), share_of_the_grid=float(cells.size) / float(n ** d))),
                          graded_stretch=a.graded, graded_edges=(None if edges is None else [float(v) for v in edges[0]]),
                          scheduler="constant lr per stage, fresh Adam per stage; last stage lr x (1, 0.3, 0.1, 0.03, 0.01, 0.003, 0.001)"),
            energy=rows[-1]["riesz"], energy_ref=truth["energy"], big_grid=big, kept=kept,
