@@ -33,6 +33,7 @@ typedef enum { ncclFloat = 7, ncclDouble = 8 } ncclDataType_t;
 #include "gpe_observe.h"
 #include "gpe_observe_mix.h"
 #include "gpe_sampler.h"
+#include "gpe_sampler_plan.h"
 #include "gpe_generic.h"
 #include "gpe_fused.h"
 #include "gpe_wide_api.h"
@@ -659,31 +660,40 @@ struct gpe_engine {
     int64_t keep_patience = 0;
     float* theta_best = nullptr;                      // [P], the engine's own padded layout
     KeepDev* keep_dev = nullptr;
-    // device-side stratified sampler (gpe_bind_sampler): the engine owns the collocation points and redraws them in place
-    float* smp_x = nullptr;                           // [smp_n][dim]; ux points here while the sampler is bound
-    SamplerGrid smp_grid = {};
-    int64_t smp_n = 0, smp_first = 0, smp_every = 0;  // every == 0: no sampler
-    int64_t smp_draw0 = 0, smp_held = 0;              // draw at the bind / draw the buffer holds (as enqueued)
-    int64_t smp_steps = 0;                            // steps enqueued since the bind
-    // graded sampler (gpe_bind_sampler_graded): the cell edges of every axis, one after the other, and the engine-owned weights
-    bool smp_graded = false;
-    float* smp_edges = nullptr;                       // [sum_k shape[k] + 1]; axis k starts at smp_edge_off[k]
-    int64_t smp_edge_off[3] = {0, 0, 0};
-    float* smp_q = nullptr;                           // [smp_n] cell volumes; wq points here while the graded sampler is bound
-    // residual-adaptive sampler (gpe_sampler_adaptive): a graded sampler whose cells are blocks of varying row counts (smp_graded is
-    // set too: edges, weights and their lifetime are the graded sampler's); every buffer is allocated at the bind
-    bool smp_adaptive = false;
-    AdaptiveDev smp_ad = {};                          // mass [B + 1], count [B], off [B + 1], vol [B] and the allocation's constants
-    float* smp_vol = nullptr;                         // (smp_ad.vol, writable)
-    float* smp_resid = nullptr;                       // [smp_n][n_out]: the residual of the set held, written by the detour before a redraw
-    // cell-subset sampler (gpe_sampler_cells): the uniform or the graded sampler on rows [smp_first, smp_first + smp_n) of a cell list
-    int64_t* smp_cells = nullptr;                     // [smp_cells_n] strictly ascending row-major cell indices; NULL: row j is cell smp_first + j
-    int64_t smp_cells_n = 0;
+    // device-side stratified sampler (gpe_bind_sampler and its kin): the engine owns the collocation points and redraws them in place.
+    // One record for the four kinds; what is allocated says which one is bound (the predicates), and sampler_free resets all of it.
+    struct Sampler {
+        float* x = nullptr;                               // [n][dim]; ux points here while a sampler is bound
+        SamplerGrid grid = {};
+        int64_t n = 0, first = 0, every = 0;              // rows, first cell (or first row of the list); every == 0: no sampler
+        int64_t draw0 = 0, held = 0;                      // draw at the bind / draw the buffer holds (as enqueued)
+        int64_t steps = 0;                                // steps enqueued since the bind
+        // graded (gpe_bind_sampler_graded; the adaptive sampler, and the cell-subset sampler given edges, are graded too): the cell edges
+        // of every axis, one after the other, and the engine-owned weights
+        float* edges = nullptr;                           // [sum_k shape[k] + 1]; axis k starts at edge_off[k]
+        int64_t edge_off[3] = {0, 0, 0};
+        float* q = nullptr;                               // [n] cell volumes; wq points here while a graded sampler is bound
+        // residual-adaptive (gpe_sampler_adaptive): the cells are blocks of varying row counts; every buffer is allocated at the bind
+        struct Adaptive {
+            AdaptiveDev dev = {};                         // mass [B + 1], count [B], off [B + 1], vol [B], share [B] and the allocation's constants
+            float* vol = nullptr;                         // (dev.vol, writable)
+            float* resid = nullptr;                       // [n][n_out]: the residual of the set held, written by the detour before a redraw
+        } ad;
+        // cell subset (gpe_sampler_cells): the rows are [first, first + n) of a list of cells, uniform or graded
+        struct Cells {
+            int64_t* list = nullptr;                      // [n] strictly ascending row-major cell indices
+            int64_t n = 0;
+        } cl;
+        double* wq_red = nullptr;                         // [2] output of k_weight_total: scratch of every weight bind, allocated at the first, kept until the engine goes
+        bool bound() const { return every > 0; }
+        bool graded() const { return edges != nullptr; }
+        bool adaptive() const { return ad.dev.mass != nullptr; }      // (implies graded)
+        bool cells() const { return cl.list != nullptr; }             // (excludes adaptive)
+    } smp;
     // per-point quadrature weights (gpe_bind_weights): every collocation sum takes q_i, every N of a mean becomes W (Phys::n_global)
-    const float* wq = nullptr;                        // [n_pde]: the caller's array, or smp_q; NULL: unweighted
+    const float* wq = nullptr;                        // [n_pde]: the caller's array, or smp.q; NULL: unweighted
     double wq_local = 0.0, wq_total = 0.0;            // sum of this rank's weights / W over all ranks
     float mix_wE = 0.f;                               // mixture energy term (gpe_mixture_energy_weight): its weight, 0 = the plain mixture step
-    double* wq_red = nullptr;                         // [2] output of k_weight_total, allocated at the first bind
     // device-resident L-BFGS (gpe_lbfgs.h): every buffer allocated by gpe_lbfgs_config, freed with the engine
     struct Lbfgs {
         bool on = false;
@@ -1952,6 +1962,7 @@ static void orth_state_free(OrthState& s) {      // the stream is idle, or hipFr
     s = OrthState();
 }
 
+static void sampler_free(gpe_engine* e);
 void gpe_destroy(gpe_engine* e) {
     if (!e) return;
     (void)hipSetDevice(e->device);
@@ -1966,8 +1977,9 @@ void gpe_destroy(gpe_engine* e) {
     for (int k = 0; k < GPE_MAX_ORTH; ++k) orth_state_free(e->ost[k]);
     for (hipEvent_t ev : e->ev_pool) (void)hipEventDestroy(ev);
     if (e->ext_exchange) { e->grad = nullptr; e->dbl = nullptr; }
-    void* ps[] = {e->theta, e->am, e->av, e->grad, e->dbl, e->od, e->hist, e->last, (void*)e->orth_dev, e->Wpk, e->WpkT, e->gslab, e->gslab_bc, e->grad_bc, (void*)e->upd_snap, (void*)e->head_slots, (void*)e->upd_ticket, (void*)e->upd_snap_small, (void*)e->obs_buf, (void*)e->obs_out, (void*)e->mon_ring, (void*)e->smp_x, (void*)e->theta_best, (void*)e->keep_dev, (void*)e->smp_edges, (void*)e->smp_q, (void*)e->wq_red, (void*)e->smp_ad.mass, (void*)e->smp_ad.count, (void*)e->smp_ad.off, (void*)e->smp_ad.share, (void*)e->smp_vol, (void*)e->smp_resid};
+    void* ps[] = {e->theta, e->am, e->av, e->grad, e->dbl, e->od, e->hist, e->last, (void*)e->orth_dev, e->Wpk, e->WpkT, e->gslab, e->gslab_bc, e->grad_bc, (void*)e->upd_snap, (void*)e->head_slots, (void*)e->upd_ticket, (void*)e->upd_snap_small, (void*)e->obs_buf, (void*)e->obs_out, (void*)e->mon_ring, (void*)e->theta_best, (void*)e->keep_dev, (void*)e->smp.wq_red};
     for (void* p : ps) if (p) (void)hipFree(p);
+    sampler_free(e);
     lbfgs_free(e);
     delete e;
 }
@@ -2077,7 +2089,6 @@ static int rebuild_main(gpe_engine* e) {
     return GPE_OK;
 }
 
-static void sampler_clear(gpe_engine* e);
 static bool precomputed_base(const gpe_engine* e);
 static void weights_clear(gpe_engine* e) { e->wq = nullptr; e->wq_local = 0.0; e->wq_total = 0.0; }      // (callers run fill_phys)
 static int orth_resize(gpe_engine* e);
@@ -2108,7 +2119,7 @@ static int bind_points_impl(gpe_engine* e, const float* d_x, int64_t n_local, co
     if ((rc = orth_resize(e))) return rc;
     fill_phys(e);
     e->acc_clean = false;
-    if (e->smp_every <= 0 && (rc = orth_refill(e))) return rc;      // (a sampler's set does not exist yet: sampler_launch fills behind its draw)
+    if (!e->smp.bound() && (rc = orth_refill(e))) return rc;      // (a sampler's set does not exist yet: sampler_launch fills behind its draw)
     HIPCHK(e, hipStreamSynchronize(e->stream));
     return GPE_OK;
 }
@@ -2118,67 +2129,58 @@ int gpe_bind_points(gpe_engine* e, const float* d_x, int64_t n_local, const floa
     if (!d_x || n_local <= 0) FAIL(e, GPE_ERR_INVALID, "bind_points: need n_local > 0 points");
     if (e->cfg.potential == GPE_POT_PRECOMPUTED && !d_V) FAIL(e, GPE_ERR_INVALID, "precomputed potential requested but d_V is NULL");
     HIPCHK(e, hipStreamSynchronize(e->stream));
-    sampler_clear(e);                            // the caller's points take over
+    sampler_free(e);                             // the caller's points take over
     return bind_points_impl(e, d_x, n_local, d_V);
 }
 
 // ---- device-side stratified sampler ------------------------------------------------------------------------
-static void graded_free(gpe_engine* e) {         // the graded sampler's edges and weights (the stream is idle); bound weights that were its own go too
-    if (e->wq && e->wq == e->smp_q) weights_clear(e);
-    if (e->smp_edges) { (void)hipFree(e->smp_edges); e->smp_edges = nullptr; }
-    if (e->smp_q) { (void)hipFree(e->smp_q); e->smp_q = nullptr; }
-    e->smp_graded = false;
-    // ... and what the adaptive sampler adds to them
-    if (e->smp_ad.mass) (void)hipFree(e->smp_ad.mass);
-    if (e->smp_ad.count) (void)hipFree(e->smp_ad.count);
-    if (e->smp_ad.off) (void)hipFree(e->smp_ad.off);
-    if (e->smp_ad.share) (void)hipFree(e->smp_ad.share);
-    if (e->smp_vol) { (void)hipFree(e->smp_vol); e->smp_vol = nullptr; }
-    if (e->smp_resid) { (void)hipFree(e->smp_resid); e->smp_resid = nullptr; }
-    e->smp_ad = AdaptiveDev{};
-    e->smp_adaptive = false;
+// what a re-bind replaces but the point buffer: edges, weights, adaptive buffers, the list (the stream is idle); bound weights that were
+// the sampler's own go too
+static void sampler_free_parts(gpe_engine* e) {
+    gpe_engine::Sampler& s = e->smp;
+    if (e->wq && e->wq == s.q) weights_clear(e);
+    void* ps[] = {s.edges, s.q, s.ad.dev.mass, s.ad.dev.count, s.ad.dev.off, s.ad.dev.share, s.ad.vol, s.ad.resid, s.cl.list};
+    for (void* p : ps) if (p) (void)hipFree(p);
+    s.edges = nullptr; s.q = nullptr;
+    s.edge_off[0] = s.edge_off[1] = s.edge_off[2] = 0;
+    s.ad = gpe_engine::Sampler::Adaptive{};
+    s.cl = gpe_engine::Sampler::Cells{};
 }
-static void cells_free(gpe_engine* e) {          // the cell list of gpe_sampler_cells (the stream is idle)
-    if (e->smp_cells) { (void)hipFree(e->smp_cells); e->smp_cells = nullptr; }
-    e->smp_cells_n = 0;
-}
-static void sampler_clear(gpe_engine* e) {       // the stream is idle (callers synchronise first)
-    if (e->smp_x) { (void)hipFree(e->smp_x); e->smp_x = nullptr; }
-    graded_free(e);
-    cells_free(e);
-    e->smp_n = 0; e->smp_every = 0; e->smp_steps = 0; e->smp_draw0 = 0; e->smp_held = 0; e->smp_first = 0;
+// everything: no sampler is bound behind this (the stream is idle: callers synchronise first).  Only the weight total's scratch stays.
+static void sampler_free(gpe_engine* e) {
+    sampler_free_parts(e);
+    if (e->smp.x) (void)hipFree(e->smp.x);
+    double* red = e->smp.wq_red;
+    e->smp = gpe_engine::Sampler{};
+    e->smp.wq_red = red;
 }
 
 // draw `draw` into the point buffer (and the [x ; -x] batch) on the engine's stream; nothing synchronises
-// (with_weights: the graded sampler's bind, which writes the cell volumes too -- they do not depend on the draw)
+// (with_weights: a graded sampler's bind, which writes the cell volumes too -- they do not depend on the draw)
 static int sampler_launch(gpe_engine* e, int64_t draw, bool with_weights = false) {
-    if (e->smp_adaptive) {                       // counts and offsets from the masses in smp_ad.mass (all zero at the bind), then rows and weights
-        const float* ed = e->smp_edges;
-        hipLaunchKernelGGL(k_adaptive_alloc, dim3(1), dim3(SMP_AD_THREADS), 0, e->stream, e->smp_ad);
-        hipLaunchKernelGGL(k_sampler_draw_adaptive, dim3(cdiv(e->smp_n, SMP_THREADS)), dim3(SMP_THREADS), 0, e->stream, e->smp_grid,
-                           ed + e->smp_edge_off[0], ed + e->smp_edge_off[1], ed + e->smp_edge_off[2], e->smp_ad, (uint64_t)draw,
-                           e->smp_x, e->smp_q);
-    } else if (e->smp_cells && e->smp_graded) {  // (smp_first + smp_n <= smp_cells_n and every entry < prod shape: checked at the bind)
-        const float* ed = e->smp_edges;
-        hipLaunchKernelGGL(k_sampler_draw_graded_cells, dim3(cdiv(e->smp_n, SMP_THREADS)), dim3(SMP_THREADS), 0, e->stream, e->smp_grid,
-                           ed + e->smp_edge_off[0], ed + e->smp_edge_off[1], ed + e->smp_edge_off[2], (const int64_t*)e->smp_cells,
-                           e->smp_first, e->smp_n, (uint64_t)draw, e->smp_x, with_weights ? e->smp_q : (float*)nullptr);
-    } else if (e->smp_cells) {
-        float* xs = (e->cfg.w_sym != 0.f && e->sym.n == 2 * e->smp_n) ? e->sym.xown : nullptr;
-        hipLaunchKernelGGL(k_sampler_draw_cells, dim3(cdiv(e->smp_n, SMP_THREADS)), dim3(SMP_THREADS), 0, e->stream, e->smp_grid,
-                           (const int64_t*)e->smp_cells, e->smp_first, e->smp_n, (uint64_t)draw, e->smp_x, xs);
-    } else if (e->smp_graded) {
-        const float* ed = e->smp_edges;
-        hipLaunchKernelGGL(k_sampler_draw_graded, dim3(cdiv(e->smp_n, SMP_THREADS)), dim3(SMP_THREADS), 0, e->stream, e->smp_grid,
-                           ed + e->smp_edge_off[0], ed + e->smp_edge_off[1], ed + e->smp_edge_off[2], e->smp_first, e->smp_n, (uint64_t)draw,
-                           e->smp_x, with_weights ? e->smp_q : (float*)nullptr);
+    const gpe_engine::Sampler& s = e->smp;
+    const dim3 grid(cdiv(s.n, SMP_THREADS)), block(SMP_THREADS);
+    if (s.graded()) {
+        const float *e0 = s.edges + s.edge_off[0], *e1 = s.edges + s.edge_off[1], *e2 = s.edges + s.edge_off[2];
+        float* qw = with_weights ? s.q : nullptr;
+        if (s.adaptive()) {                      // counts and offsets from the masses in ad.dev.mass (all zero at the bind), then rows and weights
+            hipLaunchKernelGGL(k_adaptive_alloc, dim3(1), dim3(SMP_AD_THREADS), 0, e->stream, s.ad.dev);
+            hipLaunchKernelGGL(k_sampler_draw_adaptive, grid, block, 0, e->stream, s.grid, e0, e1, e2, s.ad.dev, (uint64_t)draw, s.x, s.q);
+        } else if (s.cells()) {                  // (first + n <= cl.n and every entry < prod shape: checked at the bind)
+            hipLaunchKernelGGL(k_sampler_draw_graded_cells, grid, block, 0, e->stream, s.grid, e0, e1, e2, (const int64_t*)s.cl.list, s.first, s.n,
+                               (uint64_t)draw, s.x, qw);
+        } else {
+            hipLaunchKernelGGL(k_sampler_draw_graded, grid, block, 0, e->stream, s.grid, e0, e1, e2, s.first, s.n, (uint64_t)draw, s.x, qw);
+        }
     } else {
-        float* xs = (e->cfg.w_sym != 0.f && e->sym.n == 2 * e->smp_n) ? e->sym.xown : nullptr;
-        hipLaunchKernelGGL(k_sampler_draw, dim3(cdiv(e->smp_n, SMP_THREADS)), dim3(SMP_THREADS), 0, e->stream, e->smp_grid, e->smp_first,
-                           e->smp_n, (uint64_t)draw, e->smp_x, xs);
+        float* xs = (e->cfg.w_sym != 0.f && e->sym.n == 2 * s.n) ? e->sym.xown : nullptr;
+        if (s.cells())
+            hipLaunchKernelGGL(k_sampler_draw_cells, grid, block, 0, e->stream, s.grid, (const int64_t*)s.cl.list, s.first, s.n, (uint64_t)draw, s.x, xs);
+        else
+            hipLaunchKernelGGL(k_sampler_draw, grid, block, 0, e->stream, s.grid, s.first, s.n, (uint64_t)draw, s.x, xs);
     }
     HIPCHK(e, hipGetLastError());
-    e->smp_held = draw;
+    e->smp.held = draw;
     return orth_refill(e);                       // frozen orthogonality states: psi_k of the new set, before the step's first kernel
 }
 
@@ -2191,14 +2193,15 @@ static int sampler_launch(gpe_engine* e, int64_t draw, bool with_weights = false
 static int launch_head_pde(gpe_engine* e, bool energy = false);
 static int launch_seed_pde(gpe_engine* e, float* d_resid, int want_seeds, int head_slots);
 static int adaptive_masses(gpe_engine* e) {
+    const gpe_engine::Sampler& s = e->smp;
     int rc;
     if ((rc = launch_begin(e, /*force=*/true))) return rc;
     if ((rc = mlp_forward(e, e->main, false))) return rc;
     if ((rc = launch_head_pde(e))) return rc;
-    if ((rc = launch_seed_pde(e, e->smp_resid, 0, /*head_slots=*/0))) return rc;
-    const unsigned g = (unsigned)std::min<int64_t>(cdiv((int64_t)e->smp_ad.B, 4), (int64_t)e->num_cu * 4);
-    hipLaunchKernelGGL(k_block_mass, dim3(g), dim3(SMP_MASS_THREADS), 0, e->stream, (const float*)e->smp_resid, (const float*)e->smp_q,
-                       (const int32_t*)e->smp_ad.off, e->nd.n_out, (int)e->smp_ad.B, e->smp_ad.mass);
+    if ((rc = launch_seed_pde(e, s.ad.resid, 0, /*head_slots=*/0))) return rc;
+    const unsigned g = (unsigned)std::min<int64_t>(cdiv((int64_t)s.ad.dev.B, 4), (int64_t)e->num_cu * 4);
+    hipLaunchKernelGGL(k_block_mass, dim3(g), dim3(SMP_MASS_THREADS), 0, e->stream, (const float*)s.ad.resid, (const float*)s.q,
+                       (const int32_t*)s.ad.dev.off, e->nd.n_out, (int)s.ad.dev.B, s.ad.dev.mass);
     HIPCHK(e, hipGetLastError());
     return GPE_OK;
 }
@@ -2207,228 +2210,176 @@ static int adaptive_masses(gpe_engine* e) {
 // (the step starts with k_begin; Phys and the merged-boundary Pts depend on the point count and the pointers only, which stay) --
 // without that call's two synchronisations.
 static int sampler_before_step(gpe_engine* e, bool capturing) {
-    if (e->smp_every <= 0 || capturing) return GPE_OK;
-    const int64_t want = e->smp_draw0 + e->smp_steps / e->smp_every;
-    if (want == e->smp_held) return GPE_OK;
+    const gpe_engine::Sampler& s = e->smp;
+    if (!s.bound() || capturing) return GPE_OK;
+    const int64_t want = s.draw0 + s.steps / s.every;
+    if (want == s.held) return GPE_OK;
     e->acc_clean = false;
     int rc;
-    if (e->smp_adaptive && (rc = adaptive_masses(e))) return rc;
+    if (s.adaptive() && (rc = adaptive_masses(e))) return rc;
     return sampler_launch(e, want);
 }
 
 // one fixed-order fp64 total of a weight array on the engine's stream, read back here: the bind's one synchronisation
 static int weights_total(gpe_engine* e, const float* d_q, int64_t n, double* total, double* bad) {
-    if (!e->wq_red && hipMalloc((void**)&e->wq_red, 2 * sizeof(double) + 256) != hipSuccess) {
+    if (!e->smp.wq_red && hipMalloc((void**)&e->smp.wq_red, 2 * sizeof(double) + 256) != hipSuccess) {
         (void)hipGetLastError();
         FAIL(e, GPE_ERR_NOMEM, "bind_weights: no memory for the weight total");
     }
-    hipLaunchKernelGGL(k_weight_total, dim3(1), dim3(WQ_THREADS), 0, e->stream, d_q, n, e->wq_red);
+    hipLaunchKernelGGL(k_weight_total, dim3(1), dim3(WQ_THREADS), 0, e->stream, d_q, n, e->smp.wq_red);
     HIPCHK(e, hipGetLastError());
     double h[2] = {0.0, 0.0};
-    HIPCHK(e, hipMemcpyAsync(h, e->wq_red, sizeof h, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipMemcpyAsync(h, e->smp.wq_red, sizeof h, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));
     *total = h[0]; *bad = h[1];
     return GPE_OK;
 }
 
-// edges == NULL: the uniform grid of gpe_bind_sampler; else the graded grid of gpe_bind_sampler_graded (one host array per used axis)
-struct AdaptiveArgs { int64_t n_points; int32_t n_min, s; };
-// ad != NULL (with edges): the residual-adaptive sampler of gpe_sampler_adaptive -- the cells are blocks, the buffer holds ad->n_points rows
-// cl != NULL (with or without edges): the cell-subset sampler of gpe_sampler_cells -- first_cell / n_local index the list, not the grid
-struct CellsArgs { const int64_t* h_cells; int64_t n_cells; };
-static int bind_sampler_impl(gpe_engine* e, const gpe_sampler_spec* sp, const float* const* edges, const AdaptiveArgs* ad = nullptr,
-                             const CellsArgs* cl = nullptr) {
-    const char* who = cl ? "sampler_cells" : ad ? "sampler_adaptive" : edges ? "bind_sampler_graded" : "bind_sampler";
-    if (ad && e->comm) FAIL(e, GPE_ERR_STATE, "%s: the engine has a communicator, and a data-parallel allocation needs a mass exchange", who);
-    const int dim = e->nd.dim;
+// ---- the bind, in phases (sampler_bind calls each once, in this order) ----
+// edges NULL: the uniform grid of gpe_bind_sampler, else one host array per used axis; ad (with edges): gpe_sampler_adaptive;
+// cl (with or without edges): gpe_sampler_cells -- first_cell / n_local index the list.  who: sampler_who, the name in every message.
+
+// 1. what the engine's own state rules out; nothing is touched
+static int sampler_refuse_state(gpe_engine* e, const char* who, bool adaptive) {
+    if (adaptive && e->comm) FAIL(e, GPE_ERR_STATE, "%s: the engine has a communicator, and a data-parallel allocation needs a mass exchange", who);
     if (e->cfg.potential == GPE_POT_PRECOMPUTED) FAIL(e, GPE_ERR_INVALID, "%s: a precomputed potential lives on fixed points", who);
     if (precomputed_base(e)) FAIL(e, GPE_ERR_INVALID, "%s: a precomputed base lives on fixed points", who);
     for (int k = 0; k < GPE_MAX_ORTH; ++k)       // (a frozen state is re-evaluated behind every redraw: only caller arrays are refused)
         if (e->orth_host[k] && !e->ost[k].on) FAIL(e, GPE_ERR_INVALID, "%s: orthogonality array %d is bound, and lives on fixed points", who, k);
-    if (sp->every <= 0) FAIL(e, GPE_ERR_INVALID, "%s: every = %lld, need > 0", who, (long long)sp->every);
-    if (edges && e->cfg.w_sym != 0.f) FAIL(e, GPE_ERR_INVALID, "%s: the symmetry batch has no quadrature weights (w_sym != 0)", who);
-    double cells = 1.0;
-    for (int k = 0; k < 3; ++k) {
-        if ((sp->shape[k] > 0) != (k < dim))
-            FAIL(e, GPE_ERR_INVALID, "%s: shape must use exactly the network's %d input axes (shape[%d] = %lld)", who, dim, k, (long long)sp->shape[k]);
-        if (k >= dim) continue;
-        if (sp->shape[k] > (1 << 24)) FAIL(e, GPE_ERR_INVALID, "%s: shape[%d] = %lld, at most 2^24 cells per axis", who, k, (long long)sp->shape[k]);
-        if (!(sp->hi[k] > sp->lo[k])) FAIL(e, GPE_ERR_INVALID, "%s: hi <= lo on axis %d", who, k);
-        if (!(sp->clip_hi[k] >= sp->clip_lo[k])) FAIL(e, GPE_ERR_INVALID, "%s: clip_hi < clip_lo on axis %d", who, k);
-        cells *= (double)sp->shape[k];
-    }
-    if (cl) {                                    // the list: strictly ascending cells of this grid; the rows: a block of the list
-        unsigned __int128 total = 1;             // (up to 2^72 cells: beyond int64, and a double would round the last cell onto the bound)
-        for (int k = 0; k < dim; ++k) total *= (unsigned __int128)sp->shape[k];
-        for (int64_t i = 0; i < cl->n_cells; ++i) {
-            const int64_t c = cl->h_cells[i];
-            if (c < 0 || (unsigned __int128)c >= total)
-                FAIL(e, GPE_ERR_INVALID, "%s: cells[%lld] = %lld outside the grid's %.0f cells", who, (long long)i, (long long)c, cells);
-            if (i > 0 && !(c > cl->h_cells[i - 1]))
-                FAIL(e, GPE_ERR_INVALID, "%s: the list is not strictly ascending at position %lld (%lld after %lld)", who, (long long)i,
-                     (long long)c, (long long)cl->h_cells[i - 1]);
-        }
-        if (sp->first_cell < 0 || sp->n_local <= 0 || sp->n_local > cl->n_cells || sp->first_cell > cl->n_cells - sp->n_local)
-            FAIL(e, GPE_ERR_INVALID, "%s: rows [%lld, %lld + %lld) outside the list's %lld", who, (long long)sp->first_cell, (long long)sp->first_cell,
-                 (long long)sp->n_local, (long long)cl->n_cells);
-    } else if (sp->first_cell < 0 || sp->n_local <= 0 || (double)sp->first_cell + (double)sp->n_local > cells)
-        FAIL(e, GPE_ERR_INVALID, "%s: cells [%lld, %lld + %lld) outside the grid's %.0f", who, (long long)sp->first_cell, (long long)sp->first_cell, (long long)sp->n_local, cells);
-    const int64_t n_rows = ad ? ad->n_points : sp->n_local;
-    if (ad) {
-        if (sp->first_cell != 0 || (double)sp->n_local != cells)
-            FAIL(e, GPE_ERR_INVALID, "%s: single-rank, first_cell must be 0 and n_local the block count %.0f", who, cells);
-        if (ad->n_points <= 0 || ad->n_points > SMP_AD_MAX_POINTS) FAIL(e, GPE_ERR_INVALID, "%s: n_points = %lld, need 1 .. 2^22", who, (long long)ad->n_points);
-        if (ad->n_min < 1 || (double)sp->n_local * (double)ad->n_min > (double)ad->n_points)
-            FAIL(e, GPE_ERR_INVALID, "%s: %lld blocks of at least n_min = %d rows do not fit %lld points", who, (long long)sp->n_local, ad->n_min, (long long)ad->n_points);
-        if (ad->s < 1 || ad->s > 1024) FAIL(e, GPE_ERR_INVALID, "%s: uniform_per_1024 = %d, need 1 .. 1024", who, ad->s);
-    }
-    // graded grid: strictly increasing finite edges that start at lo and end at hi; W = product over the axes of the fp64 sums, in index
-    // order, of the fp32 widths -- of the WHOLE grid, whichever block of cells this rank holds
-    double w_grid = 1.0;
-    int64_t n_edges = 0;
-    if (edges) {
-        for (int k = 0; k < dim; ++k) {
-            const float* ed = edges[k];
-            if (!ed) FAIL(e, GPE_ERR_INVALID, "%s: no edges for axis %d", who, k);
-            double wk = 0.0;
-            for (int64_t i = 0; i <= sp->shape[k]; ++i) {
-                if (!__builtin_isfinite(ed[i])) FAIL(e, GPE_ERR_INVALID, "%s: edge %lld of axis %d is not finite", who, (long long)i, k);
-                if (i > 0 && !(ed[i] > ed[i - 1])) FAIL(e, GPE_ERR_INVALID, "%s: edges of axis %d do not increase at %lld", who, k, (long long)i);
-                if (i > 0) { const float w = ed[i] - ed[i - 1]; wk += (double)w; }
-            }
-            if (ed[0] != sp->lo[k] || ed[sp->shape[k]] != sp->hi[k])
-                FAIL(e, GPE_ERR_INVALID, "%s: lo / hi of axis %d are not its first / last edge", who, k);
-            w_grid *= wk;
-            n_edges += sp->shape[k] + 1;
-        }
-    }
-    // ... of the WHOLE list under gpe_sampler_cells: the fp64 sum, in list order, of the fp32 cell volumes as k_sampler_draw_graded_cells
-    // forms them (fp32 widths, rounded fp32 products in axis order).  Keep this loop BEHIND both validations above: the list scan bounds
-    // every cell by prod shape (so ik[k] < shape[k]) and the edge scan found shape[k] + 1 entries per used axis -- the reads of
-    // edges[k][ik[k] + 1] below check nothing themselves.
-    if (edges && cl) {
-        w_grid = 0.0;
-        for (int64_t i = 0; i < cl->n_cells; ++i) {
-            int64_t rest = cl->h_cells[i], ik[3] = {0, 0, 0};
-            for (int k = dim - 1; k >= 0; --k) { ik[k] = rest % sp->shape[k]; rest /= sp->shape[k]; }
-            float v = edges[0][ik[0] + 1] - edges[0][ik[0]];
-            for (int k = 1; k < dim; ++k) { const float w = edges[k][ik[k] + 1] - edges[k][ik[k]]; v = v * w; }
-            w_grid += (double)v;
-        }
-    }
-    // adaptive: the block volumes as k_sampler_draw_graded forms a cell's (fp32 widths, rounded fp32 products in axis order), and the
-    // volume shares must not all truncate to zero (K_B > 0 in k_adaptive_alloc)
-    std::vector<float> vol;
-    if (ad) {
-        vol.resize((size_t)sp->n_local);
-        uint64_t kv_sum = 0;
-        for (int64_t b = 0; b < sp->n_local; ++b) {
-            int64_t rest = b, ik[3] = {0, 0, 0};
-            for (int k = dim - 1; k >= 0; --k) { ik[k] = rest % sp->shape[k]; rest /= sp->shape[k]; }
-            float v = edges[0][ik[0] + 1] - edges[0][ik[0]];
-            for (int k = 1; k < dim; ++k) { const float w = edges[k][ik[k] + 1] - edges[k][ik[k]]; v = v * w; }
-            vol[(size_t)b] = v;
-            const double share = (double)v / w_grid * 0x1p30;
-            if (share >= 0.0 && share <= 0x1p31) kv_sum += (uint64_t)share;
-        }
-        if (!(w_grid > 0.0) || !__builtin_isfinite(w_grid) || kv_sum == 0)
-            FAIL(e, GPE_ERR_INVALID, "%s: the block volumes underflow or overflow fp32", who);
-    }
+    return GPE_OK;
+}
+
+// 2. the plan: gpe_sampler_plan.h (it judges w_sym with edges too, where that refusal has always stood: behind `every`)
+
+// 3a. synchronise; the engine's copy of the list, and a point buffer if the row count changes (*x stays NULL otherwise: the buffer and a
+// captured graph's pointers stay).  Nothing of the engine changes: a failure here leaves it as it was.
+static int sampler_reserve(gpe_engine* e, const char* who, const CellsArgs* cl, int64_t n_rows, int64_t** d_cells, float** x) {
     HIPCHK(e, hipStreamSynchronize(e->stream));
     if (e->side) HIPCHK(e, hipStreamSynchronize(e->side));
-    int64_t* d_cells = nullptr;                  // the engine's copy of the list, made before anything of the engine changes
     if (cl) {
-        if (hipMalloc((void**)&d_cells, (size_t)cl->n_cells * sizeof(int64_t) + 256) != hipSuccess) {
+        if (hipMalloc((void**)d_cells, (size_t)cl->n_cells * sizeof(int64_t) + 256) != hipSuccess) {
             (void)hipGetLastError();
             FAIL(e, GPE_ERR_NOMEM, "%s: no memory for the list of %lld cells", who, (long long)cl->n_cells);
         }
-        if (hipMemcpy(d_cells, cl->h_cells, (size_t)cl->n_cells * sizeof(int64_t), hipMemcpyHostToDevice) != hipSuccess) {
+        if (hipMemcpy(*d_cells, cl->h_cells, (size_t)cl->n_cells * sizeof(int64_t), hipMemcpyHostToDevice) != hipSuccess) {
             (void)hipGetLastError();
-            (void)hipFree(d_cells);
+            (void)hipFree(*d_cells);
             FAIL(e, GPE_ERR_HIP, "%s: upload of the cell list failed", who);
         }
     }
-    if (e->smp_n != n_rows || !e->smp_x) {      // same size: the buffer (and a captured graph's pointers) stay
-        float* p = nullptr;
-        if (hipMalloc((void**)&p, (size_t)n_rows * dim * sizeof(float) + 256) != hipSuccess) {
-            (void)hipGetLastError();
-            if (d_cells) (void)hipFree(d_cells);
-            FAIL(e, GPE_ERR_NOMEM, "%s: no memory for %lld points", who, (long long)n_rows);
-        }
-        sampler_clear(e);
-        e->smp_x = p;
+    if ((e->smp.n != n_rows || !e->smp.x) && hipMalloc((void**)x, (size_t)n_rows * e->nd.dim * sizeof(float) + 256) != hipSuccess) {
+        (void)hipGetLastError();
+        if (*d_cells) (void)hipFree(*d_cells);
+        FAIL(e, GPE_ERR_NOMEM, "%s: no memory for %lld points", who, (long long)n_rows);
     }
-    graded_free(e);                              // edges and weights of an earlier graded bind
-    cells_free(e);                               // ... and the list of an earlier cell-subset bind
-    e->smp_cells = d_cells; e->smp_cells_n = cl ? cl->n_cells : 0;
-    SamplerGrid& g = e->smp_grid;
-    memset(&g, 0, sizeof g);
-    g.dim = dim; g.key0 = (uint32_t)sp->seed; g.key1 = (uint32_t)(sp->seed >> 32);
-    for (int k = 0; k < dim; ++k) {
-        g.shape[k] = sp->shape[k]; g.lo[k] = sp->lo[k]; g.clip_lo[k] = sp->clip_lo[k]; g.clip_hi[k] = sp->clip_hi[k];
-        g.h[k] = (float)(((double)sp->hi[k] - (double)sp->lo[k]) / (double)sp->shape[k]);
-    }
-    int rc = GPE_OK;
+    return GPE_OK;
+}
+
+// 3b. the old sampler goes -- all of it if a new point buffer x was reserved, else all but the buffer -- and the list, edges, weights and
+// adaptive buffers enter the record.  From here on a failure is sampler_bind_failed's.
+static int sampler_acquire(gpe_engine* e, const char* who, const gpe_sampler_spec* sp, const float* const* edges, const CellsArgs* cl,
+                           const SamplerPlan& plan, int64_t* d_cells, float* x) {
+    gpe_engine::Sampler& s = e->smp;
+    if (x) { sampler_free(e); s.x = x; }
+    else sampler_free_parts(e);
+    if (e->mse_target) { e->mse_target = nullptr; free_batch(e->mse); }      // a pre-training target lived on the points that just went
+    s.cl.list = d_cells; s.cl.n = cl ? cl->n_cells : 0;
     if (edges) {
-        if (hipMalloc((void**)&e->smp_edges, (size_t)n_edges * sizeof(float) + 256) != hipSuccess ||
-            hipMalloc((void**)&e->smp_q, (size_t)n_rows * sizeof(float) + 256) != hipSuccess) {
+        if (hipMalloc((void**)&s.edges, (size_t)plan.n_edges * sizeof(float) + 256) != hipSuccess ||
+            hipMalloc((void**)&s.q, (size_t)plan.n_rows * sizeof(float) + 256) != hipSuccess) {
             (void)hipGetLastError();
-            e->err = std::string(who) + ": no memory for the edges and weights"; rc = GPE_ERR_NOMEM;
+            e->err = std::string(who) + ": no memory for the edges and weights";
+            return GPE_ERR_NOMEM;
         }
         int64_t off = 0;
-        for (int k = 0; k < 3 && !rc; ++k) {
-            e->smp_edge_off[k] = k < dim ? off : 0;      // (unused axes point at axis 0: never read)
-            if (k >= dim) continue;
-            if (hipMemcpy(e->smp_edges + off, edges[k], (size_t)(sp->shape[k] + 1) * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+        for (int k = 0; k < e->nd.dim; ++k) {    // (unused axes keep offset 0, axis 0: never read)
+            s.edge_off[k] = off;
+            if (hipMemcpy(s.edges + off, edges[k], (size_t)(sp->shape[k] + 1) * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
                 (void)hipGetLastError();
-                e->err = std::string(who) + ": upload of the edges failed"; rc = GPE_ERR_HIP;
+                e->err = std::string(who) + ": upload of the edges failed";
+                return GPE_ERR_HIP;
             }
             off += sp->shape[k] + 1;
         }
-        e->smp_graded = !rc;
     }
-    if (ad && !rc) {                             // masses (all zero: the bind allocates by volume), counts, offsets, volumes, residual
-        const size_t B = (size_t)sp->n_local;
-        AdaptiveDev& a = e->smp_ad;
+    if (!plan.vol.empty()) {                     // adaptive: masses (all zero: the bind allocates by volume), counts, offsets, volumes, residual
+        const size_t B = plan.vol.size();
+        AdaptiveDev& a = s.ad.dev;
         if (hipMalloc((void**)&a.mass, (B + 1) * sizeof(double) + 256) != hipSuccess ||
             hipMalloc((void**)&a.count, B * sizeof(int32_t) + 256) != hipSuccess ||
             hipMalloc((void**)&a.off, (B + 1) * sizeof(int32_t) + 256) != hipSuccess ||
             hipMalloc((void**)&a.share, B * sizeof(uint64_t) + 256) != hipSuccess ||
-            hipMalloc((void**)&e->smp_vol, B * sizeof(float) + 256) != hipSuccess ||
-            hipMalloc((void**)&e->smp_resid, (size_t)n_rows * e->nd.n_out * sizeof(float) + 256) != hipSuccess) {
+            hipMalloc((void**)&s.ad.vol, B * sizeof(float) + 256) != hipSuccess ||
+            hipMalloc((void**)&s.ad.resid, (size_t)plan.n_rows * e->nd.n_out * sizeof(float) + 256) != hipSuccess) {
             (void)hipGetLastError();
-            e->err = std::string(who) + ": no memory for the block masses, counts and the residual"; rc = GPE_ERR_NOMEM;
-        } else if (hipMemset(a.mass, 0, (B + 1) * sizeof(double)) != hipSuccess ||
-                   hipMemcpy(e->smp_vol, vol.data(), B * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipGetLastError();
-            e->err = std::string(who) + ": upload of the block volumes failed"; rc = GPE_ERR_HIP;
+            e->err = std::string(who) + ": no memory for the block masses, counts and the residual";
+            return GPE_ERR_NOMEM;
         }
-        a.vol = e->smp_vol; a.B = (int32_t)B; a.N = (int32_t)n_rows; a.n_min = ad->n_min; a.s = ad->s; a.V = w_grid;
-        e->smp_adaptive = !rc;
+        if (hipMemset(a.mass, 0, (B + 1) * sizeof(double)) != hipSuccess ||
+            hipMemcpy(s.ad.vol, plan.vol.data(), B * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipGetLastError();
+            e->err = std::string(who) + ": upload of the block volumes failed";
+            return GPE_ERR_HIP;
+        }
     }
-    e->smp_n = n_rows; e->smp_first = sp->first_cell; e->smp_every = sp->every; e->smp_draw0 = sp->draw0; e->smp_steps = 0;
-    e->smp_held = sp->draw0;
-    if (e->mse_target) { e->mse_target = nullptr; free_batch(e->mse); }      // a pre-training target lived on the points that just went
-    if (!rc) rc = bind_points_impl(e, e->smp_x, e->smp_n, nullptr);      // allocates the symmetry batch; its copy kernel reads a buffer ...
-    if (!rc) rc = sampler_launch(e, sp->draw0, /*with_weights=*/edges != nullptr);       // ... this launch fills, together with [x ; -x]
-    if (!rc && edges) {                          // the cell volumes become the bound weights, W the whole grid's volume
+    return GPE_OK;
+}
+
+// 4. the record's scalars, the bind of the buffer as the collocation batch, the first draw and -- graded -- the weights
+static int sampler_commit(gpe_engine* e, const char* who, const gpe_sampler_spec* sp, const AdaptiveArgs* ad, const SamplerPlan& plan) {
+    gpe_engine::Sampler& s = e->smp;
+    SamplerGrid& g = s.grid;
+    memset(&g, 0, sizeof g);
+    g.dim = e->nd.dim; g.key0 = (uint32_t)sp->seed; g.key1 = (uint32_t)(sp->seed >> 32);
+    for (int k = 0; k < g.dim; ++k) {
+        g.shape[k] = sp->shape[k]; g.lo[k] = sp->lo[k]; g.clip_lo[k] = sp->clip_lo[k]; g.clip_hi[k] = sp->clip_hi[k];
+        g.h[k] = (float)(((double)sp->hi[k] - (double)sp->lo[k]) / (double)sp->shape[k]);
+    }
+    if (ad) {
+        AdaptiveDev& a = s.ad.dev;
+        a.vol = s.ad.vol; a.B = (int32_t)sp->n_local; a.N = (int32_t)plan.n_rows; a.n_min = ad->n_min; a.s = ad->s; a.V = plan.w_grid;
+    }
+    s.n = plan.n_rows; s.first = sp->first_cell; s.every = sp->every; s.draw0 = sp->draw0; s.steps = 0;
+    s.held = sp->draw0;
+    int rc = bind_points_impl(e, s.x, s.n, nullptr);                 // allocates the symmetry batch; its copy kernel reads a buffer ...
+    if (!rc) rc = sampler_launch(e, sp->draw0, /*with_weights=*/s.graded());      // ... this launch fills, together with [x ; -x]
+    if (!rc && s.graded()) {                     // the cell volumes become the bound weights, W the whole grid's (or list's) volume
         double wl = 0.0, bad = 0.0;
-        rc = weights_total(e, e->smp_q, e->smp_n, &wl, &bad);
-        if (!rc && (bad != 0.0 || !(wl > 0.0) || !__builtin_isfinite(wl) || !(w_grid > 0.0) || !__builtin_isfinite(w_grid))) {
+        rc = weights_total(e, s.q, s.n, &wl, &bad);
+        if (!rc && (bad != 0.0 || !(wl > 0.0) || !__builtin_isfinite(wl) || !(plan.w_grid > 0.0) || !__builtin_isfinite(plan.w_grid))) {
             e->err = std::string(who) + ": the cell volumes of this block underflow or overflow fp32"; rc = GPE_ERR_INVALID;
         }
-        if (!rc) { e->wq = e->smp_q; e->wq_local = wl; e->wq_total = w_grid; fill_phys(e); }
+        if (!rc) { e->wq = s.q; e->wq_local = wl; e->wq_total = plan.w_grid; fill_phys(e); }
     }
     if (!rc && hipStreamSynchronize(e->stream) != hipSuccess) { e->err = std::string(who) + ": synchronise failed"; rc = GPE_ERR_HIP; }
-    if (rc) {                                    // never leave a half-bound sampler behind
-        const std::string keep = e->err;
-        (void)hipStreamSynchronize(e->stream);
-        sampler_clear(e);
-        e->ux = nullptr; e->n_pde = 0; free_batch(e->main); free_batch(e->sym);
-        fill_phys(e);
-        e->err = keep;
-    }
     return rc;
+}
+
+// 5. never leave a half-bound sampler behind: no sampler, no points, the error text kept
+static int sampler_bind_failed(gpe_engine* e, int rc) {
+    const std::string keep = e->err;
+    (void)hipStreamSynchronize(e->stream);
+    sampler_free(e);
+    e->ux = nullptr; e->n_pde = 0; free_batch(e->main); free_batch(e->sym);
+    fill_phys(e);
+    e->err = keep;
+    return rc;
+}
+
+static int sampler_bind(gpe_engine* e, const gpe_sampler_spec* sp, const float* const* edges, const AdaptiveArgs* ad = nullptr,
+                        const CellsArgs* cl = nullptr) {
+    const char* who = sampler_who(edges, ad, cl);
+    int rc;
+    if ((rc = sampler_refuse_state(e, who, ad != nullptr))) return rc;
+    SamplerPlan plan;
+    std::string msg;
+    if ((rc = sampler_plan(e->nd.dim, e->cfg.w_sym != 0.f, sp, edges, ad, cl, SMP_AD_MAX_POINTS, &plan, &msg))) { e->err = msg; return rc; }
+    int64_t* d_cells = nullptr;
+    float* x = nullptr;
+    if ((rc = sampler_reserve(e, who, cl, plan.n_rows, &d_cells, &x))) return rc;
+    if ((rc = sampler_acquire(e, who, sp, edges, cl, plan, d_cells, x))) return sampler_bind_failed(e, rc);
+    if ((rc = sampler_commit(e, who, sp, ad, plan))) return sampler_bind_failed(e, rc);
+    return GPE_OK;
 }
 
 int gpe_bind_sampler(gpe_engine* e, const gpe_sampler_spec* sp) {
@@ -2436,10 +2387,10 @@ int gpe_bind_sampler(gpe_engine* e, const gpe_sampler_spec* sp) {
     if (!sp) {                                   // clear: the buffer goes, so nothing stays bound
         HIPCHK(e, hipStreamSynchronize(e->stream));
         if (e->side) HIPCHK(e, hipStreamSynchronize(e->side));
-        if (e->smp_every <= 0) return GPE_OK;
+        if (!e->smp.bound()) return GPE_OK;
         monitor_drop_if_on_bound_points(e);
         graph_drop(e);
-        sampler_clear(e);                        // (a graded sampler's weights go with it)
+        sampler_free(e);                         // (a graded sampler's weights go with it)
         e->ux = nullptr; e->uV = nullptr; e->n_pde = 0;
         free_batch(e->main); free_batch(e->sym);
         if (e->uxb && e->nb_user > 0) { int rc = setup_batch(e, e->bc, e->uxb, e->nb_user, 1, 0, false, nullptr); if (rc) return rc; }
@@ -2448,14 +2399,14 @@ int gpe_bind_sampler(gpe_engine* e, const gpe_sampler_spec* sp) {
         fill_phys(e);
         return GPE_OK;
     }
-    return bind_sampler_impl(e, sp, nullptr);
+    return sampler_bind(e, sp, nullptr);
 }
 
 int gpe_bind_sampler_graded(gpe_engine* e, const gpe_sampler_spec* sp, const float* h_edges0, const float* h_edges1, const float* h_edges2) {
     if (!e) return GPE_ERR_INVALID;
     if (!sp) FAIL(e, GPE_ERR_INVALID, "bind_sampler_graded: no spec (gpe_bind_sampler(NULL) clears a sampler of either kind)");
     const float* edges[3] = {h_edges0, h_edges1, h_edges2};
-    return bind_sampler_impl(e, sp, edges);
+    return sampler_bind(e, sp, edges);
 }
 
 int gpe_sampler_adaptive(gpe_engine* e, const gpe_sampler_spec* sp, const float* h_edges0, const float* h_edges1, const float* h_edges2,
@@ -2464,7 +2415,7 @@ int gpe_sampler_adaptive(gpe_engine* e, const gpe_sampler_spec* sp, const float*
     if (!sp) FAIL(e, GPE_ERR_INVALID, "sampler_adaptive: no spec (gpe_bind_sampler(NULL) clears a sampler of any kind)");
     const float* edges[3] = {h_edges0, h_edges1, h_edges2};
     const AdaptiveArgs ad{n_points, n_min, uniform_per_1024};
-    return bind_sampler_impl(e, sp, edges, &ad);
+    return sampler_bind(e, sp, edges, &ad);
 }
 
 int gpe_sampler_cells(gpe_engine* e, const gpe_sampler_spec* sp, const int64_t* h_cells, int64_t n_cells,
@@ -2473,53 +2424,53 @@ int gpe_sampler_cells(gpe_engine* e, const gpe_sampler_spec* sp, const int64_t* 
     if (!sp) FAIL(e, GPE_ERR_INVALID, "sampler_cells: no spec (gpe_bind_sampler(NULL) clears a sampler of any kind)");
     if (!h_cells || n_cells <= 0) FAIL(e, GPE_ERR_INVALID, "sampler_cells: need a list of n_cells > 0 cells (n_cells = %lld)", (long long)n_cells);
     const float* edges[3] = {h_edges0, h_edges1, h_edges2};
-    bool graded = false;                         // edges on any used axis: graded, and bind_sampler_impl wants them on every used axis
+    bool graded = false;                         // edges on any used axis: graded, and the plan wants them on every used axis
     for (int k = 0; k < e->nd.dim && k < 3; ++k) graded = graded || edges[k] != nullptr;
     const CellsArgs cl{h_cells, n_cells};
-    return bind_sampler_impl(e, sp, graded ? edges : nullptr, nullptr, &cl);
+    return sampler_bind(e, sp, graded ? edges : nullptr, nullptr, &cl);
 }
 
 int gpe_sampler_cells_read(gpe_engine* e, const int64_t** d_cells, int64_t* n_cells, int64_t* first) {
     if (!e) return GPE_ERR_INVALID;
-    if (e->smp_every <= 0 || !e->smp_cells) FAIL(e, GPE_ERR_STATE, "sampler_cells_read: no cell-subset sampler bound");
+    if (!e->smp.bound() || !e->smp.cells()) FAIL(e, GPE_ERR_STATE, "sampler_cells_read: no cell-subset sampler bound");
     HIPCHK(e, hipStreamSynchronize(e->stream));
-    if (d_cells) *d_cells = e->smp_cells;
-    if (n_cells) *n_cells = e->smp_cells_n;
-    if (first) *first = e->smp_first;
+    if (d_cells) *d_cells = e->smp.cl.list;
+    if (n_cells) *n_cells = e->smp.cl.n;
+    if (first) *first = e->smp.first;
     return GPE_OK;
 }
 
 int gpe_sampler_adaptive_blocks(gpe_engine* e, int64_t* n_blocks, int64_t* n_points) {
     if (!e) return GPE_ERR_INVALID;
-    if (!e->smp_adaptive) FAIL(e, GPE_ERR_STATE, "sampler_adaptive_blocks: no adaptive sampler bound");
-    if (n_blocks) *n_blocks = e->smp_ad.B;
-    if (n_points) *n_points = e->smp_ad.N;
+    if (!e->smp.adaptive()) FAIL(e, GPE_ERR_STATE, "sampler_adaptive_blocks: no adaptive sampler bound");
+    if (n_blocks) *n_blocks = e->smp.ad.dev.B;
+    if (n_points) *n_points = e->smp.ad.dev.N;
     return GPE_OK;
 }
 
 int gpe_sampler_adaptive_state(gpe_engine* e, double* h_mass, double* mass_total, int32_t* h_count, int64_t* draw) {
     if (!e) return GPE_ERR_INVALID;
-    if (!e->smp_adaptive) FAIL(e, GPE_ERR_STATE, "sampler_adaptive_state: no adaptive sampler bound");
+    if (!e->smp.adaptive()) FAIL(e, GPE_ERR_STATE, "sampler_adaptive_state: no adaptive sampler bound");
     HIPCHK(e, hipStreamSynchronize(e->stream));
-    const size_t B = (size_t)e->smp_ad.B;
-    if (h_mass) HIPCHK(e, hipMemcpy(h_mass, e->smp_ad.mass, B * sizeof(double), hipMemcpyDeviceToHost));
-    if (mass_total) HIPCHK(e, hipMemcpy(mass_total, e->smp_ad.mass + B, sizeof(double), hipMemcpyDeviceToHost));
-    if (h_count) HIPCHK(e, hipMemcpy(h_count, e->smp_ad.count, B * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (draw) *draw = e->smp_held;
+    const size_t B = (size_t)e->smp.ad.dev.B;
+    if (h_mass) HIPCHK(e, hipMemcpy(h_mass, e->smp.ad.dev.mass, B * sizeof(double), hipMemcpyDeviceToHost));
+    if (mass_total) HIPCHK(e, hipMemcpy(mass_total, e->smp.ad.dev.mass + B, sizeof(double), hipMemcpyDeviceToHost));
+    if (h_count) HIPCHK(e, hipMemcpy(h_count, e->smp.ad.dev.count, B * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (draw) *draw = e->smp.held;
     return GPE_OK;
 }
 
 int gpe_bind_weights(gpe_engine* e, const float* d_q, double w_total) {
     if (!e) return GPE_ERR_INVALID;
     if (!d_q) {                                  // clear: the count-based N is back
-        if (e->smp_graded) FAIL(e, GPE_ERR_STATE, "bind_weights: the graded sampler owns the bound weights (gpe_bind_sampler(NULL) clears both)");
+        if (e->smp.graded()) FAIL(e, GPE_ERR_STATE, "bind_weights: the graded sampler owns the bound weights (gpe_bind_sampler(NULL) clears both)");
         HIPCHK(e, hipStreamSynchronize(e->stream));
         weights_clear(e);
         fill_phys(e);
         return GPE_OK;
     }
     if (!e->ux || e->n_pde <= 0) FAIL(e, GPE_ERR_STATE, "bind_weights before bind_points");
-    if (e->smp_every > 0) FAIL(e, GPE_ERR_STATE, "bind_weights: a sampler is bound, its rows move at the next redraw");
+    if (e->smp.bound()) FAIL(e, GPE_ERR_STATE, "bind_weights: a sampler is bound, its rows move at the next redraw");
     if (e->cfg.w_sym != 0.f) FAIL(e, GPE_ERR_INVALID, "bind_weights: the symmetry batch has no quadrature weights (w_sym != 0)");
     if (!(w_total >= 0.0) || !__builtin_isfinite(w_total)) FAIL(e, GPE_ERR_INVALID, "bind_weights: w_total = %g, need a finite value >= 0 (0: this rank's total)", w_total);
     double wl = 0.0, bad = 0.0;
@@ -2545,11 +2496,11 @@ int gpe_weights(gpe_engine* e, const float** d_q, int64_t* n, double* w_local, d
 
 int gpe_sampler_points(gpe_engine* e, const float** d_x, int64_t* n, int64_t* draw) {
     if (!e) return GPE_ERR_INVALID;
-    if (e->smp_every <= 0) FAIL(e, GPE_ERR_STATE, "sampler_points: no sampler bound");
+    if (!e->smp.bound()) FAIL(e, GPE_ERR_STATE, "sampler_points: no sampler bound");
     HIPCHK(e, hipStreamSynchronize(e->stream));
-    if (d_x) *d_x = e->smp_x;
-    if (n) *n = e->smp_n;
-    if (draw) *draw = e->smp_held;
+    if (d_x) *d_x = e->smp.x;
+    if (n) *n = e->smp.n;
+    if (draw) *draw = e->smp.held;
     return GPE_OK;
 }
 
@@ -2580,7 +2531,7 @@ static int orth_publish(gpe_engine* e) {         // orth_host -> the device copy
 int gpe_bind_orth(gpe_engine* e, int k, const float* d_psi) {
     if (!e || k < 0 || k >= GPE_MAX_ORTH) return GPE_ERR_INVALID;
     if (e->cfg.mixture) FAIL(e, GPE_ERR_STATE, "bind_orth: a mixture engine has no orthogonality term");
-    if (d_psi && e->smp_every > 0) FAIL(e, GPE_ERR_STATE, "bind_orth: a sampler is bound, an orthogonality array would go stale at its next redraw");
+    if (d_psi && e->smp.bound()) FAIL(e, GPE_ERR_STATE, "bind_orth: a sampler is bound, an orthogonality array would go stale at its next redraw");
     if (e->ost[k].on) {                          // the array (or NULL) replaces a frozen state
         HIPCHK(e, hipStreamSynchronize(e->stream));
         orth_state_free(e->ost[k]);
@@ -3217,7 +3168,7 @@ static int step_begin(gpe_engine* e, StepOpts o) {
     }
     if (rc) return rc;
     e->st.phase = 1; e->st.head_slots = slots;
-    if (e->smp_every > 0 && !o.capturing) e->smp_steps++;
+    if (e->smp.bound() && !o.capturing) e->smp.steps++;
     return seq.keep();
 }
 int gpe_step_begin(gpe_engine* e) { return e ? step_begin(e, StepOpts{}) : GPE_ERR_INVALID; }
@@ -3333,7 +3284,7 @@ int gpe_step_update(gpe_engine* e) { return e ? step_update(e) : GPE_ERR_INVALID
 int gpe_bind_target(gpe_engine* e, const float* d_target) {
     if (!e) return GPE_ERR_INVALID;
     if (e->main.n <= 0) FAIL(e, GPE_ERR_STATE, "bind_target before bind_points");
-    if (e->smp_every > 0) FAIL(e, GPE_ERR_STATE, "bind_target: a sampler is bound, a target array would go stale at its next redraw");
+    if (e->smp.bound()) FAIL(e, GPE_ERR_STATE, "bind_target: a sampler is bound, a target array would go stale at its next redraw");
     e->mse_target = d_target;
     if (!d_target) { free_batch(e->mse); return GPE_OK; }
     return setup_batch(e, e->mse, e->ux, e->n_pde, 1, 0, false, nullptr);
@@ -3341,7 +3292,7 @@ int gpe_bind_target(gpe_engine* e, const float* d_target) {
 
 int gpe_mse_begin(gpe_engine* e) {
     if (!e) return GPE_ERR_INVALID;
-    if (e->smp_every > 0) FAIL(e, GPE_ERR_STATE, "mse step while a sampler is bound: the target lives on fixed points");
+    if (e->smp.bound()) FAIL(e, GPE_ERR_STATE, "mse step while a sampler is bound: the target lives on fixed points");
     if (!e->mse_target || e->mse.n <= 0) FAIL(e, GPE_ERR_STATE, "mse step before bind_target");
     int rc;
     e->st = StepState{};
@@ -3430,7 +3381,7 @@ int gpe_lbfgs_config(gpe_engine* e, double lr, int history, double tolerance_gra
 
 static int lbfgs_refusals(gpe_engine* e, const char* who) {
     if (!e->lb.on) FAIL(e, GPE_ERR_STATE, "%s: L-BFGS is not configured (gpe_lbfgs_config)", who);
-    if (e->smp_every > 0) FAIL(e, GPE_ERR_STATE, "%s: a sampler with every > 0 is bound, the objective would change under the history", who);
+    if (e->smp.bound()) FAIL(e, GPE_ERR_STATE, "%s: a sampler with every > 0 is bound, the objective would change under the history", who);
     if (e->comm) FAIL(e, GPE_ERR_STATE, "%s: the engine has a communicator, L-BFGS is single-rank", who);
     return GPE_OK;
 }
@@ -3650,7 +3601,7 @@ int gpe_comm_unique_id(gpe_engine* e, void* out128) {
 int gpe_comm_init(gpe_engine* e, const void* id128, int rank, int world) {
     if (!e || !id128 || world < 1 || rank < 0 || rank >= world) return GPE_ERR_INVALID;
     if (e->comm) FAIL(e, GPE_ERR_STATE, "communicator already initialised");
-    if (e->smp_adaptive) FAIL(e, GPE_ERR_STATE, "comm_init: an adaptive sampler is bound, and a data-parallel allocation needs a mass exchange");
+    if (e->smp.adaptive()) FAIL(e, GPE_ERR_STATE, "comm_init: an adaptive sampler is bound, and a data-parallel allocation needs a mass exchange");
     if (world != (e->cfg.world_size > 0 ? e->cfg.world_size : 1))
         FAIL(e, GPE_ERR_INVALID, "comm world %d != gpe_config.world_size %d", world, e->cfg.world_size);
     int rc = rccl_load(e);
@@ -3785,7 +3736,7 @@ int gpe_comm_set_async(gpe_engine* e, int on) {
 
 int gpe_step_dp(gpe_engine* e) {
     if (!e) return GPE_ERR_INVALID;
-    if (e->smp_adaptive) FAIL(e, GPE_ERR_STATE, "gpe_step_dp: the adaptive sampler is single-rank");
+    if (e->smp.adaptive()) FAIL(e, GPE_ERR_STATE, "gpe_step_dp: the adaptive sampler is single-rank");
     if (!e->comm) FAIL(e, GPE_ERR_STATE, "gpe_step_dp before gpe_comm_init");
     if (e->async_grad) return step_dp_async(e);
     int rc;
@@ -3812,7 +3763,7 @@ int gpe_step_dp(gpe_engine* e) {
 }
 
 int gpe_run_dp(gpe_engine* e, int64_t n_steps) {
-    if (e && e->smp_adaptive) FAIL(e, GPE_ERR_STATE, "gpe_run_dp: the adaptive sampler is single-rank");
+    if (e && e->smp.adaptive()) FAIL(e, GPE_ERR_STATE, "gpe_run_dp: the adaptive sampler is single-rank");
     for (int64_t i = 0; i < n_steps; ++i) {
         int rc = gpe_step_dp(e);
         if (rc) return rc;
@@ -3941,12 +3892,12 @@ int gpe_run(gpe_engine* e, int64_t n_steps) {
                 // a replay must not run past a monitor step, nor across a redraw of the sampler: up to there with plain launches when
                 // fewer than a graph's steps are left to it
                 int64_t room = e->mon_every > 0 ? e->mon_every - e->mon_steps % e->mon_every : e->graph_steps;
-                if (e->smp_every > 0) room = std::min(room, e->smp_every - e->smp_steps % e->smp_every);
+                if (e->smp.bound()) room = std::min(room, e->smp.every - e->smp.steps % e->smp.every);
                 if (room >= e->graph_steps) {
-                    if (e->smp_every > 0) {       // the redraw a replay may start with is enqueued here, outside the graph
+                    if (e->smp.bound()) {         // the redraw a replay may start with is enqueued here, outside the graph
                         int rc = sampler_before_step(e, /*capturing=*/false);
                         if (rc) return rc;
-                        e->smp_steps += e->graph_steps;
+                        e->smp.steps += e->graph_steps;
                     }
                     HIPCHK(e, hipGraphLaunch(e->graph_exec, e->stream));
                     after_update(e);

@@ -1,17 +1,19 @@
-// gpe_sampler.h -- stratified collocation sets drawn on the device (include/gpe_hip.h: gpe_bind_sampler).  One uniformly placed point
-// per cell of a regular grid, from a counter-based generator, written in place into the engine's own point buffer.  Replaces the host
-// loop of tools/accuracy_nd.py:run_epochs (16 jittered numpy copies of the grid, uploaded, cycled with gpe_bind_points); the reference
-// has no counterpart: it trains on one fixed grid.
+// gpe_sampler.h -- stratified collocation sets drawn on the device (include/gpe_hip.h: gpe_bind_sampler and its kin).  One uniformly
+// placed point per cell of a tensor-product grid, from a counter-based generator, written in place into the engine's own point buffer.
+// Replaces the host loop of tools/accuracy_nd.py:run_epochs (16 jittered numpy copies of the grid, uploaded, cycled with
+// gpe_bind_points); the reference has no counterpart: it trains on one fixed grid.
 //
-// The draw is a pure function of (seed, draw, cell) -- gpe_pinn/sampler.py restates it in numpy and the two agree bit for bit:
-//   words  Philox4x32-10, counter (cell lo, cell hi, draw lo, draw hi), key (seed lo, seed hi); output word k serves axis k
-//   u      float(r >> 8) * 2^-24                  exact: 24 bits
-//   t      float(i_k) + u                         one rounded fp32 add (i_k < 2^24, checked at the bind)
-//   x      lo[k] + t * h[k]                       one rounded multiply, one rounded add, never an fma: smp_mul_then_add below
-//   clip   x < clip_lo ? clip_lo : x, then x > clip_hi ? clip_hi : x      (comparisons, not fmin/fmax: no choice between +0 and -0)
-// Cells are numbered row-major, last axis fastest; row j of the buffer is cell first_cell + j, so contiguous blocks of cells held by
-// different ranks are, together, the set one rank would hold.
-// One thread per point, one Philox call per thread, plain vector stores (global_store_dword) only.
+// Every kernel here is one thread per row, one Philox call per thread, plain vector stores (global_store_dword) only.  They differ in
+// which cell a row is and in how an axis places its point; the arithmetic of a row is stated once, at the pieces below, and
+// gpe_pinn/sampler.py restates it in numpy, bit for bit:
+//   kernel                        row j is cell                 axis step    sampler.py
+//   k_sampler_draw                first_cell + j                uniform      stratified_points
+//   k_sampler_draw_graded         first_cell + j                graded       graded_points / graded_weights
+//   k_sampler_draw_cells          cells[first + j]              uniform      cells_points  (= stratified_points(...)[cells])
+//   k_sampler_draw_graded_cells   cells[first + j]              graded       cells_points / cells_weights
+//   k_sampler_draw_adaptive       block b, local index l        graded       adaptive_points / adaptive_weights  (further down)
+// Cells are numbered row-major, last axis fastest, so contiguous blocks of cells (or of a list) held by different ranks are, together,
+// the set one rank would hold.
 #pragma once
 #include "gpe_common.h"
 
@@ -47,124 +49,140 @@ GPE_DEV void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, u
     out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
 }
 
-// x [n][dim] <- draw `draw` of cells [first_cell, first_cell + n);  xs (NULL: none) [2n][dim] <- [x ; -x], the symmetry batch
-__global__ __launch_bounds__(SMP_THREADS) void k_sampler_draw(SamplerGrid g, int64_t first_cell, int64_t n, uint64_t draw,
-                                                              float* __restrict__ x, float* __restrict__ xs) {
-    const int64_t j = (int64_t)blockIdx.x * SMP_THREADS + threadIdx.x;
-    if (j >= n) return;
-    const uint64_t cell = (uint64_t)(first_cell + j);
-    uint32_t r[4];
-    philox4x32_10((uint32_t)cell, (uint32_t)(cell >> 32), (uint32_t)draw, (uint32_t)(draw >> 32), g.key0, g.key1, r);
-    uint64_t rest = cell;
-    float v[3];
-#pragma unroll
-    for (int k = 2; k >= 0; --k) {
-        if (k >= g.dim) continue;
-        const uint64_t s = (uint64_t)g.shape[k];
-        const uint64_t q = rest / s;
-        const float ik = (float)(uint32_t)(rest - q * s);
-        rest = q;
-        const float u = (float)(r[k] >> 8) * 0x1p-24f;
-        const float t = ik + u;
-        float xv = smp_mul_then_add(g.lo[k], t, g.h[k]);
-        xv = xv < g.clip_lo[k] ? g.clip_lo[k] : xv;
-        xv = xv > g.clip_hi[k] ? g.clip_hi[k] : xv;
-        v[k] = xv;
-    }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        if (k >= g.dim) continue;
-        x[j * g.dim + k] = v[k];
-        if (xs) { xs[j * g.dim + k] = v[k]; xs[(n + j) * g.dim + k] = -v[k]; }
-    }
+// ---- the pieces of a row ------------------------------------------------------------------------------------------------------------
+// words: Philox4x32-10, counter (c lo, c hi, draw lo, draw hi), key (seed lo, seed hi); output word k serves axis k.  The grid kernels
+// count by the cell (64 bits); the adaptive kernel by (block, local index), one word each.
+GPE_DEV void smp_words(const SamplerGrid& g, uint32_t c0, uint32_t c1, uint64_t draw, uint32_t (&r)[4]) {
+    philox4x32_10(c0, c1, (uint32_t)draw, (uint32_t)(draw >> 32), g.key0, g.key1, r);
 }
 
-// ---- graded grids (gpe_bind_sampler_graded) -------------------------------------------------------------------------------------------
-// The same draw on a tensor-product grid with caller-given, non-uniform cell edges: axis k has shape[k] cells, cell i spans
-// [edges_k[i], edges_k[i + 1]].  Same Philox call, counter / key layout, word per axis and cell numbering as k_sampler_draw; per axis
-//   a, b   edges_k[i], edges_k[i + 1]
-//   w      b - a                                  one rounded fp32 subtraction: the cell's width
-//   x      a + u * w                              smp_mul_then_add: one rounded multiply, one rounded add, never an fma
-//   clip   as above, by comparisons
-// and the point's quadrature weight is its cell's volume q = w_0, then q * w_1, then * w_2: rounded fp32 multiplies in axis order.  The
-// weights do not depend on the draw: qw != NULL (the bind) writes them, the redraws pass NULL.  g.lo / g.h are not read.
-// gpe_pinn/sampler.py:graded_points / graded_weights restate both in numpy, bit for bit.  Plain vector stores only.
-__global__ __launch_bounds__(SMP_THREADS) void k_sampler_draw_graded(SamplerGrid g, const float* __restrict__ e0, const float* __restrict__ e1,
-                                                                     const float* __restrict__ e2, int64_t first_cell, int64_t n, uint64_t draw,
-                                                                     float* __restrict__ x, float* __restrict__ qw) {
-    const int64_t j = (int64_t)blockIdx.x * SMP_THREADS + threadIdx.x;
-    if (j >= n) return;
-    const uint64_t cell = (uint64_t)(first_cell + j);
-    uint32_t r[4];
-    philox4x32_10((uint32_t)cell, (uint32_t)(cell >> 32), (uint32_t)draw, (uint32_t)(draw >> 32), g.key0, g.key1, r);
-    uint64_t rest = cell;
-    float v[3], w[3];
-#pragma unroll
-    for (int k = 2; k >= 0; --k) {
-        if (k >= g.dim) continue;
-        const float* __restrict__ ed = k == 0 ? e0 : (k == 1 ? e1 : e2);
-        const uint64_t s = (uint64_t)g.shape[k];
-        const uint64_t q = rest / s;
-        const uint32_t ik = (uint32_t)(rest - q * s);         // < shape[k]: edges_k holds shape[k] + 1 entries
-        rest = q;
-        const float a = ed[ik], b = ed[ik + 1];
-        const float u = (float)(r[k] >> 8) * 0x1p-24f;
-        w[k] = b - a;
-        float xv = smp_mul_then_add(a, u, w[k]);
-        xv = xv < g.clip_lo[k] ? g.clip_lo[k] : xv;
-        xv = xv > g.clip_hi[k] ? g.clip_hi[k] : xv;
-        v[k] = xv;
-    }
+// row-major split, last axis fastest: takes axis k's index off what is left of the cell.  64-bit divisions (a rank's cells fit int64, a
+// grid may hold more than 2^32); the index is < shape[k] <= 2^24
+GPE_DEV uint32_t smp_split(uint64_t& rest, int64_t shape_k) {
+    const uint64_t s = (uint64_t)shape_k;
+    const uint64_t q = rest / s;
+    const uint32_t ik = (uint32_t)(rest - q * s);
+    rest = q;
+    return ik;
+}
+
+// u = float(word >> 8) * 2^-24: exact, 24 bits, in [0, 1)
+GPE_DEV float smp_unit(uint32_t word) { return (float)(word >> 8) * 0x1p-24f; }
+
+// by comparisons, not fmin / fmax: no choice between +0 and -0
+GPE_DEV float smp_clip(const SamplerGrid& g, int k, float xv) {
+    xv = xv < g.clip_lo[k] ? g.clip_lo[k] : xv;
+    xv = xv > g.clip_hi[k] ? g.clip_hi[k] : xv;
+    return xv;
+}
+
+// uniform axis: t = float(i_k) + u, one rounded fp32 add (i_k < 2^24, checked at the bind); x = lo[k] + t * h[k], one rounded multiply,
+// one rounded add, never an fma; the clip
+GPE_DEV float smp_axis_uniform(const SamplerGrid& g, int k, uint32_t ik, uint32_t word) {
+    const float u = smp_unit(word);
+    const float t = (float)ik + u;
+    return smp_clip(g, k, smp_mul_then_add(g.lo[k], t, g.h[k]));
+}
+
+// graded axis: cell i_k spans [a, b] = [ed[i_k], ed[i_k + 1]] of the caller's edges (shape[k] + 1 entries, so the reads stay inside);
+// w = b - a, one rounded fp32 subtraction: the cell's width; x = a + u * w, one rounded multiply, one rounded add, never an fma; the
+// clip.  g.lo / g.h are not read.
+GPE_DEV float smp_axis_graded(const SamplerGrid& g, int k, const float* __restrict__ ed, uint32_t ik, uint32_t word, float& w) {
+    const float a = ed[ik], b = ed[ik + 1];
+    const float u = smp_unit(word);
+    w = b - a;
+    return smp_clip(g, k, smp_mul_then_add(a, u, w));
+}
+
+// the cell's volume, a graded row's quadrature weight: w_0, then * w_1, then * w_2 -- rounded fp32 multiplies in axis order
+GPE_DEV float smp_volume(const SamplerGrid& g, const float (&w)[3]) {
     float qv = w[0];
 #pragma unroll
     for (int k = 1; k < 3; ++k) {
         if (k >= g.dim) continue;
         qv = qv * w[k];
     }
+    return qv;
+}
+
+// x [n][dim] row j <- v
+GPE_DEV void smp_store(const SamplerGrid& g, const float (&v)[3], int64_t j, float* __restrict__ x) {
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         if (k >= g.dim) continue;
         x[j * g.dim + k] = v[k];
     }
-    if (qw) qw[j] = qv;
 }
 
-// ---- a subset of the cells (gpe_sampler_cells) ----------------------------------------------------------------------------------------
-// The same two draws with one indirection: row j of the buffer is cell cells[first + j] of the grid instead of cell first_cell + j.
-// `cells` is the engine-owned copy of the caller's strictly ascending list (a disk, a ball, any mask: gpe_pinn/sampler.py ball_cells /
-// mask_cells); the bind checked every entry against [0, prod shape), so the per-axis index stays below shape[k] and the edge reads stay
-// inside their arrays.  Everything behind the load is k_sampler_draw / k_sampler_draw_graded statement for statement, so row j holds the
-// bits row cells[first + j] of the full grid's set holds: sampler.py cells_points is stratified_points(...)[cells] by construction.
-// One thread per row; the 8-byte index loads of a wave are consecutive (one coalesced global_load_dwordx2 each); plain vector stores only.
-__global__ __launch_bounds__(SMP_THREADS) void k_sampler_draw_cells(SamplerGrid g, const int64_t* __restrict__ cells, int64_t first, int64_t n,
-                                                                    uint64_t draw, float* __restrict__ x, float* __restrict__ xs) {
-    const int64_t j = (int64_t)blockIdx.x * SMP_THREADS + threadIdx.x;
-    if (j >= n) return;
-    const uint64_t cell = (uint64_t)cells[first + j];
-    uint32_t r[4];
-    philox4x32_10((uint32_t)cell, (uint32_t)(cell >> 32), (uint32_t)draw, (uint32_t)(draw >> 32), g.key0, g.key1, r);
-    uint64_t rest = cell;
-    float v[3];
-#pragma unroll
-    for (int k = 2; k >= 0; --k) {
-        if (k >= g.dim) continue;
-        const uint64_t s = (uint64_t)g.shape[k];
-        const uint64_t q = rest / s;
-        const float ik = (float)(uint32_t)(rest - q * s);
-        rest = q;
-        const float u = (float)(r[k] >> 8) * 0x1p-24f;
-        const float t = ik + u;
-        float xv = smp_mul_then_add(g.lo[k], t, g.h[k]);
-        xv = xv < g.clip_lo[k] ? g.clip_lo[k] : xv;
-        xv = xv > g.clip_hi[k] ? g.clip_hi[k] : xv;
-        v[k] = xv;
-    }
+// ... and, for the two uniform forms, xs (NULL: none) [2n][dim] rows j and n + j <- v and -v: the symmetry batch [x ; -x]
+GPE_DEV void smp_store_sym(const SamplerGrid& g, const float (&v)[3], int64_t j, int64_t n, float* __restrict__ x, float* __restrict__ xs) {
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         if (k >= g.dim) continue;
         x[j * g.dim + k] = v[k];
         if (xs) { xs[j * g.dim + k] = v[k]; xs[(n + j) * g.dim + k] = -v[k]; }
     }
+}
+
+// ---- the two rows of the grid kernels ---------------------------------------------------------------------------------------------------
+// row j of x (and of [x ; -x]) <- draw `draw` of cell `cell` of the uniform grid
+GPE_DEV void smp_row_uniform(const SamplerGrid& g, uint64_t cell, int64_t j, int64_t n, uint64_t draw, float* __restrict__ x,
+                             float* __restrict__ xs) {
+    uint32_t r[4];
+    smp_words(g, (uint32_t)cell, (uint32_t)(cell >> 32), draw, r);
+    uint64_t rest = cell;
+    float v[3];
+#pragma unroll
+    for (int k = 2; k >= 0; --k) {
+        if (k >= g.dim) continue;
+        v[k] = smp_axis_uniform(g, k, smp_split(rest, g.shape[k]), r[k]);
+    }
+    smp_store_sym(g, v, j, n, x, xs);
+}
+
+// ... of the graded grid; qw (NULL: not wanted) [n] row j <- the cell's volume.  The weights do not depend on the draw: the bind writes
+// them, the redraws pass NULL.
+GPE_DEV void smp_row_graded(const SamplerGrid& g, const float* __restrict__ e0, const float* __restrict__ e1, const float* __restrict__ e2,
+                            uint64_t cell, int64_t j, uint64_t draw, float* __restrict__ x, float* __restrict__ qw) {
+    uint32_t r[4];
+    smp_words(g, (uint32_t)cell, (uint32_t)(cell >> 32), draw, r);
+    uint64_t rest = cell;
+    float v[3], w[3];
+#pragma unroll
+    for (int k = 2; k >= 0; --k) {
+        if (k >= g.dim) continue;
+        v[k] = smp_axis_graded(g, k, k == 0 ? e0 : (k == 1 ? e1 : e2), smp_split(rest, g.shape[k]), r[k], w[k]);
+    }
+    smp_store(g, v, j, x);
+    if (qw) qw[j] = smp_volume(g, w);
+}
+
+// ---- the grid kernels: which cell is row j ------------------------------------------------------------------------------------------
+// cells [first_cell, first_cell + n) of the grid ...
+__global__ __launch_bounds__(SMP_THREADS) void k_sampler_draw(SamplerGrid g, int64_t first_cell, int64_t n, uint64_t draw,
+                                                              float* __restrict__ x, float* __restrict__ xs) {
+    const int64_t j = (int64_t)blockIdx.x * SMP_THREADS + threadIdx.x;
+    if (j >= n) return;
+    smp_row_uniform(g, (uint64_t)(first_cell + j), j, n, draw, x, xs);
+}
+
+__global__ __launch_bounds__(SMP_THREADS) void k_sampler_draw_graded(SamplerGrid g, const float* __restrict__ e0, const float* __restrict__ e1,
+                                                                     const float* __restrict__ e2, int64_t first_cell, int64_t n, uint64_t draw,
+                                                                     float* __restrict__ x, float* __restrict__ qw) {
+    const int64_t j = (int64_t)blockIdx.x * SMP_THREADS + threadIdx.x;
+    if (j >= n) return;
+    smp_row_graded(g, e0, e1, e2, (uint64_t)(first_cell + j), j, draw, x, qw);
+}
+
+// ... or rows [first, first + n) of `cells` (gpe_sampler_cells), the engine-owned copy of the caller's strictly ascending list (a disk,
+// a ball, any mask: gpe_pinn/sampler.py ball_cells / mask_cells).  The bind checked every entry against [0, prod shape), so the per-axis
+// index stays below shape[k] and the edge reads stay inside their arrays.  The 8-byte index loads of a wave are consecutive (one
+// coalesced global_load_dwordx2 each).
+__global__ __launch_bounds__(SMP_THREADS) void k_sampler_draw_cells(SamplerGrid g, const int64_t* __restrict__ cells, int64_t first, int64_t n,
+                                                                    uint64_t draw, float* __restrict__ x, float* __restrict__ xs) {
+    const int64_t j = (int64_t)blockIdx.x * SMP_THREADS + threadIdx.x;
+    if (j >= n) return;
+    smp_row_uniform(g, (uint64_t)cells[first + j], j, n, draw, x, xs);
 }
 
 __global__ __launch_bounds__(SMP_THREADS) void k_sampler_draw_graded_cells(SamplerGrid g, const float* __restrict__ e0, const float* __restrict__ e1,
@@ -173,39 +191,7 @@ __global__ __launch_bounds__(SMP_THREADS) void k_sampler_draw_graded_cells(Sampl
                                                                            float* __restrict__ qw) {
     const int64_t j = (int64_t)blockIdx.x * SMP_THREADS + threadIdx.x;
     if (j >= n) return;
-    const uint64_t cell = (uint64_t)cells[first + j];
-    uint32_t r[4];
-    philox4x32_10((uint32_t)cell, (uint32_t)(cell >> 32), (uint32_t)draw, (uint32_t)(draw >> 32), g.key0, g.key1, r);
-    uint64_t rest = cell;
-    float v[3], w[3];
-#pragma unroll
-    for (int k = 2; k >= 0; --k) {
-        if (k >= g.dim) continue;
-        const float* __restrict__ ed = k == 0 ? e0 : (k == 1 ? e1 : e2);
-        const uint64_t s = (uint64_t)g.shape[k];
-        const uint64_t q = rest / s;
-        const uint32_t ik = (uint32_t)(rest - q * s);         // < shape[k]: edges_k holds shape[k] + 1 entries
-        rest = q;
-        const float a = ed[ik], b = ed[ik + 1];
-        const float u = (float)(r[k] >> 8) * 0x1p-24f;
-        w[k] = b - a;
-        float xv = smp_mul_then_add(a, u, w[k]);
-        xv = xv < g.clip_lo[k] ? g.clip_lo[k] : xv;
-        xv = xv > g.clip_hi[k] ? g.clip_hi[k] : xv;
-        v[k] = xv;
-    }
-    float qv = w[0];
-#pragma unroll
-    for (int k = 1; k < 3; ++k) {
-        if (k >= g.dim) continue;
-        qv = qv * w[k];
-    }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        if (k >= g.dim) continue;
-        x[j * g.dim + k] = v[k];
-    }
-    if (qw) qw[j] = qv;
+    smp_row_graded(g, e0, e1, e2, (uint64_t)cells[first + j], j, draw, x, qw);
 }
 
 // ---- residual-adaptive allocation (gpe_sampler_adaptive) -------------------------------------------------------------------------------
@@ -353,8 +339,8 @@ __global__ __launch_bounds__(SMP_AD_THREADS) void k_adaptive_alloc(AdaptiveDev a
 }
 
 // x [N][dim], qw [N] <- draw `draw`.  Row j: block b = upper_bound(off, j) - 1 (offsets staged in LDS when B + 1 <= SMP_OFF_LDS), local
-// index l = j - off[b]; Philox counter (b, l, draw lo, draw hi), key (seed lo, seed hi), output word k for axis k; per axis u, w, x and
-// the clip exactly as k_sampler_draw_graded; q = float(double(v_b) / double(n_b)): one IEEE fp64 division, one conversion.
+// index l = j - off[b]; the words are counted by (b, l) and b splits in 32 bits (B <= 2^22); per axis smp_axis_graded, the step of the
+// graded grid kernels; q = float(double(v_b) / double(n_b)): one IEEE fp64 division, one conversion.
 __global__ __launch_bounds__(SMP_THREADS) void k_sampler_draw_adaptive(SamplerGrid g, const float* __restrict__ e0, const float* __restrict__ e1,
                                                                        const float* __restrict__ e2, AdaptiveDev a, uint64_t draw,
                                                                        float* __restrict__ x, float* __restrict__ qw) {
@@ -374,29 +360,19 @@ __global__ __launch_bounds__(SMP_THREADS) void k_sampler_draw_adaptive(SamplerGr
     }
     const uint32_t b = (uint32_t)lo, l = (uint32_t)(j - off[lo]);
     uint32_t r[4];
-    philox4x32_10(b, l, (uint32_t)draw, (uint32_t)(draw >> 32), g.key0, g.key1, r);
+    smp_words(g, b, l, draw, r);
     uint32_t rest = b;
     float v[3];
 #pragma unroll
     for (int k = 2; k >= 0; --k) {
         if (k >= g.dim) continue;
-        const float* __restrict__ ed = k == 0 ? e0 : (k == 1 ? e1 : e2);
         const uint32_t s = (uint32_t)g.shape[k];
         const uint32_t q = rest / s;
-        const uint32_t ik = rest - q * s;                    // < shape[k]: edges_k holds shape[k] + 1 entries
+        const uint32_t ik = rest - q * s;                    // < shape[k]
         rest = q;
-        const float ea = ed[ik], eb = ed[ik + 1];
-        const float u = (float)(r[k] >> 8) * 0x1p-24f;
-        const float w = eb - ea;
-        float xv = smp_mul_then_add(ea, u, w);
-        xv = xv < g.clip_lo[k] ? g.clip_lo[k] : xv;
-        xv = xv > g.clip_hi[k] ? g.clip_hi[k] : xv;
-        v[k] = xv;
+        float w;
+        v[k] = smp_axis_graded(g, k, k == 0 ? e0 : (k == 1 ? e1 : e2), ik, r[k], w);
     }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        if (k >= g.dim) continue;
-        x[j * g.dim + k] = v[k];
-    }
+    smp_store(g, v, j, x);
     qw[j] = (float)((double)a.vol[b] / (double)a.count[b]);
 }

@@ -340,30 +340,48 @@ class Engine:
                                            C.c_void_p(Vt.data_ptr()) if Vt is not None else None))
         self.n_local = int(x.shape[0])
 
+    def _sampler_spec(self, shape, edges, lo, hi, clip, seed, first, n, draw0, every):
+        """(gpe_sampler_spec, [edge pointer or None] * 3) of the four sampler binds.  shape None: the grid is the edges' (shape[k] =
+        len(edges[k]) - 1, lo / hi / default clip their end values); else lo / hi / shape describe it and edges, if any, must fit it.
+        n None: the cells from `first` to the grid's last.  What the engine cannot honour it refuses itself (GPE_ERR_INVALID): nothing
+        else is judged here.  (Each pointer keeps its numpy array alive.)"""
+        from . import sampler
+        per_axis_clip = lambda d: (sampler._per_axis(clip[0], d, "clip[0]"), sampler._per_axis(clip[1], d, "clip[1]"))
+        if shape is None:                     # (the order of the checks is the order of the ValueErrors: edges, then clip ...)
+            ed = sampler._edges(edges)
+            d = len(ed)
+            shp = [a.size - 1 for a in ed]
+            lo32, hi32 = [a[0] for a in ed], [a[-1] for a in ed]
+            clo, chi = (lo32, hi32) if clip is None else per_axis_clip(d)
+        else:                                 # (... here shape, lo, hi, clip, then edges and their fit)
+            shp = [int(v) for v in np.atleast_1d(np.asarray(shape)).ravel()]
+            d = len(shp)
+            if not 1 <= d <= capi.GPE_MAX_DIM:
+                raise ValueError(f"shape: 1 to {capi.GPE_MAX_DIM} axes")
+            lo32, hi32 = sampler._per_axis(lo, d, "lo"), sampler._per_axis(hi, d, "hi")
+            clo, chi = (lo32, hi32) if clip is None else per_axis_clip(d)
+            ed = None if edges is None else sampler._edges(edges)
+            if ed is not None and [a.size - 1 for a in ed] != shp:
+                raise ValueError("edges: shape[k] + 1 values per axis")
+        sp = capi.gpe_sampler_spec()
+        total = 1
+        for k in range(d):
+            sp.shape[k] = shp[k]
+            sp.lo[k], sp.hi[k], sp.clip_lo[k], sp.clip_hi[k] = float(lo32[k]), float(hi32[k]), float(clo[k]), float(chi[k])
+            total *= shp[k]
+        sp.seed = int(seed) & (2 ** 64 - 1)
+        sp.first_cell = int(first)
+        sp.n_local = total - int(first) if n is None else int(n)
+        sp.draw0, sp.every = int(draw0), int(every)
+        return sp, [ed[k].ctypes.data_as(C.c_void_p) if ed is not None and k < d else None for k in range(3)]
+
     def bind_sampler(self, lo, hi, shape, every: int, seed: int = 0, first_cell: int = 0, n=None, draw0: int = 0, clip=None):
         """Device-side stratified sampler: the engine owns the collocation batch -- one uniformly placed point per cell of the grid of
         `shape` cells over [lo, hi], cells first_cell .. first_cell + n - 1 (n None: all of them) -- and redraws it in place every
         `every` steps on its own stream (no host synchronisation, a captured graph stays valid).  clip = (clip_lo, clip_hi) keeps the
         points inside a box narrower than the cells (default (lo, hi)).  sampler.stratified_points(lo, hi, shape, seed, draw, ...)
         rebuilds any set on the CPU, bit for bit."""
-        from . import sampler
-        shp = [int(v) for v in np.atleast_1d(np.asarray(shape)).ravel()]
-        d = len(shp)
-        if not 1 <= d <= capi.GPE_MAX_DIM:
-            raise ValueError(f"shape: 1 to {capi.GPE_MAX_DIM} axes")
-        lo32, hi32 = sampler._per_axis(lo, d, "lo"), sampler._per_axis(hi, d, "hi")
-        clo, chi = (lo32, hi32) if clip is None else (sampler._per_axis(clip[0], d, "clip[0]"), sampler._per_axis(clip[1], d, "clip[1]"))
-        sp = capi.gpe_sampler_spec()          # what the engine cannot honour it refuses itself (GPE_ERR_INVALID): nothing is judged here
-        for k in range(d):
-            sp.shape[k] = shp[k]
-            sp.lo[k], sp.hi[k], sp.clip_lo[k], sp.clip_hi[k] = float(lo32[k]), float(hi32[k]), float(clo[k]), float(chi[k])
-        total = 1
-        for v in shp:
-            total *= v
-        sp.seed = int(seed) & (2 ** 64 - 1)
-        sp.first_cell = int(first_cell)
-        sp.n_local = total - int(first_cell) if n is None else int(n)
-        sp.draw0, sp.every = int(draw0), int(every)
+        sp, _ = self._sampler_spec(shape, None, lo, hi, clip, seed, first_cell, n, draw0, every)
         self._chk(self.lib.gpe_bind_sampler(self._h, C.byref(sp)))
         self._keep["x"], self._keep["V"] = None, None
         self.n_local = int(sp.n_local)
@@ -411,22 +429,7 @@ class Engine:
         array of cell edges per axis (shape[k] = len(edges[k]) - 1) -- with every point weighted by its cell's volume (bind_weights is
         implied; total = the whole grid's volume, so set cfg.dx = 1).  sampler.graded_points / graded_weights / graded_total rebuild
         points, weights and W on the CPU, bit for bit; sampler.sinh_edges makes centre-refined edges."""
-        from . import sampler
-        ed = sampler._edges(edges)
-        d = len(ed)
-        sp = capi.gpe_sampler_spec()          # what the engine cannot honour it refuses itself (GPE_ERR_INVALID): nothing is judged here
-        clo = [float(a[0]) for a in ed] if clip is None else [float(v) for v in sampler._per_axis(clip[0], d, "clip[0]")]
-        chi = [float(a[-1]) for a in ed] if clip is None else [float(v) for v in sampler._per_axis(clip[1], d, "clip[1]")]
-        total = 1
-        for k in range(d):
-            sp.shape[k] = ed[k].size - 1
-            sp.lo[k], sp.hi[k], sp.clip_lo[k], sp.clip_hi[k] = float(ed[k][0]), float(ed[k][-1]), clo[k], chi[k]
-            total *= ed[k].size - 1
-        sp.seed = int(seed) & (2 ** 64 - 1)
-        sp.first_cell = int(first_cell)
-        sp.n_local = total - int(first_cell) if n is None else int(n)
-        sp.draw0, sp.every = int(draw0), int(every)
-        ptrs = [ed[k].ctypes.data_as(C.c_void_p) if k < d else None for k in range(3)]
+        sp, ptrs = self._sampler_spec(None, edges, None, None, clip, seed, first_cell, n, draw0, every)
         self._chk(self.lib.gpe_bind_sampler_graded(self._h, C.byref(sp), *ptrs))
         self._keep["x"], self._keep["V"] = None, None
         self._keep.pop("q", None)
@@ -441,20 +444,7 @@ class Engine:
         volume.  sampler.adaptive_counts / adaptive_points / adaptive_weights rebuild counts, points and weights on the CPU, bit for
         bit, from adaptive_state().  Single-rank."""
         from . import sampler
-        ed = sampler._edges(edges)
-        d = len(ed)
-        sp = capi.gpe_sampler_spec()          # what the engine cannot honour it refuses itself (GPE_ERR_INVALID): nothing is judged here
-        clo = [float(a[0]) for a in ed] if clip is None else [float(v) for v in sampler._per_axis(clip[0], d, "clip[0]")]
-        chi = [float(a[-1]) for a in ed] if clip is None else [float(v) for v in sampler._per_axis(clip[1], d, "clip[1]")]
-        total = 1
-        for k in range(d):
-            sp.shape[k] = ed[k].size - 1
-            sp.lo[k], sp.hi[k], sp.clip_lo[k], sp.clip_hi[k] = float(ed[k][0]), float(ed[k][-1]), clo[k], chi[k]
-            total *= ed[k].size - 1
-        sp.seed = int(seed) & (2 ** 64 - 1)
-        sp.first_cell, sp.n_local = 0, total
-        sp.draw0, sp.every = int(draw0), int(every)
-        ptrs = [ed[k].ctypes.data_as(C.c_void_p) if k < d else None for k in range(3)]
+        sp, ptrs = self._sampler_spec(None, edges, None, None, clip, seed, 0, None, draw0, every)
         self._chk(self.lib.gpe_sampler_adaptive(self._h, C.byref(sp), *ptrs, int(n_points), int(n_min),
                                                 sampler.uniform_per_1024(uniform_share)))
         self._keep["x"], self._keep["V"] = None, None
@@ -469,28 +459,10 @@ class Engine:
         Uniform: set cfg.dx to the cell volume and n_global to len(cells); graded: the rows carry their cell volumes as weights with
         total = sampler.cells_total(cells, edges), so set cfg.dx = 1.  sampler.cells_points / cells_weights rebuild points and weights
         on the CPU, bit for bit."""
-        from . import sampler
         c = np.ascontiguousarray(np.asarray(cells).ravel(), dtype=np.int64)
         if c.size == 0:
             raise ValueError("bind_sampler_cells: the list of cells is empty")
-        shp = [int(v) for v in np.atleast_1d(np.asarray(shape)).ravel()]
-        d = len(shp)
-        if not 1 <= d <= capi.GPE_MAX_DIM:
-            raise ValueError(f"shape: 1 to {capi.GPE_MAX_DIM} axes")
-        lo32, hi32 = sampler._per_axis(lo, d, "lo"), sampler._per_axis(hi, d, "hi")
-        clo, chi = (lo32, hi32) if clip is None else (sampler._per_axis(clip[0], d, "clip[0]"), sampler._per_axis(clip[1], d, "clip[1]"))
-        ed = None if edges is None else sampler._edges(edges)
-        if ed is not None and [a.size - 1 for a in ed] != shp:
-            raise ValueError("edges: shape[k] + 1 values per axis")
-        sp = capi.gpe_sampler_spec()          # what the engine cannot honour it refuses itself (GPE_ERR_INVALID): nothing else is judged here
-        for k in range(d):
-            sp.shape[k] = shp[k]
-            sp.lo[k], sp.hi[k], sp.clip_lo[k], sp.clip_hi[k] = float(lo32[k]), float(hi32[k]), float(clo[k]), float(chi[k])
-        sp.seed = int(seed) & (2 ** 64 - 1)
-        sp.first_cell = int(first)
-        sp.n_local = c.size - int(first) if n_local is None else int(n_local)
-        sp.draw0, sp.every = int(draw0), int(every)
-        ptrs = [ed[k].ctypes.data_as(C.c_void_p) if ed is not None and k < d else None for k in range(3)]
+        sp, ptrs = self._sampler_spec(shape, edges, lo, hi, clip, seed, first, c.size - int(first) if n_local is None else n_local, draw0, every)
         self._chk(self.lib.gpe_sampler_cells(self._h, C.byref(sp), c.ctypes.data_as(C.c_void_p), c.size, *ptrs))
         self._keep["x"], self._keep["V"] = None, None
         self._keep.pop("q", None)

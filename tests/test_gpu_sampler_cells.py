@@ -120,6 +120,70 @@ def test_device_set_equals_the_restatement_bit_for_bit(d, graded):
     eng.close()
 
 
+# ---- 1b. each of the four grid kernels x dim x a ragged row count x a non-zero first row, at the bind and behind a redraw -------------
+# 4 099 rows: 16 full workgroups of 256 and a ragged tail; 17: one ragged workgroup; 1: the degenerate set.  The bind's launch writes the
+# graded weights (qw given), the redraw's does not (qw NULL).  "+sym": the two uniform forms with w_sym != 0, whose launch writes the
+# [x ; -x] batch as well (xs given).  The engine does not expose that batch; the step's sym term reads nothing else, so it is held to the
+# oracle on [x ; -x] of the restated set, with the bar of test_the_symmetry_batch_follows_the_redraw (UNIFORM_TOLS).
+MATRIX_SHAPE = {1: (5003,), 2: (17, 301), 3: (36, 13, 11)}                  # last axes no powers of two; 6 / 7 of the cells >= 29 + 4 099
+MATRIX_KERNELS = ["k_sampler_draw", "k_sampler_draw_graded", "k_sampler_draw_cells", "k_sampler_draw_graded_cells", "k_sampler_draw+sym",
+                  "k_sampler_draw_cells+sym"]
+
+
+@pytest.mark.parametrize("N", [1, 17, 4099])
+@pytest.mark.parametrize("d", [1, 2, 3])
+@pytest.mark.parametrize("kernel", MATRIX_KERNELS)
+def test_every_grid_kernel_holds_the_restatement_at_the_bind_and_behind_a_redraw(kernel, d, N):
+    graded, listed, sym = "graded" in kernel, "cells" in kernel, kernel.endswith("+sym")
+    half, shape = (3.0, 2.5, 2.0)[:d], MATRIX_SHAPE[d]
+    lo, hi = tuple(-h for h in half), half
+    ed = [S.sinh_edges(h, s, 1.5) for h, s in zip(half, shape)]
+    total = int(np.prod(shape))
+    cells = np.flatnonzero(np.arange(total) % 7 != 3).astype(np.int64)         # a list with gaps
+    first, seed, draw0 = 29, SEED, 2 ** 33 + 1
+    assert first + N <= cells.size
+    eng, pb, _ = small_engine(d, dx=1.0, **(dict(w_sym=5.0) if sym else {}))
+    if listed:
+        eng.bind_sampler_cells(cells, lo, hi, shape, every=1, seed=seed, draw0=draw0, edges=ed if graded else None, first=first, n_local=N)
+        rows = cells[first:first + N]
+    else:
+        if graded:
+            eng.bind_sampler_graded(ed, every=1, seed=seed, draw0=draw0, first_cell=first, n=N)
+        else:
+            eng.bind_sampler(lo, hi, shape, every=1, seed=seed, draw0=draw0, first_cell=first, n=N)
+        rows = np.arange(first, first + N, dtype=np.int64)
+    q = S.cells_weights(rows, ed) if graded else None
+
+    def held(step):
+        """the buffer holds the restated set of draw0 + step (and the graded weights); -> that set"""
+        pts, draw = eng.sampler_points()
+        assert draw == draw0 + step and tuple(pts.shape) == (N, d)
+        if listed:
+            want = S.cells_points(rows, lo, hi, shape, seed, draw, edges=ed if graded else None)
+        elif graded:
+            want = S.graded_points(ed, seed, draw, first_cell=first, n=N)
+        else:
+            want = S.stratified_points(lo, hi, shape, seed, draw, first_cell=first, n=N)
+        assert same(pts, want), (kernel, d, N, step)
+        if graded:
+            assert same(eng.weights()["q"], q), (kernel, d, N, step)
+        return want
+
+    ran = []                                             # (parameters, scalars, set) of the step on the bind's draw and of the one behind the redraw
+    flat0, x0 = eng.get_params(), held(0)
+    ran.append((flat0, eng.step(), x0))
+    flat1 = eng.get_params()
+    sc1 = eng.step()                                     # every = 1: starts with the redraw
+    ran.append((flat1, sc1, held(1)))
+    if sym:
+        for step, (flat, sc, x) in enumerate(ran):
+            osc, _, _ = go.full_loss_and_grad(pb, flat.astype(np.float64), x.astype(np.float64))
+            tol = dict(UNIFORM_TOLS)["sym"]
+            print(f"[sym] {kernel} d={d} N={N} step {step}: sym {sc['sym']!r} oracle {osc['sym']!r} rel {abs(sc['sym'] - osc['sym']) / max(abs(osc['sym']), 1e-6):.2e}")
+            assert osc["sym"] > 0 and abs(sc["sym"] - osc["sym"]) <= tol * max(abs(osc["sym"]), 1e-6), (kernel, d, N, step, sc["sym"], osc["sym"])
+    eng.close()
+
+
 # ---- 2. the full list is the plain / the graded sampler -------------------------------------------------------------------------------
 @pytest.mark.parametrize("graded", [False, True], ids=["uniform", "graded"])
 def test_the_full_list_is_the_sampler_it_indexes(graded):
