@@ -526,6 +526,19 @@ struct BwdOpts {
     bool bucketed = false;         // data-parallel step, generic set: finished layers go to the exchange stream
 };
 
+// What the records of an engine look like -- struct gpe_observables or struct gpe_mixture_observables: an engine is scalar or mixture
+// for life (gpe_observe.h, gpe_observe_mix.h)
+struct ObsKind {
+    int rec_doubles, row;          // doubles per record / per slab row of its reduction chain
+    int f_energy, f_res;           // index of the double a keeper judges by GPE_KEEP_ENERGY / GPE_KEEP_RES_RMS
+};
+#define OBS_FIELD(R, f) (int)(offsetof(struct R, f) / sizeof(double))
+static const ObsKind OBS_SCALAR = {(int)(sizeof(struct gpe_observables) / sizeof(double)), OB_ROW, OBS_FIELD(gpe_observables, energy),
+                                   OBS_FIELD(gpe_observables, res_rms)};
+static const ObsKind OBS_MIXTURE = {(int)(sizeof(struct gpe_mixture_observables) / sizeof(double)), MO_ROW, OBS_FIELD(gpe_mixture_observables, energy),
+                                    OBS_FIELD(gpe_mixture_observables, res_rms_total)};
+#undef OBS_FIELD
+
 struct gpe_engine {
     gpe_config cfg;
     NetDesc nd;
@@ -644,22 +657,30 @@ struct gpe_engine {
     int64_t dp_collectives = 0;                       // all-reduces issued since gpe_comm_init (bench / tests)
     bool dp_inline = true;                            // synchronous step on the fused / wide sets: collectives on the compute stream (GPE_DP_INLINE=0: exchange stream)
     // ---- observables (gpe_observe.h) ----
+    const ObsKind* obs_kind = nullptr;                // the engine's kind of record, chosen at the create for life
     double* obs_buf = nullptr;                        // [pass-1 slab | pass-2 slab | raw totals], allocated on first use
     double* obs_out = nullptr;                        // staging slot of gpe_observables / gpe_mixture_observables: one record of the engine's kind
     // held-out monitor (gpe_bind_monitor): its own forward batch, sized at the bind -- gpe_run must neither allocate nor synchronise
-    Batch mon;
-    const float* mon_x = nullptr; const float* mon_V = nullptr;
-    float mon_dv = 0.f;
-    int64_t mon_n = 0, mon_every = 0;                 // every == 0: no monitor
-    int64_t mon_steps = 0, mon_records = 0;           // steps enqueued / records appended since the bind
-    int mon_cap = 0;
-    double* mon_ring = nullptr;                       // [mon_cap] records of the engine's kind (obs_rec_doubles each)
+    struct Monitor {
+        Batch b;
+        const float* x = nullptr; const float* V = nullptr;
+        float dv = 0.f;
+        int64_t n = 0, every = 0;                     // every == 0: no monitor
+        int64_t steps = 0, records = 0;               // steps enqueued / records appended since the bind
+        int cap = 0;
+        double* ring = nullptr;                       // [cap] records of the engine's kind
+        bool bound() const { return every > 0; }
+        int64_t room() const { return every - steps % every; }      // steps up to and including the next record's (bound() only)
+    } mon;
     // keeper (gpe_bind_keeper): the best parameters by one field of the monitor's records; both buffers allocated at the bind
-    int keep_metric = GPE_KEEP_NONE;                  // GPE_KEEP_NONE: no keeper
-    double keep_min_delta = 0.0;
-    int64_t keep_patience = 0;
-    float* theta_best = nullptr;                      // [P], the engine's own padded layout
-    KeepDev* keep_dev = nullptr;
+    struct Keeper {
+        int metric = GPE_KEEP_NONE;                   // GPE_KEEP_NONE: no keeper
+        double min_delta = 0.0;
+        int64_t patience = 0;
+        float* theta_best = nullptr;                  // [P], the engine's own padded layout
+        KeepDev* dev = nullptr;
+        bool armed() const { return metric != GPE_KEEP_NONE; }
+    } keep;
     // device-side stratified sampler (gpe_bind_sampler and its kin): the engine owns the collocation points and redraws them in place.
     // One record for the four kinds; what is allocated says which one is bound (the predicates), and sampler_free resets all of it.
     struct Sampler {
@@ -1541,6 +1562,7 @@ static int reset_opt(gpe_engine* e, float lr) {
 static int check_config(gpe_engine* e, const gpe_config& in) {
     if (in.abi_version != GPE_ABI_VERSION) CFAIL("abi_version %d != %d", in.abi_version, GPE_ABI_VERSION);
     const gpe_config& c = e->cfg = in;
+    e->obs_kind = c.mixture ? &OBS_MIXTURE : &OBS_SCALAR;
     if (c.n_layers < 3 || c.n_layers > GPE_MAX_LAYERS) CFAIL("n_layers must be in [3,%d]", GPE_MAX_LAYERS);
     const int dim = c.layers[0], no = c.layers[c.n_layers - 1];
     if (dim < 1 || dim > GPE_MAX_DIM) CFAIL("dim must be 1..3");
@@ -1963,6 +1985,7 @@ static void orth_state_free(OrthState& s) {      // the stream is idle, or hipFr
 }
 
 static void sampler_free(gpe_engine* e);
+static void monitor_free(gpe_engine* e);
 void gpe_destroy(gpe_engine* e) {
     if (!e) return;
     (void)hipSetDevice(e->device);
@@ -1973,13 +1996,14 @@ void gpe_destroy(gpe_engine* e) {
     if (e->cap_stream) (void)hipStreamDestroy(e->cap_stream);
     if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
     if (e->ev_join) (void)hipEventDestroy(e->ev_join);
-    free_batch(e->main); free_batch(e->bc); free_batch(e->sym); free_batch(e->aux); free_batch(e->mse); free_batch(e->mon); free_batch(e->orb);
+    free_batch(e->main); free_batch(e->bc); free_batch(e->sym); free_batch(e->aux); free_batch(e->mse); free_batch(e->orb);
     for (int k = 0; k < GPE_MAX_ORTH; ++k) orth_state_free(e->ost[k]);
     for (hipEvent_t ev : e->ev_pool) (void)hipEventDestroy(ev);
     if (e->ext_exchange) { e->grad = nullptr; e->dbl = nullptr; }
-    void* ps[] = {e->theta, e->am, e->av, e->grad, e->dbl, e->od, e->hist, e->last, (void*)e->orth_dev, e->Wpk, e->WpkT, e->gslab, e->gslab_bc, e->grad_bc, (void*)e->upd_snap, (void*)e->head_slots, (void*)e->upd_ticket, (void*)e->upd_snap_small, (void*)e->obs_buf, (void*)e->obs_out, (void*)e->mon_ring, (void*)e->theta_best, (void*)e->keep_dev, (void*)e->smp.wq_red};
+    void* ps[] = {e->theta, e->am, e->av, e->grad, e->dbl, e->od, e->hist, e->last, (void*)e->orth_dev, e->Wpk, e->WpkT, e->gslab, e->gslab_bc, e->grad_bc, (void*)e->upd_snap, (void*)e->head_slots, (void*)e->upd_ticket, (void*)e->upd_snap_small, (void*)e->obs_buf, (void*)e->obs_out, (void*)e->smp.wq_red};
     for (void* p : ps) if (p) (void)hipFree(p);
     sampler_free(e);
+    monitor_free(e);                              // (the keeper with it)
     lbfgs_free(e);
     delete e;
 }
@@ -2069,10 +2093,9 @@ int gpe_reset_optimizer(gpe_engine* e, float lr) {
 }
 
 // (re)build the collocation batch from what is bound; decides whether the boundary points ride in it
-static void monitor_clear(gpe_engine* e);
 // a precomputed base lives on the bound points: a monitor on them (the only one allowed then) does not outlive a new bind
 static void monitor_drop_if_on_bound_points(gpe_engine* e) {
-    if (e->mon_every > 0 && e->cfg.base_mode >= 0 && e->cfg.base_kind == GPE_BASE_PRECOMPUTED) monitor_clear(e);
+    if (e->mon.bound() && e->cfg.base_mode >= 0 && e->cfg.base_kind == GPE_BASE_PRECOMPUTED) monitor_free(e);
 }
 
 static int rebuild_main(gpe_engine* e) {
@@ -2705,17 +2728,16 @@ int gpe_eval_density(gpe_engine* e, const float* d_x, int64_t n, float dx, int a
 
 
 // ---- observables of the current state (gpe_observe.h) --------------------------------------------------------------------
-// A scalar engine's records are struct gpe_observables, a mixture engine's struct gpe_mixture_observables (an engine is one or the other
-// for life): doubles per record, and per slab row of its reduction chain
-static int obs_rec_doubles(const gpe_engine* e) {
-    return (int)((e->cfg.mixture ? sizeof(struct gpe_mixture_observables) : sizeof(struct gpe_observables)) / sizeof(double));
+// every entry point of this section exists once per kind of record, and refuses the engine of the other kind; other: its counterpart
+static int obs_wrong_kind(gpe_engine* e, const char* who, const char* other) {
+    if (e->cfg.mixture) FAIL(e, GPE_ERR_STATE, "%s: its records are struct gpe_observables, which a mixture engine does not have (%s)", who, other);
+    FAIL(e, GPE_ERR_STATE, "%s: not a mixture engine (gpe_config.mixture; a scalar engine has %s)", who, other);
 }
-static int obs_row(const gpe_engine* e) { return e->cfg.mixture ? MO_ROW : OB_ROW; }
 static int obs_ensure(gpe_engine* e) {
     if (e->obs_buf) return GPE_OK;
     int rc;
-    if ((rc = dev_alloc(e, (Batch*)nullptr, &e->obs_buf, (size_t)2 * OBS_MAX_WG * obs_row(e) + obs_row(e)))) return rc;
-    return dev_alloc(e, (Batch*)nullptr, &e->obs_out, (size_t)obs_rec_doubles(e));
+    if ((rc = dev_alloc(e, (Batch*)nullptr, &e->obs_buf, (size_t)2 * OBS_MAX_WG * e->obs_kind->row + e->obs_kind->row))) return rc;
+    return dev_alloc(e, (Batch*)nullptr, &e->obs_out, (size_t)e->obs_kind->rec_doubles);
 }
 static bool precomputed_base(const gpe_engine* e) { return e->cfg.base_mode >= 0 && e->cfg.base_kind == GPE_BASE_PRECOMPUTED; }
 // which points an observables call / a monitor may look at: any, unless something exists on the bound points only
@@ -2729,19 +2751,21 @@ static int obs_check_points(gpe_engine* e, const char* who, const float* d_x, in
     if (e->cfg.potential == GPE_POT_PRECOMPUTED && !d_V) FAIL(e, GPE_ERR_INVALID, "%s: precomputed potential requested but d_V is NULL", who);
     return GPE_OK;
 }
-// the two reduction passes over the full jets b.O of the points x, and the struct into *dst (device memory); nothing synchronises
-// q: per-point quadrature weights [n] (the bound set under gpe_bind_weights), or NULL
-static int launch_observe(gpe_engine* e, Batch& b, const float* x, int64_t n, const float* V, float dv, struct gpe_observables* dst,
-                          const float* q = nullptr) {
+// The chain of kind K (ObsScalar, ObsMix): the two reduction passes over the full jets b.O of the points x, and the record into *dst
+// (device memory); nothing synchronises.  q: per-point quadrature weights [n] (the bound set under gpe_bind_weights), or NULL.
+extern "C++" {      // (a template inside the C-linkage block of the entry points)
+template <class K>
+static void obs_chain(gpe_engine* e, const typename K::Arg& ka, Batch& b, const float* x, int64_t n, const float* V, float dv, double* dst,
+                      const float* q) {
     const unsigned g = (unsigned)std::min<int64_t>(cdiv(n, OBS_THREADS), OBS_MAX_WG);        // a function of n alone: fixed point -> thread map
     double* slab1 = e->obs_buf;
-    double* slab2 = slab1 + (size_t)OBS_MAX_WG * OB_ROW;
-    double* raw = slab2 + (size_t)OBS_MAX_WG * OB_ROW;
+    double* slab2 = slab1 + (size_t)OBS_MAX_WG * K::ROW;
+    double* raw = slab2 + (size_t)OBS_MAX_WG * K::ROW;
     const float* const* bp = (const float* const*)e->orth_dev;
 #define OBS_CHAIN(DD, WW)                                                                                                                 \
-    hipLaunchKernelGGL((k_obs_pass1<DD, WW>), dim3(g), dim3(OBS_THREADS), 0, e->stream, e->ph, e->base_norm, x, V, (const float*)b.O, bp, n, b.ld, slab1, q); \
-    hipLaunchKernelGGL(k_obs_reduce, dim3(1), dim3(OBS_THREADS), 0, e->stream, (const double*)slab1, (int)g, raw);                       \
-    hipLaunchKernelGGL((k_obs_pass2<DD, WW>), dim3(g), dim3(OBS_THREADS), 0, e->stream, e->ph, e->base_norm, x, V, (const float*)b.O, bp, n, b.ld, \
+    hipLaunchKernelGGL((k_obs_pass1<K, DD, WW>), dim3(g), dim3(OBS_THREADS), 0, e->stream, e->ph, e->base_norm, x, V, (const float*)b.O, bp, n, b.ld, slab1, q); \
+    hipLaunchKernelGGL(k_obs_reduce<K>, dim3(1), dim3(OBS_THREADS), 0, e->stream, (const double*)slab1, (int)g, raw);                    \
+    hipLaunchKernelGGL((k_obs_pass2<K, DD, WW>), dim3(g), dim3(OBS_THREADS), 0, e->stream, e->ph, ka, e->base_norm, x, V, (const float*)b.O, bp, n, b.ld, \
                        (const double*)raw, (double)dv, slab2, q);
     switch (e->nd.dim * 2 + (q ? 1 : 0)) {
         case 2: OBS_CHAIN(1, false) break;
@@ -2752,83 +2776,51 @@ static int launch_observe(gpe_engine* e, Batch& b, const float* x, int64_t n, co
         default: OBS_CHAIN(3, true) break;
     }
 #undef OBS_CHAIN
-    hipLaunchKernelGGL(k_obs_finish, dim3(1), dim3(OBS_THREADS), 0, e->stream, e->ph, (const double*)slab2, (int)g, (const double*)raw, (double)dv,
-                       (double)n, (const OptDev*)e->od, dst);
+    hipLaunchKernelGGL(k_obs_finish<K>, dim3(1), dim3(OBS_THREADS), 0, e->stream, e->ph, ka, (const double*)slab2, (int)g, (const double*)raw, (double)dv,
+                       (double)n, (const OptDev*)e->od, (typename K::Record*)dst);
+}
+}
+// a mixture's couplings and target norms are those in force now (e->oc.mix, by value)
+static int launch_observe(gpe_engine* e, Batch& b, const float* x, int64_t n, const float* V, float dv, double* dst, const float* q = nullptr) {
+    if (e->cfg.mixture) obs_chain<ObsMix>(e, e->oc.mix, b, x, n, V, dv, dst, q);
+    else obs_chain<ObsScalar>(e, ObsNoArg{}, b, x, n, V, dv, dst, q);
     HIPCHK(e, hipGetLastError());
     return GPE_OK;
 }
 
+// gpe_observables / gpe_mixture_observables: out takes one record of the engine's kind
+static int observables_impl(gpe_engine* e, const char* who, const float* d_x, int64_t n, const float* d_V, float dv, void* out) {
+    const float* q = nullptr;
+    if (!d_x) {
+        if (!e->ux) FAIL(e, GPE_ERR_STATE, "%s of the bound points before bind_points", who);
+        d_x = e->ux; n = e->n_pde; d_V = e->uV;
+        q = e->wq;                               // the bound set carries its bound weights; an explicit set and the monitor have none
+    }
+    int rc;
+    if ((rc = obs_check_points(e, who, d_x, n, d_V))) return rc;
+    if ((rc = obs_ensure(e))) return rc;
+    if ((rc = aux_forward(e, d_x, n, 1 + 2 * e->nd.dim, e->nd.dim))) return rc;       // full diagonal second derivatives, as gpe_forward_jets
+    if ((rc = launch_observe(e, e->aux, d_x, n, d_V, dv, e->obs_out, q))) return rc;
+    HIPCHK(e, hipMemcpyAsync(out, e->obs_out, (size_t)e->obs_kind->rec_doubles * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    return GPE_OK;
+}
 int gpe_observables(gpe_engine* e, const float* d_x, int64_t n, const float* d_V, float dv, struct gpe_observables* out) {
     if (!e || !out) return GPE_ERR_INVALID;
-    if (e->cfg.mixture) FAIL(e, GPE_ERR_STATE, "observables: not defined for a mixture engine (they would read the two components as complex psi)");
-    const float* q = nullptr;
-    if (!d_x) {
-        if (!e->ux) FAIL(e, GPE_ERR_STATE, "observables of the bound points before bind_points");
-        d_x = e->ux; n = e->n_pde; d_V = e->uV;
-        q = e->wq;                               // the bound set carries its bound weights; an explicit set and the monitor have none
-    }
-    int rc;
-    if ((rc = obs_check_points(e, "observables", d_x, n, d_V))) return rc;
-    if ((rc = obs_ensure(e))) return rc;
-    if ((rc = aux_forward(e, d_x, n, 1 + 2 * e->nd.dim, e->nd.dim))) return rc;       // full diagonal second derivatives, as gpe_forward_jets
-    if ((rc = launch_observe(e, e->aux, d_x, n, d_V, dv, (struct gpe_observables*)e->obs_out, q))) return rc;
-    HIPCHK(e, hipMemcpyAsync(out, e->obs_out, sizeof *out, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-    return GPE_OK;
+    if (e->cfg.mixture) return obs_wrong_kind(e, "observables", "gpe_mixture_observables");
+    return observables_impl(e, "observables", d_x, n, d_V, dv, out);
 }
-
-// the mixture instances of the chain (gpe_observe_mix.h): same grid, same slab layout with rows of MO_ROW doubles; the couplings and
-// target norms are those in force now (e->oc.mix, by value)
-static int launch_observe_mix(gpe_engine* e, Batch& b, const float* x, int64_t n, const float* V, float dv, struct gpe_mixture_observables* dst,
-                              const float* q = nullptr) {
-    const unsigned g = (unsigned)std::min<int64_t>(cdiv(n, OBS_THREADS), OBS_MAX_WG);        // a function of n alone: fixed point -> thread map
-    double* slab1 = e->obs_buf;
-    double* slab2 = slab1 + (size_t)OBS_MAX_WG * MO_ROW;
-    double* raw = slab2 + (size_t)OBS_MAX_WG * MO_ROW;
-#define MIXOBS_CHAIN(DD, WW)                                                                                                              \
-    hipLaunchKernelGGL((k_mixobs_pass1<DD, WW>), dim3(g), dim3(OBS_THREADS), 0, e->stream, e->ph, x, V, (const float*)b.O, n, b.ld, slab1, q); \
-    hipLaunchKernelGGL(k_mixobs_reduce, dim3(1), dim3(OBS_THREADS), 0, e->stream, (const double*)slab1, (int)g, raw);                    \
-    hipLaunchKernelGGL((k_mixobs_pass2<DD, WW>), dim3(g), dim3(OBS_THREADS), 0, e->stream, e->ph, e->oc.mix, x, V, (const float*)b.O, n, b.ld, \
-                       (const double*)raw, (double)dv, slab2, q);
-    switch (e->nd.dim * 2 + (q ? 1 : 0)) {
-        case 2: MIXOBS_CHAIN(1, false) break;
-        case 3: MIXOBS_CHAIN(1, true) break;
-        case 4: MIXOBS_CHAIN(2, false) break;
-        case 5: MIXOBS_CHAIN(2, true) break;
-        case 6: MIXOBS_CHAIN(3, false) break;
-        default: MIXOBS_CHAIN(3, true) break;
-    }
-#undef MIXOBS_CHAIN
-    hipLaunchKernelGGL(k_mixobs_finish, dim3(1), dim3(OBS_THREADS), 0, e->stream, e->ph, e->oc.mix, (const double*)slab2, (int)g, (const double*)raw,
-                       (double)dv, (double)n, (const OptDev*)e->od, dst);
-    HIPCHK(e, hipGetLastError());
-    return GPE_OK;
-}
-
 int gpe_mixture_observables(gpe_engine* e, const float* d_x, int64_t n, const float* d_V, float dv, struct gpe_mixture_observables* out) {
     if (!e || !out) return GPE_ERR_INVALID;
-    if (!e->cfg.mixture) FAIL(e, GPE_ERR_STATE, "mixture_observables: not a mixture engine (gpe_config.mixture; a scalar engine has gpe_observables)");
-    const float* q = nullptr;
-    if (!d_x) {
-        if (!e->ux) FAIL(e, GPE_ERR_STATE, "mixture_observables of the bound points before bind_points");
-        d_x = e->ux; n = e->n_pde; d_V = e->uV;
-        q = e->wq;                               // the bound set carries its bound weights; an explicit set and the monitor have none
-    }
-    int rc;
-    if ((rc = obs_check_points(e, "mixture_observables", d_x, n, d_V))) return rc;
-    if ((rc = obs_ensure(e))) return rc;
-    if ((rc = aux_forward(e, d_x, n, 1 + 2 * e->nd.dim, e->nd.dim))) return rc;       // full diagonal second derivatives, as gpe_forward_jets
-    if ((rc = launch_observe_mix(e, e->aux, d_x, n, d_V, dv, (struct gpe_mixture_observables*)e->obs_out, q))) return rc;
-    HIPCHK(e, hipMemcpyAsync(out, e->obs_out, sizeof *out, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-    return GPE_OK;
+    if (!e->cfg.mixture) return obs_wrong_kind(e, "mixture_observables", "gpe_observables");
+    return observables_impl(e, "mixture_observables", d_x, n, d_V, dv, out);
 }
 
 // ---- keeper: model selection and a patience stop driven by the monitor (gpe_observe.h: k_keep_decide, k_keep_copy) -----------------------
-static void keeper_clear(gpe_engine* e) {             // the stream is idle, or hipFree waits for it
-    e->keep_metric = GPE_KEEP_NONE; e->keep_min_delta = 0.0; e->keep_patience = 0;
-    if (e->theta_best) { (void)hipFree(e->theta_best); e->theta_best = nullptr; }
-    if (e->keep_dev) { (void)hipFree(e->keep_dev); e->keep_dev = nullptr; }
+static void keeper_free(gpe_engine* e) {              // the stream is idle, or hipFree waits for it
+    if (e->keep.theta_best) (void)hipFree(e->keep.theta_best);
+    if (e->keep.dev) (void)hipFree(e->keep.dev);
+    e->keep = gpe_engine::Keeper();
 }
 // "nothing kept": best = +inf, every counter and flag zero
 static int keeper_reset(gpe_engine* e, KeepDev* kd) {
@@ -2839,39 +2831,33 @@ static int keeper_reset(gpe_engine* e, KeepDev* kd) {
     HIPCHK(e, hipStreamSynchronize(e->stream));
     return GPE_OK;
 }
-static int keeper_field(const gpe_engine* e, int metric) {      // index of the chosen double in the engine's kind of record
-    if (e->cfg.mixture)
-        return (int)((metric == GPE_KEEP_ENERGY ? offsetof(struct gpe_mixture_observables, energy)
-                                                : offsetof(struct gpe_mixture_observables, res_rms_total)) / sizeof(double));
-    return (int)((metric == GPE_KEEP_ENERGY ? offsetof(struct gpe_observables, energy) : offsetof(struct gpe_observables, res_rms)) / sizeof(double));
-}
 static int keeper_state(gpe_engine* e, const char* who, KeepDev* h) {      // synchronises
-    if (e->keep_metric == GPE_KEEP_NONE) FAIL(e, GPE_ERR_STATE, "%s: no keeper bound (gpe_bind_keeper)", who);
-    HIPCHK(e, hipMemcpyAsync(h, e->keep_dev, sizeof *h, hipMemcpyDeviceToHost, e->stream));
+    if (!e->keep.armed()) FAIL(e, GPE_ERR_STATE, "%s: no keeper bound (gpe_bind_keeper)", who);
+    HIPCHK(e, hipMemcpyAsync(h, e->keep.dev, sizeof *h, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));
     return GPE_OK;
 }
 
-static void monitor_clear(gpe_engine* e) {
-    keeper_clear(e);                                  // its metric exists on the monitor's points only
-    e->mon_every = 0; e->mon_steps = 0; e->mon_records = 0;
-    e->mon_x = nullptr; e->mon_V = nullptr; e->mon_n = 0;
-    free_batch(e->mon);
-    if (e->mon_ring) { (void)hipFree(e->mon_ring); e->mon_ring = nullptr; e->mon_cap = 0; }
+static void monitor_free(gpe_engine* e) {
+    keeper_free(e);                                   // its metric exists on the monitor's points only
+    free_batch(e->mon.b);
+    if (e->mon.ring) (void)hipFree(e->mon.ring);
+    e->mon = gpe_engine::Monitor();
 }
 
 // gpe_bind_monitor / gpe_mixture_monitor: the ring holds records of the engine's kind
 static int monitor_bind(gpe_engine* e, const float* d_x, int64_t n, const float* d_V, float dv, int64_t every, int32_t capacity) {
+    gpe_engine::Monitor& mn = e->mon;
     HIPCHK(e, hipStreamSynchronize(e->stream));
-    if (!d_x || every <= 0) { monitor_clear(e); return GPE_OK; }
+    if (!d_x || every <= 0) { monitor_free(e); return GPE_OK; }
     // validate and allocate first, swap last: a bind that fails leaves the monitor that was there, records included
     int rc;
     if ((rc = obs_check_points(e, "monitor", d_x, n, d_V))) return rc;
     if ((rc = obs_ensure(e))) return rc;
     const int cap = capacity > 0 ? capacity : 4096;
-    const size_t rec_bytes = (size_t)obs_rec_doubles(e) * sizeof(double);
-    double* ring = e->mon_ring;
-    if (cap != e->mon_cap) {
+    const size_t rec_bytes = (size_t)e->obs_kind->rec_doubles * sizeof(double);
+    double* ring = mn.ring;
+    if (cap != mn.cap) {
         ring = nullptr;
         if (hipMalloc((void**)&ring, (size_t)cap * rec_bytes) != hipSuccess) {
             (void)hipGetLastError();
@@ -2879,87 +2865,85 @@ static int monitor_bind(gpe_engine* e, const float* d_x, int64_t n, const float*
         }
     }
     Batch nb;
-    if (e->mon.n == n && e->mon.O) std::swap(nb, e->mon);           // same size: the batch is reused
+    if (mn.b.n == n && mn.b.O) std::swap(nb, mn.b);                 // same size: the batch is reused
     if ((rc = setup_batch(e, nb, d_x, n, 1 + 2 * e->nd.dim, e->nd.dim, false, d_V, /*with_store=*/false))) {
         free_batch(nb);
-        if (ring != e->mon_ring) (void)hipFree(ring);
+        if (ring != mn.ring) (void)hipFree(ring);
         return rc;                                                   // (a reused batch cannot fail: nothing is allocated for it)
     }
-    free_batch(e->mon);
-    e->mon = nb;
-    if (ring != e->mon_ring) { if (e->mon_ring) (void)hipFree(e->mon_ring); e->mon_ring = ring; e->mon_cap = cap; }
-    HIPCHK(e, hipMemsetAsync(e->mon_ring, 0, (size_t)cap * rec_bytes, e->stream));
+    free_batch(mn.b);
+    mn.b = nb;
+    if (ring != mn.ring) { if (mn.ring) (void)hipFree(mn.ring); mn.ring = ring; mn.cap = cap; }
+    HIPCHK(e, hipMemsetAsync(mn.ring, 0, (size_t)cap * rec_bytes, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));
-    e->mon_x = d_x; e->mon_V = d_V; e->mon_n = n; e->mon_dv = dv; e->mon_every = every;
-    e->mon_steps = 0; e->mon_records = 0;
+    mn.x = d_x; mn.V = d_V; mn.n = n; mn.dv = dv; mn.every = every;
+    mn.steps = 0; mn.records = 0;
     // an armed keeper stays armed and starts again from "nothing kept": its metric is comparable on one point set only
-    if (e->keep_metric != GPE_KEEP_NONE) return keeper_reset(e, e->keep_dev);
+    if (e->keep.armed()) return keeper_reset(e, e->keep.dev);
     return GPE_OK;
 }
-
+// (a clearing call is served whatever the kind: there is nothing of the other kind to clear)
 int gpe_bind_monitor(gpe_engine* e, const float* d_x, int64_t n, const float* d_V, float dv, int64_t every, int32_t capacity) {
     if (!e) return GPE_ERR_INVALID;
-    if (e->cfg.mixture && d_x && every > 0)
-        FAIL(e, GPE_ERR_STATE, "monitor: its records are struct gpe_observables, which a mixture engine does not have (gpe_mixture_monitor)");
+    if (e->cfg.mixture && d_x && every > 0) return obs_wrong_kind(e, "monitor", "gpe_mixture_monitor");
     return monitor_bind(e, d_x, n, d_V, dv, every, capacity);
 }
 int gpe_mixture_monitor(gpe_engine* e, const float* d_x, int64_t n, const float* d_V, float dv, int64_t every, int32_t capacity) {
     if (!e) return GPE_ERR_INVALID;
-    if (!e->cfg.mixture) FAIL(e, GPE_ERR_STATE, "mixture_monitor: not a mixture engine (gpe_config.mixture; a scalar engine has gpe_bind_monitor)");
+    if (!e->cfg.mixture) return obs_wrong_kind(e, "mixture_monitor", "gpe_bind_monitor");
     return monitor_bind(e, d_x, n, d_V, dv, every, capacity);
 }
 
-// gpe_bind_keeper / gpe_mixture_keeper: the field judged is one of the engine's kind of record (keeper_field)
+// gpe_bind_keeper / gpe_mixture_keeper: the field judged is one of the engine's kind of record (ObsKind)
 static int keeper_bind(gpe_engine* e, int metric, double min_delta, int64_t patience) {
+    gpe_engine::Keeper& kp = e->keep;
     if (metric == GPE_KEEP_NONE) {
         HIPCHK(e, hipStreamSynchronize(e->stream));
-        keeper_clear(e);
+        keeper_free(e);
         return GPE_OK;
     }
     // validate and allocate first, swap last: a bind that fails leaves the keeper that was there, its kept set included
     if (metric != GPE_KEEP_RES_RMS && metric != GPE_KEEP_ENERGY) FAIL(e, GPE_ERR_INVALID, "keeper: metric %d is none of GPE_KEEP_RES_RMS, GPE_KEEP_ENERGY", metric);
-    if (e->mon_every <= 0) FAIL(e, GPE_ERR_INVALID, "keeper: needs a bound monitor (gpe_bind_monitor): it judges the monitor's records");
+    if (!e->mon.bound()) FAIL(e, GPE_ERR_INVALID, "keeper: needs a bound monitor (gpe_bind_monitor): it judges the monitor's records");
     if (!(min_delta >= 0.0) || !__builtin_isfinite(min_delta)) FAIL(e, GPE_ERR_INVALID, "keeper: min_delta must be finite and >= 0");
     if (patience < 0) FAIL(e, GPE_ERR_INVALID, "keeper: patience must be >= 0 (0: never stop)");
     if (e->comm)
         FAIL(e, GPE_ERR_INVALID, "keeper: this engine has a communicator (gpe_comm_init): every rank's monitor sees its own points, so the ranks would keep "
                                  "and stop at different records; data-parallel keepers are not supported");
     HIPCHK(e, hipStreamSynchronize(e->stream));
-    float* tb = e->theta_best; KeepDev* kd = e->keep_dev;             // an armed keeper's buffers are reused (P never changes)
+    float* tb = kp.theta_best; KeepDev* kd = kp.dev;                  // an armed keeper's buffers are reused (P never changes)
     if (!tb && hipMalloc((void**)&tb, (size_t)e->P * 4 + 256) != hipSuccess) {
         (void)hipGetLastError();
         FAIL(e, GPE_ERR_NOMEM, "keeper: no memory for a copy of %d parameters", e->P);
     }
     if (!kd && hipMalloc((void**)&kd, sizeof(KeepDev)) != hipSuccess) {
         (void)hipGetLastError();
-        if (tb != e->theta_best) (void)hipFree(tb);
+        if (tb != kp.theta_best) (void)hipFree(tb);
         FAIL(e, GPE_ERR_NOMEM, "keeper: no memory for its state");
     }
     int rc = keeper_reset(e, kd);
     if (rc) {                                                         // (an armed keeper may have lost its counters; its buffers stay)
-        if (tb != e->theta_best) (void)hipFree(tb);
-        if (kd != e->keep_dev) (void)hipFree(kd);
+        if (tb != kp.theta_best) (void)hipFree(tb);
+        if (kd != kp.dev) (void)hipFree(kd);
         return rc;
     }
-    e->theta_best = tb; e->keep_dev = kd;
-    e->keep_metric = metric; e->keep_min_delta = min_delta; e->keep_patience = patience;
+    kp.theta_best = tb; kp.dev = kd;
+    kp.metric = metric; kp.min_delta = min_delta; kp.patience = patience;
     return GPE_OK;
 }
-
 int gpe_bind_keeper(gpe_engine* e, int metric, double min_delta, int64_t patience) {
     if (!e) return GPE_ERR_INVALID;
-    if (e->cfg.mixture && metric != GPE_KEEP_NONE)
-        FAIL(e, GPE_ERR_STATE, "keeper: it judges records of struct gpe_observables, which a mixture engine does not have (gpe_mixture_keeper)");
+    if (e->cfg.mixture && metric != GPE_KEEP_NONE) return obs_wrong_kind(e, "keeper", "gpe_mixture_keeper");
     return keeper_bind(e, metric, min_delta, patience);
 }
 int gpe_mixture_keeper(gpe_engine* e, int metric, double min_delta, int64_t patience) {
     if (!e) return GPE_ERR_INVALID;
-    if (!e->cfg.mixture) FAIL(e, GPE_ERR_STATE, "mixture_keeper: not a mixture engine (gpe_config.mixture; a scalar engine has gpe_bind_keeper)");
+    if (!e->cfg.mixture) return obs_wrong_kind(e, "mixture_keeper", "gpe_bind_keeper");
     return keeper_bind(e, metric, min_delta, patience);
 }
 
-// gpe_keeper_read / gpe_mixture_keeper_read: rec takes the first rec_bytes of the kept record
-static int keeper_read(gpe_engine* e, float* h_flat, size_t n, void* rec, size_t rec_bytes, int64_t* seen, int64_t* kept, int64_t* since_best, int* stopped) {
+// gpe_keeper_read / gpe_mixture_keeper_read: rec takes the kept record, one of the engine's kind
+static int keeper_read(gpe_engine* e, float* h_flat, size_t n, void* rec, int64_t* seen, int64_t* kept, int64_t* since_best, int* stopped) {
     if (h_flat && (int64_t)n != e->P_user) FAIL(e, GPE_ERR_INVALID, "keeper_read: got %zu floats, model has %d", n, e->P_user);
     KeepDev h;
     int rc;
@@ -2970,24 +2954,24 @@ static int keeper_read(gpe_engine* e, float* h_flat, size_t n, void* rec, size_t
     if (stopped) *stopped = h.stopped;
     if (!h_flat && !rec) return GPE_OK;
     if (h.kept == 0) FAIL(e, GPE_ERR_INVALID, "keeper_read: nothing kept yet (%lld records judged, none finite)", (long long)h.seen);
-    if (rec) memcpy(rec, h.rec, rec_bytes);
+    if (rec) memcpy(rec, h.rec, (size_t)e->obs_kind->rec_doubles * sizeof(double));
     if (h_flat) {
-        if ((rc = flat_from_device(e, e->theta_best, h_flat))) return rc;
+        if ((rc = flat_from_device(e, e->keep.theta_best, h_flat))) return rc;
         HIPCHK(e, hipStreamSynchronize(e->stream));
     }
     return GPE_OK;
 }
-
+// (the counters and the parameters are served whatever the kind: only a record has one)
 int gpe_keeper_read(gpe_engine* e, float* h_flat, size_t n, struct gpe_observables* rec, int64_t* seen, int64_t* kept, int64_t* since_best, int* stopped) {
     if (!e) return GPE_ERR_INVALID;
-    if (e->cfg.mixture && rec) FAIL(e, GPE_ERR_STATE, "keeper_read: a mixture engine keeps a struct gpe_mixture_observables (gpe_mixture_keeper_read)");
-    return keeper_read(e, h_flat, n, rec, sizeof *rec, seen, kept, since_best, stopped);
+    if (e->cfg.mixture && rec) return obs_wrong_kind(e, "keeper_read", "gpe_mixture_keeper_read");
+    return keeper_read(e, h_flat, n, rec, seen, kept, since_best, stopped);
 }
 int gpe_mixture_keeper_read(gpe_engine* e, float* h_flat, size_t n, struct gpe_mixture_observables* rec, int64_t* seen, int64_t* kept,
                             int64_t* since_best, int* stopped) {
     if (!e) return GPE_ERR_INVALID;
-    if (!e->cfg.mixture) FAIL(e, GPE_ERR_STATE, "mixture_keeper_read: not a mixture engine (gpe_config.mixture; a scalar engine has gpe_keeper_read)");
-    return keeper_read(e, h_flat, n, rec, sizeof *rec, seen, kept, since_best, stopped);
+    if (!e->cfg.mixture) return obs_wrong_kind(e, "mixture_keeper_read", "gpe_keeper_read");
+    return keeper_read(e, h_flat, n, rec, seen, kept, since_best, stopped);
 }
 
 int gpe_keeper_restore(gpe_engine* e) {
@@ -2996,72 +2980,75 @@ int gpe_keeper_restore(gpe_engine* e) {
     int rc;
     if ((rc = keeper_state(e, "keeper_restore", &h))) return rc;
     if (h.kept == 0) FAIL(e, GPE_ERR_INVALID, "keeper_restore: nothing kept yet");
-    HIPCHK(e, hipMemcpyAsync(e->theta, e->theta_best, (size_t)e->P * 4, hipMemcpyDeviceToDevice, e->stream));
+    HIPCHK(e, hipMemcpyAsync(e->theta, e->keep.theta_best, (size_t)e->P * 4, hipMemcpyDeviceToDevice, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));
     e->packed_dirty = true;                           // as gpe_set_params: the packed weight copies are rebuilt before their next use
     return lbfgs_reset(e);
 }
 
-// k steps were just enqueued (never past a monitor step: gpe_run cuts there).  On a monitor step: forward of the monitor points with the
-// parameters that step left behind -- on the fused path through the packed weight copies the update refreshed, or ensure_packed
-// refreshes here, the path gpe_forward between two gpe_run calls takes -- the reduction chain, one record into the ring.
-static int monitor_record(gpe_engine* e);
-static int monitor_after_steps(gpe_engine* e, int64_t k) {
-    if (e->mon_every <= 0) return GPE_OK;
-    e->mon_steps += k;
-    if (e->mon_steps % e->mon_every != 0) return GPE_OK;
-    return monitor_record(e);
+// The monitor's one cadence: k steps (or ticks of gpe_lbfgs_run) were just enqueued -- never past a monitor step: gpe_run cuts its
+// replays at Monitor::room() -- and the answer is whether a record is due now.
+static bool monitor_tick(gpe_engine* e, int64_t k) {
+    if (!e->mon.bound()) return false;
+    e->mon.steps += k;
+    return e->mon.steps % e->mon.every == 0;
 }
-// the chain of one record, of theta as it stands (gpe_lbfgs_run puts the judged point there first: lbfgs_monitor_tick)
+// The chain of one record, of theta as it stands (gpe_lbfgs_run puts the judged point there first: lbfgs_monitor_tick): forward of the
+// monitor points with the parameters the last step left behind -- on the fused path through the packed weight copies the update
+// refreshed, or ensure_packed refreshes here, the path gpe_forward between two gpe_run calls takes -- the reduction chain, one record
+// into the ring.
 static int monitor_record(gpe_engine* e) {
+    gpe_engine::Monitor& mn = e->mon;
+    const gpe_engine::Keeper& kp = e->keep;
     int rc;
-    if ((rc = mlp_forward(e, e->mon, false))) return rc;
-    double* slot = e->mon_ring + (size_t)(e->mon_records % e->mon_cap) * obs_rec_doubles(e);
-    if (e->cfg.mixture) rc = launch_observe_mix(e, e->mon, e->mon_x, e->mon_n, e->mon_V, e->mon_dv, (struct gpe_mixture_observables*)slot);
-    else rc = launch_observe(e, e->mon, e->mon_x, e->mon_n, e->mon_V, e->mon_dv, (struct gpe_observables*)slot);
-    if (rc) return rc;
-    if (e->keep_metric != GPE_KEEP_NONE) {            // the record just written, judged and -- if it is the best so far -- theta set aside
-        hipLaunchKernelGGL(k_keep_decide, dim3(1), dim3(64), 0, e->stream, (const double*)slot, keeper_field(e, e->keep_metric), obs_rec_doubles(e),
-                           e->keep_min_delta, (long long)e->keep_patience, e->keep_dev, e->od);
+    if ((rc = mlp_forward(e, mn.b, false))) return rc;
+    double* slot = mn.ring + (size_t)(mn.records % mn.cap) * e->obs_kind->rec_doubles;
+    if ((rc = launch_observe(e, mn.b, mn.x, mn.n, mn.V, mn.dv, slot))) return rc;
+    if (kp.armed()) {                                 // the record just written, judged and -- if it is the best so far -- theta set aside
+        hipLaunchKernelGGL(k_keep_decide, dim3(1), dim3(64), 0, e->stream, (const double*)slot,
+                           kp.metric == GPE_KEEP_ENERGY ? e->obs_kind->f_energy : e->obs_kind->f_res, e->obs_kind->rec_doubles, kp.min_delta,
+                           (long long)kp.patience, kp.dev, e->od);
         const unsigned g = (unsigned)std::min<int64_t>(cdiv((int64_t)cdiv(e->P, 4), KEEP_THREADS), KEEP_MAX_WG);       // a function of P alone
-        hipLaunchKernelGGL(k_keep_copy, dim3(g), dim3(KEEP_THREADS), 0, e->stream, (const KeepDev*)e->keep_dev, (const float*)e->theta, e->theta_best, e->P);
+        hipLaunchKernelGGL(k_keep_copy, dim3(g), dim3(KEEP_THREADS), 0, e->stream, (const KeepDev*)kp.dev, (const float*)e->theta, kp.theta_best, e->P);
         HIPCHK(e, hipGetLastError());
     }
-    e->mon_records++;
+    mn.records++;
     return GPE_OK;
 }
+static int monitor_after_steps(gpe_engine* e, int64_t k) { return monitor_tick(e, k) ? monitor_record(e) : GPE_OK; }
 
 // gpe_read_monitor / gpe_mixture_monitor_read: out takes records of the engine's kind
 static int monitor_read(gpe_engine* e, int64_t first, int64_t count, void* out, int64_t* available) {
-    const size_t rec_bytes = (size_t)obs_rec_doubles(e) * sizeof(double);
+    const gpe_engine::Monitor& mn = e->mon;
+    const size_t rec_bytes = (size_t)e->obs_kind->rec_doubles * sizeof(double);
     HIPCHK(e, hipStreamSynchronize(e->stream));
-    if (available) *available = e->mon_records;
+    if (available) *available = mn.records;
     if (count == 0) return GPE_OK;
-    if (first + count > e->mon_records)
-        FAIL(e, GPE_ERR_INVALID, "monitor records [%lld, %lld) requested, %lld exist", (long long)first, (long long)(first + count), (long long)e->mon_records);
-    if (first < e->mon_records - e->mon_cap)
-        FAIL(e, GPE_ERR_INVALID, "monitor record %lld is gone: the ring keeps the newest %d of %lld", (long long)first, e->mon_cap, (long long)e->mon_records);
+    if (first + count > mn.records)
+        FAIL(e, GPE_ERR_INVALID, "monitor records [%lld, %lld) requested, %lld exist", (long long)first, (long long)(first + count), (long long)mn.records);
+    if (first < mn.records - mn.cap)
+        FAIL(e, GPE_ERR_INVALID, "monitor record %lld is gone: the ring keeps the newest %d of %lld", (long long)first, mn.cap, (long long)mn.records);
     for (int64_t i = 0; i < count;) {
-        const int64_t slot = (first + i) % e->mon_cap;
-        const int64_t run = std::min<int64_t>(count - i, e->mon_cap - slot);
-        HIPCHK(e, hipMemcpy((char*)out + i * rec_bytes, (const char*)e->mon_ring + slot * rec_bytes, run * rec_bytes, hipMemcpyDeviceToHost));
+        const int64_t slot = (first + i) % mn.cap;
+        const int64_t run = std::min<int64_t>(count - i, mn.cap - slot);
+        HIPCHK(e, hipMemcpy((char*)out + i * rec_bytes, (const char*)mn.ring + slot * rec_bytes, run * rec_bytes, hipMemcpyDeviceToHost));
         i += run;
     }
     return GPE_OK;
 }
 int gpe_read_monitor(gpe_engine* e, int64_t first, int64_t count, struct gpe_observables* out, int64_t* available) {
     if (!e || first < 0 || count < 0 || (count > 0 && !out)) return GPE_ERR_INVALID;
-    if (e->cfg.mixture) {                             // (a mixture engine never held a record of this kind: none available, none to read)
-        if (count > 0) FAIL(e, GPE_ERR_STATE, "read_monitor: a mixture engine's records are struct gpe_mixture_observables (gpe_mixture_monitor_read)");
+    if (e->cfg.mixture && count == 0) {               // (a mixture engine never held a record of this kind: none available, none to read)
         HIPCHK(e, hipStreamSynchronize(e->stream));
         if (available) *available = 0;
         return GPE_OK;
     }
+    if (e->cfg.mixture) return obs_wrong_kind(e, "read_monitor", "gpe_mixture_monitor_read");
     return monitor_read(e, first, count, out, available);
 }
 int gpe_mixture_monitor_read(gpe_engine* e, int64_t first, int64_t count, struct gpe_mixture_observables* out, int64_t* available) {
     if (!e || first < 0 || count < 0 || (count > 0 && !out)) return GPE_ERR_INVALID;
-    if (!e->cfg.mixture) FAIL(e, GPE_ERR_STATE, "mixture_monitor_read: not a mixture engine (gpe_config.mixture; a scalar engine has gpe_read_monitor)");
+    if (!e->cfg.mixture) return obs_wrong_kind(e, "mixture_monitor_read", "gpe_read_monitor");
     return monitor_read(e, first, count, out, available);
 }
 
@@ -3429,16 +3416,14 @@ int gpe_lbfgs_update(gpe_engine* e) {
 // stands in theta's place for the length of the monitor chain -- on the fused path mlp_forward repacks the weight copies from it -- and
 // theta comes back behind it, so the run goes on from the bits it would have had; the next evaluation repacks, as after every tick.
 static int lbfgs_monitor_tick(gpe_engine* e) {
-    if (!e->lb.mon || e->mon_every <= 0) return GPE_OK;
-    e->mon_steps += 1;
-    if (e->mon_steps % e->mon_every != 0) return GPE_OK;
+    if (!e->lb.mon || !monitor_tick(e, 1)) return GPE_OK;
     const unsigned g = lbfgs_view_grid(e->P);
     hipLaunchKernelGGL(k_lbfgs_view, dim3(g), dim3(LBV_THREADS), 0, e->stream, e->P, e->theta, e->lb.view_buf, e->lb.st);
     HIPCHK(e, hipGetLastError());
     e->packed_dirty = e->path == GPE_PATH_FUSED;
     const int rc = monitor_record(e);
     hipLaunchKernelGGL(k_lbfgs_unview, dim3(g), dim3(LBV_THREADS), 0, e->stream, e->P, e->theta, (const float*)e->lb.view_buf, e->lb.st,
-                       (const KeepDev*)(e->keep_metric != GPE_KEEP_NONE ? e->keep_dev : nullptr));
+                       (const KeepDev*)(e->keep.armed() ? e->keep.dev : nullptr));
     HIPCHK(e, hipGetLastError());
     e->packed_dirty = e->path == GPE_PATH_FUSED;
     return rc;
@@ -3891,7 +3876,7 @@ int gpe_run(gpe_engine* e, int64_t n_steps) {
             while (done + e->graph_steps <= n_steps) {
                 // a replay must not run past a monitor step, nor across a redraw of the sampler: up to there with plain launches when
                 // fewer than a graph's steps are left to it
-                int64_t room = e->mon_every > 0 ? e->mon_every - e->mon_steps % e->mon_every : e->graph_steps;
+                int64_t room = e->mon.bound() ? e->mon.room() : e->graph_steps;
                 if (e->smp.bound()) room = std::min(room, e->smp.every - e->smp.steps % e->smp.every);
                 if (room >= e->graph_steps) {
                     if (e->smp.bound()) {         // the redraw a replay may start with is enqueued here, outside the graph

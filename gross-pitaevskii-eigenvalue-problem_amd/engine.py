@@ -648,28 +648,66 @@ class Engine:
         self._keep[name + "_x"], self._keep[name + "_V"] = x, Vt
         return x, Vt, float(self.cfg.dx if dv is None else dv)
 
+    # the entry points and the record of each kind of engine (scalar, mixture); the public methods below are thin pairs over these
+    _OBS_KINDS = {False: dict(observables="gpe_observables", bind_monitor="gpe_bind_monitor", read_monitor="gpe_read_monitor",
+                              bind_keeper="gpe_bind_keeper", record=capi.gpe_observables),
+                  True: dict(observables="gpe_mixture_observables", bind_monitor="gpe_mixture_monitor", read_monitor="gpe_mixture_monitor_read",
+                             bind_keeper="gpe_mixture_keeper", record=capi.gpe_mixture_observables)}
+
+    def _obs_entry(self, mixture, name):
+        return getattr(self.lib, self._OBS_KINDS[bool(mixture)][name])
+
+    def _observables(self, mixture, x, V, dv) -> dict:
+        fn, out = self._obs_entry(mixture, "observables"), self._OBS_KINDS[mixture]["record"]()
+        if x is None:
+            self._chk(fn(self._h, None, 0, None, float(self.cfg.dx if dv is None else dv), C.byref(out)))
+        else:
+            x, Vt, dv = self._obs_args(x, V, dv, "obs")
+            self._chk(fn(self._h, C.c_void_p(x.data_ptr()), x.shape[0], C.c_void_p(Vt.data_ptr()) if Vt is not None else None, dv, C.byref(out)))
+        return out.as_dict()
+
+    def _bind_monitor(self, mixture, x, every, V, dv, capacity):
+        if x is None or every <= 0:
+            return self.clear_monitor()
+        x, Vt, dv = self._obs_args(x, V, dv, "mon")
+        self._chk(self._obs_entry(mixture, "bind_monitor")(self._h, C.c_void_p(x.data_ptr()), x.shape[0],
+                                                           C.c_void_p(Vt.data_ptr()) if Vt is not None else None, dv, int(every), int(capacity)))
+        self._mon_cap = int(capacity) if capacity > 0 else 4096
+
+    def _read_monitor_raw(self, first, count, mixture=False):
+        avail = self.monitor_available()
+        if count is None:                                   # everything from `first` on that the ring still holds
+            first = max(int(first), avail - getattr(self, "_mon_cap", 4096), 0)
+            count = max(avail - first, 0)
+        arr = (self._OBS_KINDS[mixture]["record"] * max(int(count), 1))()
+        if count > 0:
+            self._chk(self._obs_entry(mixture, "read_monitor")(self._h, int(first), int(count), arr, None))
+        return arr, int(count)
+
+    def _read_monitor(self, mixture, first, count):
+        arr, count = self._read_monitor_raw(first, count, mixture)
+        return [arr[i].as_dict() for i in range(count)]
+
+    def _read_monitor_array(self, mixture, first, count) -> np.ndarray:
+        arr, count = self._read_monitor_raw(first, count, mixture)
+        width = len(self.MIXTURE_OBSERVABLE_FIELDS if mixture else self.OBSERVABLE_FIELDS)
+        return np.frombuffer(arr, dtype=np.float64).reshape(-1, width)[:count].copy()
+
+    def _bind_keeper(self, mixture, metric, min_delta, patience):
+        if metric not in self.KEEP_METRICS:
+            raise ValueError(f"metric: one of {sorted(self.KEEP_METRICS)}")
+        self._chk(self._obs_entry(mixture, "bind_keeper")(self._h, self.KEEP_METRICS[metric], float(min_delta), int(patience)))
+
     def observables(self, x=None, V=None, dv=None) -> dict:
         """E, mu, <L_z>, norm, moments, peak density and residual of the normalised state on the points x (None: the bound collocation
         points with their bound potential); dv: quadrature weight (None: cfg.dx).  What tools/accuracy_cfg4.py:state_numbers used to
         form on the host from forward_jets."""
-        out = capi.gpe_observables()
-        if x is None:
-            self._chk(self.lib.gpe_observables(self._h, None, 0, None, float(self.cfg.dx if dv is None else dv), C.byref(out)))
-        else:
-            x, Vt, dv = self._obs_args(x, V, dv, "obs")
-            self._chk(self.lib.gpe_observables(self._h, C.c_void_p(x.data_ptr()), x.shape[0],
-                                               C.c_void_p(Vt.data_ptr()) if Vt is not None else None, dv, C.byref(out)))
-        return out.as_dict()
+        return self._observables(False, x, V, dv)
 
     def bind_monitor(self, x, every: int, V=None, dv=None, capacity: int = 0):
         """Held-out monitor: after every `every`-th step enqueued by step() / run() the observables on x are appended to a device ring
         (capacity 0: 4096 records) with no host synchronisation; read them with read_monitor()."""
-        if x is None or every <= 0:
-            return self.clear_monitor()
-        x, Vt, dv = self._obs_args(x, V, dv, "mon")
-        self._chk(self.lib.gpe_bind_monitor(self._h, C.c_void_p(x.data_ptr()), x.shape[0],
-                                            C.c_void_p(Vt.data_ptr()) if Vt is not None else None, dv, int(every), int(capacity)))
-        self._mon_cap = int(capacity) if capacity > 0 else 4096
+        return self._bind_monitor(False, x, every, V, dv, capacity)
 
     def clear_monitor(self):
         self._chk(self.lib.gpe_bind_monitor(self._h, None, 0, None, 0.0, 0, 0))
@@ -678,30 +716,16 @@ class Engine:
     def monitor_available(self) -> int:
         """Records appended since bind_monitor / bind_mixture_monitor (synchronises); the ring keeps the newest `capacity` of them."""
         n = C.c_int64()
-        read = self.lib.gpe_mixture_monitor_read if self.cfg.mixture else self.lib.gpe_read_monitor
-        self._chk(read(self._h, 0, 0, None, C.byref(n)))
+        self._chk(self._obs_entry(self.cfg.mixture, "read_monitor")(self._h, 0, 0, None, C.byref(n)))
         return int(n.value)
-
-    def _read_monitor_raw(self, first, count, mixture=False):
-        avail = self.monitor_available()
-        if count is None:                                   # everything from `first` on that the ring still holds
-            first = max(int(first), avail - getattr(self, "_mon_cap", 4096), 0)
-            count = max(avail - first, 0)
-        arr = ((capi.gpe_mixture_observables if mixture else capi.gpe_observables) * max(int(count), 1))()
-        if count > 0:
-            read = self.lib.gpe_mixture_monitor_read if mixture else self.lib.gpe_read_monitor
-            self._chk(read(self._h, int(first), int(count), arr, None))
-        return arr, int(count)
 
     def read_monitor(self, first: int = 0, count=None):
         """Monitor records [first, first+count) (0-based since bind_monitor; count None: up to the newest) as dicts."""
-        arr, count = self._read_monitor_raw(first, count)
-        return [arr[i].as_dict() for i in range(count)]
+        return self._read_monitor(False, first, count)
 
     def read_monitor_array(self, first: int = 0, count=None) -> np.ndarray:
         """The same records as one float64 array [count, len(OBSERVABLE_FIELDS)]."""
-        arr, count = self._read_monitor_raw(first, count)
-        return np.frombuffer(arr, dtype=np.float64).reshape(-1, len(self.OBSERVABLE_FIELDS))[:count].copy()
+        return self._read_monitor_array(False, first, count)
 
     # ---- keeper: the best parameters by the held-out monitor, kept on the device (include/gpe_hip.h: gpe_bind_keeper) -------------------
     KEEP_METRICS = {"res_rms": capi.KEEP_RES_RMS, "energy": capi.KEEP_ENERGY}
@@ -717,41 +741,25 @@ class Engine:
         norms, on the points x (None: the bound collocation points with their bound potential and weights); dv: quadrature weight
         (None: cfg.dx).  Two-entry lists per component, inter = [11, 22, 12], mean_x / var_x [component][axis].  What
         tools/accuracy_mixture.py:state used to form on the host."""
-        out = capi.gpe_mixture_observables()
-        if x is None:
-            self._chk(self.lib.gpe_mixture_observables(self._h, None, 0, None, float(self.cfg.dx if dv is None else dv), C.byref(out)))
-        else:
-            x, Vt, dv = self._obs_args(x, V, dv, "obs")
-            self._chk(self.lib.gpe_mixture_observables(self._h, C.c_void_p(x.data_ptr()), x.shape[0],
-                                                       C.c_void_p(Vt.data_ptr()) if Vt is not None else None, dv, C.byref(out)))
-        return out.as_dict()
+        return self._observables(True, x, V, dv)
 
     def bind_mixture_monitor(self, x, every: int, V=None, dv=None, capacity: int = 0):
         """bind_monitor for a mixture engine: after every `every`-th step enqueued by step() / run() the mixture observables on x are
         appended to a device ring (capacity 0: 4096 records) with no host synchronisation; read them with read_mixture_monitor()."""
-        if x is None or every <= 0:
-            return self.clear_monitor()
-        x, Vt, dv = self._obs_args(x, V, dv, "mon")
-        self._chk(self.lib.gpe_mixture_monitor(self._h, C.c_void_p(x.data_ptr()), x.shape[0],
-                                               C.c_void_p(Vt.data_ptr()) if Vt is not None else None, dv, int(every), int(capacity)))
-        self._mon_cap = int(capacity) if capacity > 0 else 4096
+        return self._bind_monitor(True, x, every, V, dv, capacity)
 
     def read_mixture_monitor(self, first: int = 0, count=None):
         """Mixture monitor records [first, first+count) (0-based since bind_mixture_monitor; count None: up to the newest) as dicts."""
-        arr, count = self._read_monitor_raw(first, count, mixture=True)
-        return [arr[i].as_dict() for i in range(count)]
+        return self._read_monitor(True, first, count)
 
     def read_mixture_monitor_array(self, first: int = 0, count=None) -> np.ndarray:
         """The same records as one float64 array [count, len(MIXTURE_OBSERVABLE_FIELDS)]."""
-        arr, count = self._read_monitor_raw(first, count, mixture=True)
-        return np.frombuffer(arr, dtype=np.float64).reshape(-1, len(self.MIXTURE_OBSERVABLE_FIELDS))[:count].copy()
+        return self._read_monitor_array(True, first, count)
 
     def bind_mixture_keeper(self, metric: str = "res_rms", min_delta: float = 0.0, patience: int = 0):
         """bind_keeper for a mixture engine: judges the mixture monitor's records by "res_rms" (res_rms_total) or "energy".  Needs
         bind_mixture_monitor first; keeper_state(), best_params(), best_record() (the mixture record) and restore_best() serve it."""
-        if metric not in self.KEEP_METRICS:
-            raise ValueError(f"metric: one of {sorted(self.KEEP_METRICS)}")
-        self._chk(self.lib.gpe_mixture_keeper(self._h, self.KEEP_METRICS[metric], float(min_delta), int(patience)))
+        self._bind_keeper(True, metric, min_delta, patience)
 
     def _keeper_read(self, *args):
         return (self.lib.gpe_mixture_keeper_read if self.cfg.mixture else self.lib.gpe_keeper_read)(self._h, *args)
@@ -761,9 +769,7 @@ class Engine:
         an improvement by more than min_delta, sets the parameters and the record aside -- on the device, with no host synchronisation.
         patience > 0: training stops (as by stop_tol / stop_patience) after that many records in a row without improvement.  Needs
         bind_monitor first; keeper.select restates the rule."""
-        if metric not in self.KEEP_METRICS:
-            raise ValueError(f"metric: one of {sorted(self.KEEP_METRICS)}")
-        self._chk(self.lib.gpe_bind_keeper(self._h, self.KEEP_METRICS[metric], float(min_delta), int(patience)))
+        self._bind_keeper(False, metric, min_delta, patience)
 
     def clear_keeper(self):
         self._chk(self.lib.gpe_bind_keeper(self._h, capi.KEEP_NONE, 0.0, 0))
