@@ -720,8 +720,10 @@ struct gpe_engine {
         bool on = false;
         LbfgsCfg cfg = {};
         int ld = 0, n_part = 0;
-        float *S = nullptr, *Y = nullptr, *g_prev = nullptr, *d = nullptr;      // rings [m][ld]; [P] each
-        double *part = nullptr, *SY = nullptr, *YY = nullptr, *ro = nullptr, *coef = nullptr;
+        struct Hist {                                                             // a new `history` (cfg.m) reallocates this alone, cleared
+            float *S = nullptr, *Y = nullptr, *g_prev = nullptr, *d = nullptr;    // rings [m][ld]; [ld] each
+            double *part = nullptr, *SY = nullptr, *YY = nullptr, *ro = nullptr, *coef = nullptr;
+        } h;
         LbfgsDev* st = nullptr;
         LsCfg ls = {};                                                            // strong-Wolfe line search (gpe_lbfgs_line_search); kind 0: none
         float* ls_buf = nullptr;                                                  // [4][ld]: three trial-gradient slots, theta0
@@ -1535,9 +1537,16 @@ static int lbfgs_reset(gpe_engine* e, bool theta_to_start = false) {
     return GPE_OK;
 }
 
+static void lbfgs_free_history(gpe_engine* e) {
+    gpe_engine::Lbfgs::Hist& h = e->lb.h;
+    void* ps[] = {h.S, h.Y, h.g_prev, h.d, h.part, h.SY, h.YY, h.ro, h.coef};
+    for (void* p : ps) if (p) (void)hipFree(p);
+    h = gpe_engine::Lbfgs::Hist();
+}
+
 static void lbfgs_free(gpe_engine* e) {
-    void* ps[] = {e->lb.S, e->lb.Y, e->lb.g_prev, e->lb.d, e->lb.part, e->lb.SY, e->lb.YY, e->lb.ro, e->lb.coef, e->lb.st, e->lb.ls_buf, e->lb.ls_part,
-                  e->lb.view_buf};
+    lbfgs_free_history(e);
+    void* ps[] = {e->lb.st, e->lb.ls_buf, e->lb.ls_part, e->lb.view_buf};
     for (void* p : ps) if (p) (void)hipFree(p);
     e->lb = gpe_engine::Lbfgs();
 }
@@ -3342,35 +3351,52 @@ int gpe_lbfgs_config(gpe_engine* e, double lr, int history, double tolerance_gra
     if (e->cfg.world_size > 1 || e->comm) FAIL(e, GPE_ERR_INVALID, "lbfgs_config: a data-parallel engine has no L-BFGS (the history is per rank)");
     if (!e->lb.st || e->lb.cfg.m != history) {
         HIPCHK(e, hipStreamSynchronize(e->stream));
-        const LsCfg ls = e->lb.ls;                    // the line search does not depend on `history`: it and its buffers stay
-        float* ls_buf = e->lb.ls_buf; double* ls_part = e->lb.ls_part;
-        const bool mon = e->lb.mon;                   // nor does gpe_lbfgs_monitor
-        float* view_buf = e->lb.view_buf;
-        e->lb.ls_buf = nullptr; e->lb.ls_part = nullptr; e->lb.view_buf = nullptr;
-        lbfgs_free(e);
-        e->lb.ls = ls; e->lb.ls_buf = ls_buf; e->lb.ls_part = ls_part;
-        e->lb.mon = mon; e->lb.view_buf = view_buf;
+        lbfgs_free_history(e);                        // the line search, gpe_lbfgs_monitor and their buffers do not depend on `history`
+        gpe_engine::Lbfgs::Hist& h = e->lb.h;
         const int m = history;
         e->lb.ld = (int)round_up(e->P, 64);
         e->lb.n_part = lbfgs_grid(e->P);
         int rc;
-        if ((rc = dev_alloc(e, nullptr, &e->lb.S, (size_t)m * e->lb.ld)) || (rc = dev_alloc(e, nullptr, &e->lb.Y, (size_t)m * e->lb.ld)) ||
-            (rc = dev_alloc(e, nullptr, &e->lb.g_prev, (size_t)e->lb.ld)) || (rc = dev_alloc(e, nullptr, &e->lb.d, (size_t)e->lb.ld)) ||
-            (rc = dev_alloc(e, nullptr, &e->lb.part, (size_t)e->lb.n_part * lbfgs_row(m))) ||
-            (rc = dev_alloc(e, nullptr, &e->lb.SY, (size_t)m * m)) || (rc = dev_alloc(e, nullptr, &e->lb.YY, (size_t)m * m)) ||
-            (rc = dev_alloc(e, nullptr, &e->lb.ro, (size_t)m)) || (rc = dev_alloc(e, nullptr, &e->lb.coef, (size_t)2 * m + 1)) ||
-            (rc = dev_alloc(e, nullptr, &e->lb.st, (size_t)1))) { lbfgs_free(e); return rc; }
+        if ((rc = dev_alloc(e, nullptr, &h.S, (size_t)m * e->lb.ld)) || (rc = dev_alloc(e, nullptr, &h.Y, (size_t)m * e->lb.ld)) ||
+            (rc = dev_alloc(e, nullptr, &h.g_prev, (size_t)e->lb.ld)) || (rc = dev_alloc(e, nullptr, &h.d, (size_t)e->lb.ld)) ||
+            (rc = dev_alloc(e, nullptr, &h.part, (size_t)e->lb.n_part * lbfgs_row(m))) ||
+            (rc = dev_alloc(e, nullptr, &h.SY, (size_t)m * m)) || (rc = dev_alloc(e, nullptr, &h.YY, (size_t)m * m)) ||
+            (rc = dev_alloc(e, nullptr, &h.ro, (size_t)m)) || (rc = dev_alloc(e, nullptr, &h.coef, (size_t)2 * m + 1)) ||
+            (!e->lb.st && (rc = dev_alloc(e, nullptr, &e->lb.st, (size_t)1)))) { lbfgs_free(e); return rc; }
     }
     e->lb.cfg = LbfgsCfg{lr, tolerance_grad, tolerance_change, stop_loss, history};
     e->lb.on = true;
     return lbfgs_reset(e);
 }
 
-static int lbfgs_refusals(gpe_engine* e, const char* who) {
+// Refuses an engine without L-BFGS; h: the state as the work enqueued so far leaves it, on the host (every reader synchronises here)
+static int lbfgs_state(gpe_engine* e, const char* who, LbfgsDev* h = nullptr) {
     if (!e->lb.on) FAIL(e, GPE_ERR_STATE, "%s: L-BFGS is not configured (gpe_lbfgs_config)", who);
+    if (!h) return GPE_OK;
+    HIPCHK(e, hipMemcpyAsync(h, e->lb.st, sizeof *h, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    return GPE_OK;
+}
+
+static int lbfgs_refusals(gpe_engine* e, const char* who) {
+    int rc;
+    if ((rc = lbfgs_state(e, who))) return rc;
     if (e->smp.bound()) FAIL(e, GPE_ERR_STATE, "%s: a sampler with every > 0 is bound, the objective would change under the history", who);
     if (e->comm) FAIL(e, GPE_ERR_STATE, "%s: the engine has a communicator, L-BFGS is single-rank", who);
     return GPE_OK;
+}
+
+// the iteration's three launches; LS: on the point the tick's decision accepted, if it accepted one (gpe_lbfgs.h)
+extern "C++" template <bool LS>
+static void launch_lbfgs_iteration(gpe_engine* e) {
+    const gpe_engine::Lbfgs& lb = e->lb;
+    const int m = lb.cfg.m;
+    hipLaunchKernelGGL(k_lbfgs_dots<LS>, dim3(lb.n_part), dim3(64), 0, e->stream, e->P, lb.ld, m, (const float*)e->grad, (const float*)lb.h.g_prev,
+                       (const float*)lb.h.d, (const float*)lb.h.S, (const float*)lb.h.Y, (const LbfgsDev*)lb.st, lb.h.part);
+    hipLaunchKernelGGL(k_lbfgs_coef<LS>, dim3(1), dim3(256), 0, e->stream, m, lb.n_part, lb.cfg, lb.st, (const double*)lb.h.part, lb.h.SY, lb.h.YY,
+                       lb.h.ro, lb.h.coef, (const gpe_scalars*)e->last);
+    hipLaunchKernelGGL(k_lbfgs_apply<LS>, dim3(cdiv(e->P, 256)), dim3(256), 0, e->stream, e->P, lb.ld, m, (const float*)e->grad, lb.h.g_prev, lb.h.d,
+                       lb.h.S, lb.h.Y, e->theta, (const LbfgsDev*)lb.st, (const double*)lb.h.coef);
 }
 
 int gpe_lbfgs_update(gpe_engine* e) {
@@ -3382,30 +3408,13 @@ int gpe_lbfgs_update(gpe_engine* e) {
     StepScope seq{e};               // the step ends here
     launch_update(e, e->grad, e->sums(), e->lsums(), mse ? 0.0 : bc_count(e), /*do_update=*/0, mse, nullptr);
     HIPCHK(e, hipGetLastError());
-    const int m = e->lb.cfg.m;
     if (e->lb.ls.kind) {                                // one tick: the same five launches whatever the decision is
-        hipLaunchKernelGGL(k_ls_dots, dim3(e->lb.n_part), dim3(64), 0, e->stream, e->P, e->lb.ld, (const float*)e->grad, (const float*)e->lb.d,
+        hipLaunchKernelGGL(k_ls_dots, dim3(e->lb.n_part), dim3(64), 0, e->stream, e->P, e->lb.ld, (const float*)e->grad, (const float*)e->lb.h.d,
                            (const LbfgsDev*)e->lb.st, e->lb.ls_part);
         hipLaunchKernelGGL(k_ls_decide, dim3(1), dim3(64), 0, e->stream, e->lb.n_part, e->lb.cfg, e->lb.ls, e->lb.st, (const double*)e->lb.ls_part,
                            (const gpe_scalars*)e->last);
-        hipLaunchKernelGGL(k_lbfgs_dots<true>, dim3(e->lb.n_part), dim3(64), 0, e->stream, e->P, e->lb.ld, m, (const float*)e->grad,
-                           (const float*)e->lb.g_prev, (const float*)e->lb.d, (const float*)e->lb.S, (const float*)e->lb.Y, (const LbfgsDev*)e->lb.st,
-                           e->lb.part);
-        hipLaunchKernelGGL(k_lbfgs_coef<true>, dim3(1), dim3(256), 0, e->stream, m, e->lb.n_part, e->lb.cfg, e->lb.st, (const double*)e->lb.part,
-                           e->lb.SY, e->lb.YY, e->lb.ro, e->lb.coef, (const gpe_scalars*)e->last);
-        hipLaunchKernelGGL(k_lbfgs_apply<true>, dim3(cdiv(e->P, 256)), dim3(256), 0, e->stream, e->P, e->lb.ld, m, (const float*)e->grad,
-                           e->lb.g_prev, e->lb.d, e->lb.S, e->lb.Y, e->theta, (const LbfgsDev*)e->lb.st, (const double*)e->lb.coef);
-        HIPCHK(e, hipGetLastError());
-        after_update(e);
-        e->packed_dirty = e->path == GPE_PATH_FUSED;
-        return GPE_OK;
-    }
-    hipLaunchKernelGGL(k_lbfgs_dots<false>, dim3(e->lb.n_part), dim3(64), 0, e->stream, e->P, e->lb.ld, m, (const float*)e->grad, (const float*)e->lb.g_prev,
-                       (const float*)e->lb.d, (const float*)e->lb.S, (const float*)e->lb.Y, (const LbfgsDev*)e->lb.st, e->lb.part);
-    hipLaunchKernelGGL(k_lbfgs_coef<false>, dim3(1), dim3(256), 0, e->stream, m, e->lb.n_part, e->lb.cfg, e->lb.st, (const double*)e->lb.part, e->lb.SY,
-                       e->lb.YY, e->lb.ro, e->lb.coef, (const gpe_scalars*)e->last);
-    hipLaunchKernelGGL(k_lbfgs_apply<false>, dim3(cdiv(e->P, 256)), dim3(256), 0, e->stream, e->P, e->lb.ld, m, (const float*)e->grad, e->lb.g_prev, e->lb.d,
-                       e->lb.S, e->lb.Y, e->theta, (const LbfgsDev*)e->lb.st, (const double*)e->lb.coef);
+        launch_lbfgs_iteration<true>(e);
+    } else launch_lbfgs_iteration<false>(e);
     HIPCHK(e, hipGetLastError());
     after_update(e);
     e->packed_dirty = e->path == GPE_PATH_FUSED;      // theta moved behind the record launch's repack: the next k_begin repacks
@@ -3446,11 +3455,9 @@ int gpe_lbfgs_run(gpe_engine* e, int64_t n_iters, int mse) {
 int gpe_lbfgs_monitor(gpe_engine* e, int on) {
     if (!e) return GPE_ERR_INVALID;
     if (on != 0 && on != 1) FAIL(e, GPE_ERR_INVALID, "lbfgs_monitor: on must be 0 or 1, got %d", on);
-    if (!e->lb.on) FAIL(e, GPE_ERR_STATE, "lbfgs_monitor: L-BFGS is not configured (gpe_lbfgs_config)");
-    if (on && !e->lb.view_buf) {
-        int rc;
-        if ((rc = dev_alloc(e, nullptr, &e->lb.view_buf, (size_t)e->lb.ld))) return rc;
-    }
+    int rc;
+    if ((rc = lbfgs_state(e, "lbfgs_monitor"))) return rc;
+    if (on && !e->lb.view_buf && (rc = dev_alloc(e, nullptr, &e->lb.view_buf, (size_t)e->lb.ld))) return rc;
     e->lb.mon = on != 0;
     return GPE_OK;
 }
@@ -3459,25 +3466,19 @@ int gpe_lbfgs_point(gpe_engine* e, float* h_flat, size_t n) {
     if (!e) return GPE_ERR_INVALID;
     if (!h_flat) FAIL(e, GPE_ERR_INVALID, "lbfgs_point: no output array");
     if ((int64_t)n != e->P_user) FAIL(e, GPE_ERR_INVALID, "lbfgs_point: got %zu floats, model has %d", n, e->P_user);
-    if (!e->lb.on) FAIL(e, GPE_ERR_STATE, "lbfgs_point: L-BFGS is not configured (gpe_lbfgs_config)");
     LbfgsDev h;
-    HIPCHK(e, hipMemcpyAsync(&h, e->lb.st, sizeof h, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
+    if (int rc = lbfgs_state(e, "lbfgs_point", &h)) return rc;
     // the rule of k_lbfgs_view, on a copy of the state: this reader synchronises anyway, and it writes nothing on the device
-    const bool at_start = !h.frozen && h.ls.state != LS_IDLE && h.ls.theta0 != nullptr;
-    int rc = flat_from_device(e, at_start ? h.ls.theta0 : e->theta, h_flat);
-    if (rc) return rc;
+    if (int rc = flat_from_device(e, lbfgs_judged_at_start(&h) ? h.ls.theta0 : e->theta, h_flat)) return rc;
     HIPCHK(e, hipStreamSynchronize(e->stream));
     return GPE_OK;
 }
 
 int gpe_lbfgs_read(gpe_engine* e, double out[16]) {
     if (!e || !out) return GPE_ERR_INVALID;
-    if (!e->lb.on) FAIL(e, GPE_ERR_STATE, "lbfgs_read: L-BFGS is not configured (gpe_lbfgs_config)");
     static_assert(LBR_FIELDS == 16, "gpe_lbfgs_read record");
     LbfgsDev h;
-    HIPCHK(e, hipMemcpyAsync(&h, e->lb.st, sizeof h, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
+    if (int rc = lbfgs_state(e, "lbfgs_read", &h)) return rc;
     memcpy(out, h.rec, sizeof h.rec);
     // the state as it stands (a reset clears it; the record fields of the last iteration would be stale then)
     out[LBR_N_ITER] = (double)h.n_iter; out[LBR_COUNT] = h.count; out[LBR_FROZEN] = h.frozen; out[LBR_HEAD] = h.head; out[LBR_H_DIAG] = h.H_diag;
@@ -3491,26 +3492,24 @@ int gpe_lbfgs_line_search(gpe_engine* e, int kind, double c1, double c2, int max
     if (!(__builtin_isfinite(c1) && __builtin_isfinite(c2))) FAIL(e, GPE_ERR_INVALID, "lbfgs_line_search: c1 and c2 must be finite");
     if (!(0.0 < c1 && c1 < c2 && c2 < 1.0)) FAIL(e, GPE_ERR_INVALID, "lbfgs_line_search: 0 < c1 < c2 < 1 required, got %g, %g", c1, c2);
     if (max_ls < 1 || max_ls > 64) FAIL(e, GPE_ERR_INVALID, "lbfgs_line_search: max_ls must be in [1,64], got %d", max_ls);
-    if (!e->lb.on) FAIL(e, GPE_ERR_STATE, "lbfgs_line_search: L-BFGS is not configured (gpe_lbfgs_config)");
+    int rc;
+    if ((rc = lbfgs_state(e, "lbfgs_line_search"))) return rc;
     HIPCHK(e, hipStreamSynchronize(e->stream));
     if (kind && !e->lb.ls_buf) {
-        int rc;
         if ((rc = dev_alloc(e, nullptr, &e->lb.ls_buf, (size_t)(LS_SLOTS + 1) * e->lb.ld)) ||
             (rc = dev_alloc(e, nullptr, &e->lb.ls_part, (size_t)e->lb.n_part * LSD_COUNT))) return rc;
     }
     // a search of the previous setting may be running: theta goes back to its start point before the state is cleared
-    int rc = lbfgs_reset(e, /*theta_to_start=*/true);
+    rc = lbfgs_reset(e, /*theta_to_start=*/true);
     e->lb.ls = LsCfg{kind, c1, c2, max_ls};
     return rc;
 }
 
 int gpe_lbfgs_ls_read(gpe_engine* e, double out[24]) {
     if (!e || !out) return GPE_ERR_INVALID;
-    if (!e->lb.on) FAIL(e, GPE_ERR_STATE, "lbfgs_ls_read: L-BFGS is not configured (gpe_lbfgs_config)");
     static_assert(LSR_FIELDS == 24, "gpe_lbfgs_ls_read record");
     LbfgsDev h;
-    HIPCHK(e, hipMemcpyAsync(&h, e->lb.st, sizeof h, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
+    if (int rc = lbfgs_state(e, "lbfgs_ls_read", &h)) return rc;
     const LsDev& ls = h.ls;
     out[LSR_PHASE] = ls.did; out[LSR_LS_ITER] = ls.ls_iter; out[LSR_LS_EVALS] = ls.ls_evals; out[LSR_EVALS_TOTAL] = (double)ls.evals_total;
     out[LSR_T] = ls.t; out[LSR_T_PREV] = ls.state == LS_BRACKET ? ls.b[0] : 0.0;
@@ -3525,20 +3524,18 @@ int gpe_lbfgs_ls_read(gpe_engine* e, double out[24]) {
 
 int gpe_lbfgs_history(gpe_engine* e, float* h_S, float* h_Y, float* h_g_prev, float* h_d, size_t n, int* count) {
     if (!e) return GPE_ERR_INVALID;
-    if (!e->lb.on) FAIL(e, GPE_ERR_STATE, "lbfgs_history: L-BFGS is not configured (gpe_lbfgs_config)");
-    if ((int64_t)n != e->P_user) FAIL(e, GPE_ERR_INVALID, "lbfgs_history: rows of %zu floats, model has %d", n, e->P_user);
     LbfgsDev h;
-    HIPCHK(e, hipMemcpyAsync(&h, e->lb.st, sizeof h, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-    const int m = e->lb.cfg.m;
     int rc;
+    if ((rc = lbfgs_state(e, "lbfgs_history", &h))) return rc;
+    if ((int64_t)n != e->P_user) FAIL(e, GPE_ERR_INVALID, "lbfgs_history: rows of %zu floats, model has %d", n, e->P_user);
+    const int m = e->lb.cfg.m;
     for (int a = 0; a < h.count; ++a) {               // age order: row 0 is the oldest pair
         const int j = (h.head - h.count + a + m) % m;
-        if (h_S && (rc = flat_from_device(e, e->lb.S + (size_t)j * e->lb.ld, h_S + (size_t)a * n))) return rc;
-        if (h_Y && (rc = flat_from_device(e, e->lb.Y + (size_t)j * e->lb.ld, h_Y + (size_t)a * n))) return rc;
+        if (h_S && (rc = flat_from_device(e, e->lb.h.S + (size_t)j * e->lb.ld, h_S + (size_t)a * n))) return rc;
+        if (h_Y && (rc = flat_from_device(e, e->lb.h.Y + (size_t)j * e->lb.ld, h_Y + (size_t)a * n))) return rc;
     }
-    if (h_g_prev && (rc = flat_from_device(e, e->lb.g_prev, h_g_prev))) return rc;
-    if (h_d && (rc = flat_from_device(e, e->lb.d, h_d))) return rc;
+    if (h_g_prev && (rc = flat_from_device(e, e->lb.h.g_prev, h_g_prev))) return rc;
+    if (h_d && (rc = flat_from_device(e, e->lb.h.d, h_d))) return rc;
     HIPCHK(e, hipStreamSynchronize(e->stream));
     if (count) *count = h.count;
     return GPE_OK;

@@ -1,5 +1,6 @@
 """Flat float64 restatement of torch.optim.LBFGS with line_search_fn = "strong_wolfe": the reference of the device-resident line search
-(csrc/gpe_lbfgs.h: k_ls_dots, k_ls_decide and the LS instantiations of the three iteration kernels).
+(csrc/gpe_lbfgs_rules.h: ls_decide, ls_rearm; csrc/gpe_lbfgs.h: k_ls_dots, k_ls_decide and the LS instantiations of the three iteration
+kernels).
 
 torch's `_strong_wolfe` is a loop that calls the objective where it needs a value.  Here it is a state machine that CONSUMES one evaluation
 per call: tick(loss, g) takes the evaluation at the current point self.theta (= theta0 + t d, or theta0 itself when no search is running)

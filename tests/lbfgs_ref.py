@@ -1,4 +1,5 @@
-"""Flat float64 restatement of torch.optim.LBFGS without a line search: the reference of the device-resident L-BFGS (csrc/gpe_lbfgs.h).
+"""Flat float64 restatement of torch.optim.LBFGS without a line search: the reference of the device-resident L-BFGS (csrc/gpe_lbfgs.h,
+its state and freeze rule in csrc/gpe_lbfgs_rules.h).
 
 torch's `opt.step(closure)` with max_iter = K evaluates the closure once per parameter update, in order.  Its `tolerance_change` and
 `max_iter` breaks only end an outer call: the next call re-evaluates at the same parameters and carries on with the state it kept.  The

@@ -1,5 +1,5 @@
-"""The strong-Wolfe line search of the device-resident L-BFGS (csrc/gpe_lbfgs.h: k_ls_dots, k_ls_decide and the LS instantiations of
-k_lbfgs_dots / k_lbfgs_coef / k_lbfgs_apply) against the flat float64 reference tests/lbfgs_ls_ref.py, which
+"""The strong-Wolfe line search of the device-resident L-BFGS (csrc/gpe_lbfgs_rules.h: ls_decide, ls_rearm; csrc/gpe_lbfgs.h: k_ls_dots,
+k_ls_decide and the LS instantiations of k_lbfgs_dots / k_lbfgs_coef / k_lbfgs_apply) against the flat float64 reference tests/lbfgs_ls_ref.py, which
 tests/test_lbfgs_ls_reference_cpu.py holds to torch.optim.LBFGS(line_search_fn="strong_wolfe").
 
 Injection as in tests/test_gpu_lbfgs.py (its make_engine and inject): N = 256 points, gradient and loss written into exchange_grad between

@@ -1,5 +1,5 @@
 """The device-resident L-BFGS under the held-out monitor and the keeper (include/gpe_hip.h: gpe_lbfgs_monitor, gpe_lbfgs_point;
-csrc/gpe_lbfgs.h: k_lbfgs_view, k_lbfgs_unview): records are of the JUDGED POINT -- theta without a line search and in a frozen state,
+csrc/gpe_lbfgs.h: k_lbfgs_view, k_lbfgs_unview; csrc/gpe_lbfgs_rules.h: lbfgs_judged_at_start, lbfgs_freeze): records are of the JUDGED POINT -- theta without a line search and in a frozen state,
 the start point of the running search under strong Wolfe -- the run itself is not disturbed, and the keeper's patience freezes it with
 code 4.
 

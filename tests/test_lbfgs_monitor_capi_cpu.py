@@ -41,7 +41,8 @@ def test_a_null_engine_is_refused_and_no_switch_was_added():
     buf = (C.c_float * 4)()
     assert lib.gpe_lbfgs_monitor(None, 1) == capi.GPE_ERR_INVALID
     assert lib.gpe_lbfgs_point(None, buf, 4) == capi.GPE_ERR_INVALID
-    assert "getenv" not in open(os.path.join(CSRC, "gpe_lbfgs.h")).read()
+    for f in ("gpe_lbfgs.h", "gpe_lbfgs_rules.h"):
+        assert "getenv" not in open(os.path.join(CSRC, f)).read()
 
 
 def test_the_header_states_the_rule_and_the_code():
@@ -50,7 +51,7 @@ def test_the_header_states_the_rule_and_the_code():
     run = text[text.index(" * gpe_lbfgs_run:"):text.index(" * gpe_lbfgs_read:")]
     assert "gpe_lbfgs_monitor" in run and "start" in run and "trial" in run           # the judged point, stated where the run is
     assert re.search(r"4 the keeper", text[text.index(" * gpe_lbfgs_read:"):text.index(" * gpe_lbfgs_history:")])
-    assert re.search(r"LBFGS_FROZEN_KEEPER\s*=\s*4\b", open(os.path.join(CSRC, "gpe_lbfgs.h")).read())
+    assert re.search(r"LBFGS_FROZEN_KEEPER\s*=\s*4\b", open(os.path.join(CSRC, "gpe_lbfgs_rules.h")).read())
 
 
 def test_frozen_code_4_and_the_python_surface():

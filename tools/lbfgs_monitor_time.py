@@ -3,7 +3,7 @@
 evaluation does anyway -- next to the cost of one record in an Adam run of the same shape.
 
 [2,64,64,64,1], 65 536 training points, 3 001 held-out points, every = 10.  The same lbfgs_run with the flag off and on (monitor and keeper
-bound either way), HIP events on the engine's stream around the whole run, alternating, median of --reps; then gpe_run without and with
+bound either way), HIP events on the engine's stream around the whole run, alternating, median [min .. max] of --reps; then gpe_run without and with
 the monitor and keeper.  The difference of the medians times `every` is the cost of one record.
 
 usage: python tools/lbfgs_monitor_time.py [--ticks 300 --reps 9 --out profiles/lbfgs_monitor/tick_time.txt]"""
@@ -77,7 +77,8 @@ for ls in (None, "strong_wolfe"):
     st = eng.lbfgs_read()
     per_rec = (med(on) - med(off)) * a.every
     results[ls] = per_rec
-    say(f"lbfgs_run, line search {ls}: {med(off):.2f} us/tick flag off, {med(on):.2f} us/tick flag on -> {per_rec:.1f} us per monitor tick "
+    say(f"lbfgs_run, line search {ls}: {med(off):.2f} [{min(off):.2f} .. {max(off):.2f}] us/tick flag off, {med(on):.2f} [{min(on):.2f} .. {max(on):.2f}] us/tick flag on "
+        f"-> {per_rec:.1f} us per monitor tick "
         f"(view + chain + keeper + unview + the repack; {eng.monitor_available()} records in the last run, frozen {st['frozen']})")
     eng.close()
 

@@ -1,6 +1,6 @@
 """Time per L-BFGS tick with the strong-Wolfe line search beside the time per iteration without it, on the north-star network
 ([2,64,64,64,64,1], gamma 500, physics loss) at 4 096 and 65 536 collocation points, history 10 and 100.  Wall clock around gpe_lbfgs_run(50) and a
-synchronisation (the launches are enqueued back to back), medians of 7 interleaved blocks after the rings have filled.  Writes the table to stdout; profiles/lbfgs_ls/step_time.txt keeps it.
+synchronisation (the launches are enqueued back to back), medians [min .. max] of 7 interleaved blocks after the rings have filled.  Writes the table to stdout; profiles/lbfgs_ls/step_time.txt keeps it.
 
     python tools/lbfgs_tick_time.py"""
 import os
@@ -49,7 +49,8 @@ def main():
                     times[ls].append(block(e))
             rec, lsr = engs[True].lbfgs_read(), engs[True].lbfgs_ls_read()
             plain, tick = np.median(times[False]), np.median(times[True])
-            print(f"points {n:6d}  history {history:3d}  iteration without line search {plain:8.1f} us   tick with strong Wolfe {tick:8.1f} us   "
+            print(f"points {n:6d}  history {history:3d}  iteration without line search {plain:8.1f} us [{min(times[False]):.1f} .. {max(times[False]):.1f}]   "
+                  f"tick with strong Wolfe {tick:8.1f} us [{min(times[True]):.1f} .. {max(times[True]):.1f}]   "
                   f"({tick - plain:+.1f} us, {100 * (tick / plain - 1):+.1f} %)   accepted {lsr['accepted']} of {lsr['evals_total']} evaluations, "
                   f"pairs held {rec['count']}, frozen {rec['frozen']} / {engs[False].lbfgs_read()['frozen']}")
             for e in engs.values():
