@@ -38,6 +38,7 @@ typedef enum { ncclFloat = 7, ncclDouble = 8 } ncclDataType_t;
 #include "gpe_fused.h"
 #include "gpe_wide_api.h"
 #include "gpe_env.h"
+#include "gpe_dispatch.h"
 #include "gpe_lbfgs.h"
 
 static thread_local std::string g_create_error;
@@ -812,47 +813,33 @@ static int setup_batch(gpe_engine* e, Batch& b, const float* x, int64_t n, int C
 }
 
 // ---- MLP forward / backward dispatch ---------------------------------------------------------------
-// (C, E) pairs that exist: value only (1,0); 1D (3,1); Laplacian-channel training batches 2D (4,1), 3D (5,1); full diagonal
-// second derivatives for gpe_forward_jets 2D (5,2), 3D (7,3) -- forward kernels only.
-#define CE_CASE(Cc, Ee, ...) case (Cc) * 10 + (Ee): { constexpr int CC = Cc; constexpr int EE = Ee; __VA_ARGS__; } break;
-#ifdef GPE_FAST_BUILD    // kernel-tuning builds (tools/build_variant.sh): only what the 2D n_out = 1, H = 64 workloads launch
-#define DISPATCH_TRAIN(bb, ...)                                        \
-    switch ((bb).C * 10 + (bb).E) {                                    \
-        CE_CASE(1, 0, __VA_ARGS__) CE_CASE(4, 1, __VA_ARGS__) CE_CASE(5, 1, __VA_ARGS__)         \
-        default: FAIL(e, GPE_ERR_INVALID, "fast build: channels (%d,%d) not compiled", (bb).C, (bb).E); \
-    }
-#define DISPATCH_FWD(bb, ...) DISPATCH_TRAIN(bb, __VA_ARGS__)
+// gpe_dispatch.h holds the table: the (C, E) pairs that exist, the n_out values, and each fused kernel form with its template ranges.
+// Every launcher below picks its template arguments through it, one statement per kernel form; raise_lds_limits walks the same ranges.
+#ifdef GPE_FAST_BUILD    // kernel-tuning builds (tools/build_variant.sh): only what the 2D / 3D n_out = 1, H = 64 workloads launch
+#define BAD_CE "fast build: channels (%d,%d) not compiled"
 #else
-#define DISPATCH_TRAIN(bb, ...)                                        \
-    switch ((bb).C * 10 + (bb).E) {                                    \
-        CE_CASE(1, 0, __VA_ARGS__) CE_CASE(3, 1, __VA_ARGS__) CE_CASE(4, 1, __VA_ARGS__) CE_CASE(5, 1, __VA_ARGS__) \
-        default: FAIL(e, GPE_ERR_INVALID, "bad channel pair (%d,%d)", (bb).C, (bb).E); \
-    }
-#define DISPATCH_FWD(bb, ...)                                          \
-    switch ((bb).C * 10 + (bb).E) {                                    \
-        CE_CASE(1, 0, __VA_ARGS__) CE_CASE(3, 1, __VA_ARGS__) CE_CASE(4, 1, __VA_ARGS__) CE_CASE(5, 1, __VA_ARGS__) \
-        CE_CASE(5, 2, __VA_ARGS__) CE_CASE(7, 3, __VA_ARGS__)          \
-        default: FAIL(e, GPE_ERR_INVALID, "bad channel pair (%d,%d)", (bb).C, (bb).E); \
-    }
+#define BAD_CE "bad channel pair (%d,%d)"
 #endif
-
+// f(CC, EE) for the batch's channel pair out of `list`, or the error
+template <class L, class F>
+static int launch_ce(gpe_engine* e, const Batch& b, L list, F&& f) {
+    if (!pick_ce(list, b.C, b.E, f)) FAIL(e, GPE_ERR_INVALID, BAD_CE, b.C, b.E);
+    return GPE_OK;
+}
+// f(HH, CC, EE) for the fused kernels: H = 32 / 64 with the pairs of L, H = 128 with those of L128
+template <class L, class L128, class F>
+static int launch_hce(gpe_engine* e, const Batch& b, F&& f) {
 #ifdef GPE_FAST_BUILD
-#define F_LAUNCH(KERNEL, HH, CC, EE, WL, GRID, BLOCK, LDS, ...) \
-    hipLaunchKernelGGL((KERNEL<HH, CC, EE, 1, WL>), dim3(GRID), dim3(BLOCK), LDS, e->stream, __VA_ARGS__)
-#define B_LAUNCH(HH, CC, EE, WL, NH, GRID, BLOCK, LDS, ...) \
-    hipLaunchKernelGGL((f_backward<HH, CC, EE, 1, WL, NH>), dim3(GRID), dim3(BLOCK), LDS, e->stream, __VA_ARGS__)
+    if (e->H != 64 || e->nd.n_out != 1) FAIL(e, GPE_ERR_INVALID, "fast build: only H = 64, n_out = 1 compiled");
 #else
-#define F_LAUNCH(KERNEL, HH, CC, EE, WL, GRID, BLOCK, LDS, ...)                                                    \
-    do {                                                                                                         \
-        if (e->nd.n_out == 1) hipLaunchKernelGGL((KERNEL<HH, CC, EE, 1, WL>), dim3(GRID), dim3(BLOCK), LDS, e->stream, __VA_ARGS__); \
-        else                  hipLaunchKernelGGL((KERNEL<HH, CC, EE, 2, WL>), dim3(GRID), dim3(BLOCK), LDS, e->stream, __VA_ARGS__); \
-    } while (0)
-#define B_LAUNCH(HH, CC, EE, WL, NH, GRID, BLOCK, LDS, ...)                                                        \
-    do {                                                                                                         \
-        if (e->nd.n_out == 1) hipLaunchKernelGGL((f_backward<HH, CC, EE, 1, WL, NH>), dim3(GRID), dim3(BLOCK), LDS, e->stream, __VA_ARGS__); \
-        else                  hipLaunchKernelGGL((f_backward<HH, CC, EE, 2, WL, NH>), dim3(GRID), dim3(BLOCK), LDS, e->stream, __VA_ARGS__); \
-    } while (0)
+    if (e->H == 128) {
+        if (!pick_ce(L128{}, b.C, b.E, [&](auto CC, auto EE) { f(int_c<128>{}, CC, EE); })) FAIL(e, GPE_ERR_INVALID, BAD_CE " for H = 128", b.C, b.E);
+        return GPE_OK;
+    }
+    if (e->H == 32) return launch_ce(e, b, L{}, [&](auto CC, auto EE) { f(int_c<32>{}, CC, EE); });
 #endif
+    return launch_ce(e, b, L{}, [&](auto CC, auto EE) { f(int_c<64>{}, CC, EE); });
+}
 
 static size_t fused_w_bytes(gpe_engine* e) { return (size_t)(e->nd.n_lin - 2) * e->H * e->H * sizeof(float); }
 static size_t fused_small_bytes(gpe_engine* e) {       // = small_count() of gpe_fused.h, rounded up to 16 bytes (NOT read_switches' smallb, on purpose)
@@ -870,9 +857,22 @@ static bool coop_only(gpe_engine* e) { return coop_shape(e) && e->H <= 64 && e->
 static bool fwd_coop(gpe_engine* e, const Batch& b) {
     if (coop_only(e)) return true;
     if (!coop_shape(e) || e->coop == 0) return false;
-    if (e->H == 128) return e->coop_fwd128;           // wide layers: the cooperative forward wins at every size (measured)
+    if (e->H == 128) return e->coop_fwd128 && b.C <= 4;      // wide layers: the cooperative forward wins at every size (measured); gpe_forward_jets' (5,2) has no instance
     if (e->nd.n_lin - 2 > 3) return true;             // four / five maps at H <= 64: the cooperative kernels take them whenever allowed
     return (b.n + 15) / 16 <= e->coop_fwd_max_tiles;
+}
+// workgroups of the forward launch of batch b: cooperative (a workgroup per tile, two per CU) or per wave tile (four tiles per workgroup);
+// H = 128 runs one workgroup per CU either way.  The head leaves one triple per workgroup of this launch (step_begin).
+static unsigned fwd_grid(gpe_engine* e, const Batch& b, bool coop) {
+    return fused_grid(e, b.n, coop ? 1 : 4, e->H == 128 ? 1 : (coop ? 2 : e->fwd_wg_per_cu));
+}
+// large batches on two workgroups per CU: uneven split of each CU's tiles between its two workgroups, / 1024 (0: even).  Forward
+// (GPE_FWD_SHARE; per wave, hence the 4) and pipelined reverse (GPE_PIPE_SHARE); gpe_active_kernels reports what these return.
+static int fwd_tile_share(gpe_engine* e, const Batch& b, unsigned grid) {
+    return (e->fwd_share > 0 && grid == (unsigned)(2 * e->num_cu) && (b.n + 15) / 16 >= 4 * e->share_min_tiles * (int64_t)grid) ? e->fwd_share : 0;
+}
+static int pipe_tile_share(gpe_engine* e, const Batch& b, unsigned grid) {
+    return (e->pipe_share > 0 && grid == (unsigned)(2 * e->num_cu) && (b.n + 15) / 16 >= e->share_min_tiles * (int64_t)grid) ? e->pipe_share : 0;
 }
 #define HEAD_SLOTS 512
 static bool seed_in_reverse(gpe_engine* e);
@@ -898,115 +898,55 @@ static bool head_fusable_tile(gpe_engine* e) {
 }
 static bool head_fusable(gpe_engine* e) { return head_fusable_coop(e) || head_fusable_tile(e); }
 // head: the kernel runs the head too and leaves one triple per workgroup in head_slots (the step's forward pass of the main batch only)
-template <int HH, int CC, int EE, int NO>
-static void launch_fcoop_no(gpe_engine* e, Batch& b, unsigned grid, size_t lds, int store, const FwdWeights& W, bool head) {
-#define CARGS e->nd, W.theta, W.Wpk, b.pts, b.stored, b.O, b.n, b.ld, store
-    if constexpr (HH <= 64 && NO == 1 && CC >= 3) {
-        if (head) {
-            const HeadArgs ha{e->ph, e->base_norm, b.V, (const float* const*)e->orth_dev, e->bc_target, b.u, b.Hu, b.Ob, e->n_pde, b.ld, e->head_slots};
-            const size_t ldsh = lds + (size_t)CC * 16 * sizeof(float);
-            if (e->cfg.net_kind == GPE_NET_RESIDUAL) {
-                if (e->nd.n_lin - 2 == 2) hipLaunchKernelGGL((f_forward_coop<HH, CC, EE, 1, 2, true, true>), dim3(grid), dim3(HH * 4), ldsh, e->stream, CARGS, ha);
-                else hipLaunchKernelGGL((f_forward_coop<HH, CC, EE, 1, 4, true, true>), dim3(grid), dim3(HH * 4), ldsh, e->stream, CARGS, ha);
-                return;
-            }
-            switch (e->nd.n_lin - 2) {
-                case 1: hipLaunchKernelGGL((f_forward_coop<HH, CC, EE, 1, 1, true>), dim3(grid), dim3(HH * 4), ldsh, e->stream, CARGS, ha); break;
-                case 2: hipLaunchKernelGGL((f_forward_coop<HH, CC, EE, 1, 2, true>), dim3(grid), dim3(HH * 4), ldsh, e->stream, CARGS, ha); break;
-                case 3: hipLaunchKernelGGL((f_forward_coop<HH, CC, EE, 1, 3, true>), dim3(grid), dim3(HH * 4), ldsh, e->stream, CARGS, ha); break;
-                case 4: hipLaunchKernelGGL((f_forward_coop<HH, CC, EE, 1, 4, true>), dim3(grid), dim3(HH * 4), ldsh, e->stream, CARGS, ha); break;
-                default: hipLaunchKernelGGL((f_forward_coop<HH, CC, EE, 1, 5, true>), dim3(grid), dim3(HH * 4), ldsh, e->stream, CARGS, ha); break;
-            }
-            return;
-        }
-    }
-#undef CARGS
-    const HeadArgs nohead{};
-#define CARGS e->nd, W.theta, W.Wpk, b.pts, b.stored, b.O, b.n, b.ld, store, nohead
-    if constexpr (HH <= 64 && NO == 1) {
-        if (e->cfg.net_kind == GPE_NET_RESIDUAL) {        // one or two residual blocks (checked at gpe_create)
-            if (e->nd.n_lin - 2 == 2) hipLaunchKernelGGL((f_forward_coop<HH, CC, EE, 1, 2, false, true>), dim3(grid), dim3(HH * 4), lds, e->stream, CARGS);
-            else hipLaunchKernelGGL((f_forward_coop<HH, CC, EE, 1, 4, false, true>), dim3(grid), dim3(HH * 4), lds, e->stream, CARGS);
-            return;
-        }
-    }
-    switch (e->nd.n_lin - 2) {
-        case 1: hipLaunchKernelGGL((f_forward_coop<HH, CC, EE, NO, 1>), dim3(grid), dim3(HH * 4), lds, e->stream, CARGS); break;
-        case 2: hipLaunchKernelGGL((f_forward_coop<HH, CC, EE, NO, 2>), dim3(grid), dim3(HH * 4), lds, e->stream, CARGS); break;
-        case 3: hipLaunchKernelGGL((f_forward_coop<HH, CC, EE, NO, 3>), dim3(grid), dim3(HH * 4), lds, e->stream, CARGS); break;
-        case 4:
-            if constexpr (HH == 128 || NO == 1)
-                hipLaunchKernelGGL((f_forward_coop<HH, CC, EE, NO, 4>), dim3(grid), dim3(HH * 4), lds, e->stream, CARGS);
-            break;
-        default:
-            if constexpr (HH == 128 || NO == 1)
-                hipLaunchKernelGGL((f_forward_coop<HH, CC, EE, NO, 5>), dim3(grid), dim3(HH * 4), lds, e->stream, CARGS);
-            break;
-    }
-#undef CARGS
+static HeadArgs head_args(gpe_engine* e, const Batch& b) {
+    return HeadArgs{e->ph, e->base_norm, b.V, (const float* const*)e->orth_dev, e->bc_target, b.u, b.Hu, b.Ob, e->n_pde, b.ld, e->head_slots};
 }
 template <int HH, int CC, int EE>
-static void launch_f_forward(gpe_engine* e, Batch& b, unsigned grid, int store, const FwdWeights& W, bool head) {
-    if constexpr (HH <= 64 || (HH == 128 && CC <= 4)) {
-        if (fwd_coop(e, b)) {
-            const int NT = HH / 16;
-            const size_t lds = fused_small_bytes(e) + ((size_t)2 * CC * NT * 256 + (size_t)NT * e->nd.n_out * CC * 16) * sizeof(float);
-            const unsigned g = fused_grid(e, b.n, 1, HH == 128 ? 1 : 2);
-#ifdef GPE_FAST_BUILD
-            launch_fcoop_no<HH, CC, EE, 1>(e, b, g, lds, store, W, head);
-#else
-            if (e->nd.n_out == 1) launch_fcoop_no<HH, CC, EE, 1>(e, b, g, lds, store, W, head);
-            else launch_fcoop_no<HH, CC, EE, 2>(e, b, g, lds, store, W, head);
-#endif
-            return;
-        }
-    }
-    // large batches on two workgroups per CU: uneven split of each CU's tiles between its two workgroups (GPE_FWD_SHARE, / 1024)
-    const int fshare = (e->fwd_share > 0 && grid == (unsigned)(2 * e->num_cu) && (b.n + 15) / 16 >= 4 * e->share_min_tiles * (int64_t)grid) ? e->fwd_share : 0;
-    const HeadArgs nohead{};
-    if constexpr (HH > 64) {
-        F_LAUNCH(f_forward, HH, CC, EE, false, grid, 256, fused_fwd_lds(e, false), e->nd, W.theta, W.Wpk, b.pts, b.stored, b.O, b.n, b.ld, store, fshare, nohead);
-        return;
-    }
-    if constexpr (HH <= 64) {
-        if (e->fwd_b6 && staged_batch(e, b)) {
+static void launch_f_forward_coop(gpe_engine* e, Batch& b, int store, const FwdWeights& W, bool head) {
+    constexpr int NT = HH / 16;
+    const int maps = e->nd.n_lin - 2;
+    pick_n_out(e->nd.n_out, [&](auto no) {
+        constexpr int NO = decltype(no)::value;
+        const bool hd = head && head_form(HH, CC, NO), res = e->cfg.net_kind == GPE_NET_RESIDUAL && HH <= 64 && NO == 1;
+        const HeadArgs ha = hd ? head_args(e, b) : HeadArgs{};
+        const size_t lds = fused_small_bytes(e) + ((size_t)2 * CC * NT * 256 + (size_t)NT * e->nd.n_out * CC * 16 + (hd ? CC * 16 : 0)) * sizeof(float);
+        // one or two residual blocks (checked at gpe_create) are two or four maps
+        pick_int<1, 5>(res ? (maps == 2 ? 2 : 4) : maps, [&](auto nh) { pick_int<0, 1>(hd, [&](auto h) { pick_int<0, 1>(res, [&](auto r) {
+            constexpr int NH = decltype(nh)::value;
+            constexpr bool HEAD = decltype(h)::value, RES = decltype(r)::value;
+            if constexpr (coop_form(HH, NO, NH, RES) && (!HEAD || head_form(HH, CC, NO)))
+                hipLaunchKernelGGL((f_forward_coop<HH, CC, EE, NO, NH, HEAD, RES>), dim3(fwd_grid(e, b, true)), dim3(HH * 4), lds, e->stream,
+                                   e->nd, W.theta, W.Wpk, b.pts, b.stored, b.O, b.n, b.ld, store, ha);
+        }); }); });
+    });
+}
+template <int HH, int CC, int EE>
+static void launch_f_forward(gpe_engine* e, Batch& b, int store, const FwdWeights& W, bool head) {
+    if constexpr (HH <= 64 || CC <= 4) if (fwd_coop(e, b)) return launch_f_forward_coop<HH, CC, EE>(e, b, store, W, head);
+    const unsigned grid = fwd_grid(e, b, false);
+    const bool staged = HH <= 64 && staged_batch(e, b);
+    pick_n_out(e->nd.n_out, [&](auto no) {
+        constexpr int NO = decltype(no)::value;
+        if (staged && e->fwd_b6) {
             // weights (three bf16 pieces, 6 bytes each) in LDS when two workgroups per CU still fit
             const size_t w6 = (size_t)(e->nd.n_lin - 2) * HH * HH * 6;
-            const bool wl = 2 * (fused_small_bytes(e) + w6) <= (size_t)160 * 1024;
-            const size_t lds6 = fused_small_bytes(e) + (wl ? w6 : 0);
-#define B6ARGS e->nd, W.theta, W.WpkT, b.pts, b.stored, b.O, b.n, b.ld, store
-#ifdef GPE_FAST_BUILD
-            if (wl) hipLaunchKernelGGL((f_forward_b6<HH, CC, EE, 1, true>), dim3(grid), dim3(256), lds6, e->stream, B6ARGS);
-            else hipLaunchKernelGGL((f_forward_b6<HH, CC, EE, 1, false>), dim3(grid), dim3(256), lds6, e->stream, B6ARGS);
-#else
-            if (e->nd.n_out == 1) {
-                if (wl) hipLaunchKernelGGL((f_forward_b6<HH, CC, EE, 1, true>), dim3(grid), dim3(256), lds6, e->stream, B6ARGS);
-                else hipLaunchKernelGGL((f_forward_b6<HH, CC, EE, 1, false>), dim3(grid), dim3(256), lds6, e->stream, B6ARGS);
-            } else {
-                if (wl) hipLaunchKernelGGL((f_forward_b6<HH, CC, EE, 2, true>), dim3(grid), dim3(256), lds6, e->stream, B6ARGS);
-                else hipLaunchKernelGGL((f_forward_b6<HH, CC, EE, 2, false>), dim3(grid), dim3(256), lds6, e->stream, B6ARGS);
-            }
-#endif
-#undef B6ARGS
+            pick_int<0, 1>(2 * (fused_small_bytes(e) + w6) <= (size_t)160 * 1024, [&](auto w) {
+                constexpr bool WL = decltype(w)::value;
+                if constexpr (HH <= 64)
+                    hipLaunchKernelGGL((f_forward_b6<HH, CC, EE, NO, WL>), dim3(grid), dim3(256), fused_small_bytes(e) + (WL ? w6 : 0), e->stream,
+                                       e->nd, W.theta, W.WpkT, b.pts, b.stored, b.O, b.n, b.ld, store);
+            });
             return;
         }
-    }
-    if constexpr (HH <= 64 && CC >= 3) {
-        if (head && e->nd.n_out == 1) {     // whole step, large batch: the head rides in this kernel
-            const HeadArgs ha{e->ph, e->base_norm, b.V, (const float* const*)e->orth_dev, e->bc_target, b.u, b.Hu, b.Ob, e->n_pde, b.ld, e->head_slots};
-            if (e->fwd_wlds && staged_batch(e, b))
-                hipLaunchKernelGGL((f_forward<HH, CC, EE, 1, true, true>), dim3(grid), dim3(256), fused_fwd_lds(e, true), e->stream, e->nd, W.theta, W.Wpk,
-                                   b.pts, b.stored, b.O, b.n, b.ld, store, fshare, ha);
-            else
-                hipLaunchKernelGGL((f_forward<HH, CC, EE, 1, false, true>), dim3(grid), dim3(256), fused_fwd_lds(e, false), e->stream, e->nd, W.theta, W.Wpk,
-                                   b.pts, b.stored, b.O, b.n, b.ld, store, fshare, ha);
-            return;
-        }
-    }
-    if (e->fwd_wlds && staged_batch(e, b))
-        F_LAUNCH(f_forward, HH, CC, EE, true, grid, 256, fused_fwd_lds(e, true), e->nd, W.theta, W.Wpk, b.pts, b.stored, b.O, b.n, b.ld, store, fshare, nohead);
-    else
-        F_LAUNCH(f_forward, HH, CC, EE, false, grid, 256, fused_fwd_lds(e, false), e->nd, W.theta, W.Wpk, b.pts, b.stored, b.O, b.n, b.ld, store, fshare, nohead);
+        const bool hd = head && head_form(HH, CC, NO);       // whole step, large batch: the head rides in this kernel
+        const HeadArgs ha = hd ? head_args(e, b) : HeadArgs{};
+        pick_int<0, 1>(staged && e->fwd_wlds, [&](auto w) { pick_int<0, 1>(hd, [&](auto h) {
+            constexpr bool WL = decltype(w)::value, HEAD = decltype(h)::value;
+            if constexpr (!HEAD || head_form(HH, CC, NO))      // (WL is compiled at H = 128 too, and never picked there: staged)
+                hipLaunchKernelGGL((f_forward<HH, CC, EE, NO, WL, HEAD>), dim3(grid), dim3(256), fused_fwd_lds(e, WL), e->stream,
+                                   e->nd, W.theta, W.Wpk, b.pts, b.stored, b.O, b.n, b.ld, store, fwd_tile_share(e, b, grid), ha);
+        }); });
+    });
 }
 // reverse-kernel variant for one batch: 3 = cooperative (a workgroup per tile, a wave per 16-feature slice),
 // 2 = weight gradients in registers (1 wave/SIMD),
@@ -1060,109 +1000,57 @@ static size_t coop_lds(gpe_engine* e, int C) {
     const size_t zb = e->bwd_b6 && H <= 64 ? (size_t)3 * C * (NT / 2) * 256 : (size_t)C * NT * 256;     // B6: three bf16 pieces, 24 B per four values
     return (n_gsm + 4 * (size_t)H) * sizeof(float) + fused_small_bytes(e) + (zb + 2 * (size_t)C * NT * F_TILE) * sizeof(float);
 }
-#define LDS_ATTR(BYTES, ...) (void)hipFuncSetAttribute((const void*)__VA_ARGS__, hipFuncAttributeMaxDynamicSharedMemorySize, BYTES)
-template <int HH, int CC, int EE, int NO>
-static void set_pipe_lds(int bytes) {
-    if constexpr (!(HH == 64 && CC == 5)) {
-        LDS_ATTR(bytes, f_backward_pipe<HH, CC, EE, NO, 1>); LDS_ATTR(bytes, f_backward_pipe<HH, CC, EE, NO, 2>); LDS_ATTR(bytes, f_backward_pipe<HH, CC, EE, NO, 3>);
-        if constexpr (NO == 1 && CC >= 3) {
-            LDS_ATTR(bytes, f_backward_pipe<HH, CC, EE, 1, 1, true>); LDS_ATTR(bytes, f_backward_pipe<HH, CC, EE, 1, 2, true>); LDS_ATTR(bytes, f_backward_pipe<HH, CC, EE, 1, 3, true>);
-        }
-    }
-}
 // GPE_BWD_B6: the cooperative reverse kernel with its adjoint products on the bf16 pipe exists for plain MLPs of one to three maps at
 // H <= 64; residual blocks and four / five maps keep the fp32 f_backward_coop
 static bool coop_b6(const gpe_engine* e) {
     return e->bwd_b6 && e->H <= 64 && e->nd.n_lin - 2 <= 3 && e->cfg.net_kind == GPE_NET_MLP;
 }
+#define REV_ARGS e->nd, e->theta, e->WpkT, b.pts, b.stored, b.Ob, e->gslab, b.n, b.ld, e->Ppad      // what every fused reverse kernel takes first
 // seeds: the pipelined kernel forms the seeds itself from these (mlp_backward's seeds_in_kernel); nullptr: they are in b.Ob already
-template <int HH, int CC, int EE, int NO>
-static void launch_coop_no(gpe_engine* e, Batch& b, unsigned grid, size_t lds, const SeedArgs* seeds) {
-#define CARGS e->nd, e->theta, e->WpkT, b.pts, b.stored, b.Ob, e->gslab, b.n, b.ld, e->Ppad
-    if constexpr (HH <= 64) {
-        if (coop_b6(e)) {
-            switch (e->nd.n_lin - 2) {
-                case 1: hipLaunchKernelGGL((f_backward_coop<HH, CC, EE, NO, 1, true>), dim3(grid), dim3(HH * 4), lds, e->stream, CARGS); break;
-                case 2: hipLaunchKernelGGL((f_backward_coop<HH, CC, EE, NO, 2, true>), dim3(grid), dim3(HH * 4), lds, e->stream, CARGS); break;
-                default: hipLaunchKernelGGL((f_backward_coop<HH, CC, EE, NO, 3, true>), dim3(grid), dim3(HH * 4), lds, e->stream, CARGS); break;
-            }
-            return;
-        }
-        if constexpr (!(HH == 64 && CC == 5)) if (use_pipe(e, CC)) {       // (H = 64 in 3D: two workgroups' exchange buffers exceed the LDS)
-            if constexpr (NO == 1 && CC >= 3) {
-                if (seeds) {       // small batch: the kernel forms the seeds itself (k_seed_pde was not launched)
-                    const SeedArgs& sa = *seeds;
-                    switch (e->nd.n_lin - 2) {
-                        case 1: hipLaunchKernelGGL((f_backward_pipe<HH, CC, EE, 1, 1, true>), dim3(grid), dim3(HH * 4), lds, e->stream, CARGS, sa); break;
-                        case 2: hipLaunchKernelGGL((f_backward_pipe<HH, CC, EE, 1, 2, true>), dim3(grid), dim3(HH * 4), lds, e->stream, CARGS, sa); break;
-                        default: hipLaunchKernelGGL((f_backward_pipe<HH, CC, EE, 1, 3, true>), dim3(grid), dim3(HH * 4), lds, e->stream, CARGS, sa); break;
-                    }
-                    return;
-                }
-            }
-            SeedArgs none{};
-            // large batches on two workgroups per CU: uneven split of each CU's tiles between its two workgroups (GPE_PIPE_SHARE, / 1024)
-            if (e->pipe_share > 0 && grid == (unsigned)(2 * e->num_cu) && (b.n + 15) / 16 >= e->share_min_tiles * (int64_t)grid) none.old_share_q10 = e->pipe_share;
-            switch (e->nd.n_lin - 2) {
-                case 1: hipLaunchKernelGGL((f_backward_pipe<HH, CC, EE, NO, 1>), dim3(grid), dim3(HH * 4), lds, e->stream, CARGS, none); break;
-                case 2: hipLaunchKernelGGL((f_backward_pipe<HH, CC, EE, NO, 2>), dim3(grid), dim3(HH * 4), lds, e->stream, CARGS, none); break;
-                default: hipLaunchKernelGGL((f_backward_pipe<HH, CC, EE, NO, 3>), dim3(grid), dim3(HH * 4), lds, e->stream, CARGS, none); break;
-            }
-            return;
-        }
-    }
-    if constexpr (HH <= 64 && NO == 1) {
-        if (e->cfg.net_kind == GPE_NET_RESIDUAL) {
-            if (e->nd.n_lin - 2 == 2) hipLaunchKernelGGL((f_backward_coop<HH, CC, EE, 1, 2, false, true>), dim3(grid), dim3(HH * 4), lds, e->stream, CARGS);
-            else hipLaunchKernelGGL((f_backward_coop<HH, CC, EE, 1, 4, false, true>), dim3(grid), dim3(HH * 4), lds, e->stream, CARGS);
-            return;
-        }
-    }
-    switch (e->nd.n_lin - 2) {
-        case 1: hipLaunchKernelGGL((f_backward_coop<HH, CC, EE, NO, 1>), dim3(grid), dim3(HH * 4), lds, e->stream, CARGS); break;
-        case 2: hipLaunchKernelGGL((f_backward_coop<HH, CC, EE, NO, 2>), dim3(grid), dim3(HH * 4), lds, e->stream, CARGS); break;
-        case 3: hipLaunchKernelGGL((f_backward_coop<HH, CC, EE, NO, 3>), dim3(grid), dim3(HH * 4), lds, e->stream, CARGS); break;
-        case 4:
-            if constexpr (HH == 128 || NO == 1)
-                hipLaunchKernelGGL((f_backward_coop<HH, CC, EE, NO, 4>), dim3(grid), dim3(HH * 4), lds, e->stream, CARGS);
-            break;
-        default:
-            if constexpr (HH == 128 || NO == 1)
-                hipLaunchKernelGGL((f_backward_coop<HH, CC, EE, NO, 5>), dim3(grid), dim3(HH * 4), lds, e->stream, CARGS);
-            break;
-    }
-#undef CARGS
-}
 template <int HH, int CC, int EE>
 static void launch_f_backward_coop(gpe_engine* e, Batch& b, unsigned grid, size_t lds, const SeedArgs* seeds) {
-#ifdef GPE_FAST_BUILD
-    launch_coop_no<HH, CC, EE, 1>(e, b, grid, lds, seeds);
-#else
-    if (e->nd.n_out == 1) launch_coop_no<HH, CC, EE, 1>(e, b, grid, lds, seeds);
-    else launch_coop_no<HH, CC, EE, 2>(e, b, grid, lds, seeds);
-#endif
+    const int maps = e->nd.n_lin - 2;
+    pick_n_out(e->nd.n_out, [&](auto no) {
+        constexpr int NO = decltype(no)::value;
+        if constexpr (HH <= 64) if (coop_b6(e)) {
+            pick_int<1, 3>(maps, [&](auto nh) {
+                hipLaunchKernelGGL((f_backward_coop<HH, CC, EE, NO, decltype(nh)::value, true>), dim3(grid), dim3(HH * 4), lds, e->stream, REV_ARGS);
+            });
+            return;
+        }
+        if constexpr (pipe_form(HH, CC)) if (use_pipe(e, CC)) {
+            // small batch: the kernel forms the seeds itself (k_seed_pde was not launched); otherwise the large batches' uneven tile split
+            const bool sd = seeds && head_form(HH, CC, NO);
+            SeedArgs sa = sd ? *seeds : SeedArgs{};
+            if (!sd) sa.old_share_q10 = pipe_tile_share(e, b, grid);
+            pick_int<1, 3>(maps, [&](auto nh) { pick_int<0, 1>(sd, [&](auto s) {
+                constexpr bool SEEDS = decltype(s)::value;
+                if constexpr (!SEEDS || head_form(HH, CC, NO))
+                    hipLaunchKernelGGL((f_backward_pipe<HH, CC, EE, NO, decltype(nh)::value, SEEDS>), dim3(grid), dim3(HH * 4), lds, e->stream, REV_ARGS, sa);
+            }); });
+            return;
+        }
+        const bool res = e->cfg.net_kind == GPE_NET_RESIDUAL && HH <= 64 && NO == 1;
+        pick_int<1, 5>(res ? (maps == 2 ? 2 : 4) : maps, [&](auto nh) { pick_int<0, 1>(res, [&](auto r) {
+            constexpr int NH = decltype(nh)::value;
+            constexpr bool RES = decltype(r)::value;
+            if constexpr (coop_form(HH, NO, NH, RES))
+                hipLaunchKernelGGL((f_backward_coop<HH, CC, EE, NO, NH, false, RES>), dim3(grid), dim3(HH * 4), lds, e->stream, REV_ARGS);
+        }); });
+    });
 }
 template <int HH, int CC, int EE>
 static void launch_f_backward(gpe_engine* e, Batch& b, unsigned grid, size_t lds, const SeedArgs* seeds) {
-    if constexpr (HH > 64) {
-        B_LAUNCH(HH, CC, EE, false, 0, grid, 256, lds, e->nd, e->theta, e->WpkT, b.pts, b.stored, b.Ob, e->gslab, b.n, b.ld, e->Ppad, e->nslab_g);
-        return;
-    } else {
-#define BARGS e->nd, e->theta, e->WpkT, b.pts, b.stored, b.Ob, e->gslab, b.n, b.ld, e->Ppad, e->nslab_g
     const int kind = bwd_kind(e, b);
-    if (kind == 3) launch_f_backward_coop<HH, CC, EE>(e, b, grid, lds, seeds);
-    else if (kind == 2) {
-        switch (e->nd.n_lin - 2) {
-            case 1: B_LAUNCH(HH, CC, EE, true, 1, grid, 256, lds, BARGS); break;
-            case 2: B_LAUNCH(HH, CC, EE, true, 2, grid, 256, lds, BARGS); break;
-            default: B_LAUNCH(HH, CC, EE, true, 3, grid, 256, lds, BARGS); break;
-        }
-    }
-    else
-        B_LAUNCH(HH, CC, EE, false, 0, grid, 256, lds, BARGS);
-#undef BARGS
-    }
+    if (kind == 3) return launch_f_backward_coop<HH, CC, EE>(e, b, grid, lds, seeds);
+    // kind 2 (H <= 64): the weight gradients of one to three maps in registers, weights in LDS; kind 0: the plain kernel
+    pick_n_out(e->nd.n_out, [&](auto no) { pick_int<0, 3>(kind == 2 ? e->nd.n_lin - 2 : 0, [&](auto nh) {
+        constexpr int NO = decltype(no)::value, NH = decltype(nh)::value;
+        if constexpr (NH == 0 || HH <= 64)
+            hipLaunchKernelGGL((f_backward<HH, CC, EE, NO, (NH > 0), NH>), dim3(grid), dim3(256), lds, e->stream, REV_ARGS, e->nslab_g);
+    }); });
 }
+#undef REV_ARGS
 
 // persistent grids: forward 256-thread blocks, 2 per CU; reverse 256-thread x 2 per CU, or 512-thread x 1 per CU (WLDS)
 static unsigned fused_grid(gpe_engine* e, int64_t n, int waves_per_block, int blocks_per_cu) {
@@ -1241,7 +1129,6 @@ static int mlp_forward(gpe_engine* e, Batch& b, bool store, const FwdWeights* fr
     if (e->path == GPE_PATH_FUSED) {
         int rc = frozen ? GPE_OK : ensure_packed(e);
         if (rc) return rc;
-        unsigned grid = fused_grid(e, b.n, 4, e->fwd_wg_per_cu);
         if (mark) prof_mark(e, 0, true);
         if (e->wide_fwd) {
             WideCall wc = wide_call(e, b);
@@ -1252,23 +1139,8 @@ static int mlp_forward(gpe_engine* e, Batch& b, bool store, const FwdWeights* fr
             if (mark) prof_mark(e, 0, false);
             return GPE_OK;
         }
-#ifdef GPE_FAST_BUILD
-        if (e->H != 64 || e->nd.n_out != 1) FAIL(e, GPE_ERR_INVALID, "fast build: only H = 64, n_out = 1 compiled");
-        DISPATCH_FWD(b, launch_f_forward<64, CC, EE>(e, b, grid, store ? 1 : 0, W, head_slots > 0));
-#else
-        if (e->H == 128) {      // wide layers: one wave per SIMD, C <= 5 (checked at create)
-            grid = fused_grid(e, b.n, 4, 1);
-            switch (b.C * 10 + b.E) {     // wide layers: dim <= 2 (checked at create)
-                case 10: launch_f_forward<128, 1, 0>(e, b, grid, store ? 1 : 0, W, head_slots > 0); break;
-                case 31: launch_f_forward<128, 3, 1>(e, b, grid, store ? 1 : 0, W, head_slots > 0); break;
-                case 41: launch_f_forward<128, 4, 1>(e, b, grid, store ? 1 : 0, W, head_slots > 0); break;
-                case 52: launch_f_forward<128, 5, 2>(e, b, grid, store ? 1 : 0, W, head_slots > 0); break;
-                default: FAIL(e, GPE_ERR_INVALID, "bad channel pair (%d,%d) for H = 128", b.C, b.E);
-            }
-        }
-        else if (e->H == 64) { DISPATCH_FWD(b, launch_f_forward<64, CC, EE>(e, b, grid, store ? 1 : 0, W, head_slots > 0)); }
-        else            { DISPATCH_FWD(b, launch_f_forward<32, CC, EE>(e, b, grid, store ? 1 : 0, W, head_slots > 0)); }
-#endif
+        // H = 128 (wide layers): C <= 5, dim <= 2 (checked at create)
+        if ((rc = launch_hce<ce_forward, ce_h128_forward>(e, b, [&](auto HH, auto CC, auto EE) { launch_f_forward<HH, CC, EE>(e, b, store ? 1 : 0, W, head_slots > 0); }))) return rc;
         if (mark) prof_mark(e, 0, false);
     } else {
         const NetDesc& nd = e->nd;
@@ -1278,21 +1150,21 @@ static int mlp_forward(gpe_engine* e, Batch& b, bool store, const FwdWeights* fr
             const float* Sskip = nd.skip[lin] >= 0 ? b.S[nd.skip[lin]] : nullptr;     // residual block: the VALU kernel adds the block input
             if (!Sskip && lin > 0 && nd.width[lin] % 64 == 0 && nd.width[lin + 1] % 256 == 0 && e->gen_mfma && e->gen_mfma2) {
                 dim3 grid(cdiv(b.n, 16), nd.width[lin + 1] / 256);      // a block = one point tile x 256 outputs, jets shared through LDS
-                DISPATCH_FWD(b, hipLaunchKernelGGL((g_fwd_layer_mfma2<CC, EE>), grid, dim3(256), 0, e->stream, nd, lin, W.theta,
-                                                    Sprev, Out, b.n, b.ld));
+                if (int rc = launch_ce(e, b, ce_forward{}, [&](auto CC, auto EE) { hipLaunchKernelGGL((g_fwd_layer_mfma2<CC, EE>), grid, dim3(256), 0, e->stream, nd, lin, W.theta,
+                                                    Sprev, Out, b.n, b.ld); })) return rc;
             } else if (lin > 0 && nd.width[lin] % 64 == 0 && nd.width[lin + 1] % 64 == 0 && e->gen_mfma &&
                        (!Sskip || nd.width[nd.skip[lin] + 1] == nd.width[lin + 1])) {   // wide map: matrix cores (round 4: residual blocks too)
                 dim3 grid(cdiv(cdiv(b.n, 16), 4), nd.width[lin + 1] / 64);
-                DISPATCH_FWD(b, hipLaunchKernelGGL((g_fwd_layer_mfma<CC, EE>), grid, dim3(256), 0, e->stream, nd, lin, W.theta,
-                                                    Sprev, Out, b.n, b.ld, Sskip));
+                if (int rc = launch_ce(e, b, ce_forward{}, [&](auto CC, auto EE) { hipLaunchKernelGGL((g_fwd_layer_mfma<CC, EE>), grid, dim3(256), 0, e->stream, nd, lin, W.theta,
+                                                    Sprev, Out, b.n, b.ld, Sskip); })) return rc;
             } else if (nd.width[lin + 1] >= 64) {      // wide layer: 16 output features per thread
                 dim3 grid(cdiv(b.n, 256), cdiv(nd.width[lin + 1], G_FBW));
-                DISPATCH_FWD(b, hipLaunchKernelGGL((g_fwd_layer<CC, EE, G_FBW>), grid, dim3(256), 0, e->stream, nd, lin, W.theta,
-                                                    b.pts, Sprev, Out, b.n, b.ld, Sskip));
+                if (int rc = launch_ce(e, b, ce_forward{}, [&](auto CC, auto EE) { hipLaunchKernelGGL((g_fwd_layer<CC, EE, G_FBW>), grid, dim3(256), 0, e->stream, nd, lin, W.theta,
+                                                    b.pts, Sprev, Out, b.n, b.ld, Sskip); })) return rc;
             } else {
                 dim3 grid(cdiv(b.n, 256), cdiv(nd.width[lin + 1], G_FB));
-                DISPATCH_FWD(b, hipLaunchKernelGGL((g_fwd_layer<CC, EE, G_FB>), grid, dim3(256), 0, e->stream, nd, lin, W.theta,
-                                                    b.pts, Sprev, Out, b.n, b.ld, Sskip));
+                if (int rc = launch_ce(e, b, ce_forward{}, [&](auto CC, auto EE) { hipLaunchKernelGGL((g_fwd_layer<CC, EE, G_FB>), grid, dim3(256), 0, e->stream, nd, lin, W.theta,
+                                                    b.pts, Sprev, Out, b.n, b.ld, Sskip); })) return rc;
             }
         }
     }
@@ -1328,34 +1200,13 @@ static int mlp_backward(gpe_engine* e, Batch& b, const BwdOpts& o) {
             if (wr) FAIL(e, GPE_ERR_HIP, "wide reverse launch: %s", hipGetErrorString((hipError_t)wr));
             nred = wide_groups(e->H, b.n, e->num_cu);
         } else {
-#ifdef GPE_FAST_BUILD
-        if (e->H != 64 || e->nd.n_out != 1) FAIL(e, GPE_ERR_INVALID, "fast build: only H = 64, n_out = 1 compiled");
-        DISPATCH_TRAIN(b, launch_f_backward<64, CC, EE>(e, b, grid, lds, seeds));
-#else
-        if (e->H == 128 && kind == 3) {
-            grid = fused_grid(e, b.n, 1, 1);
-            nred = (int)grid;
-            switch (b.C * 10 + b.E) {
-                case 10: launch_f_backward_coop<128, 1, 0>(e, b, grid, lds, seeds); break;
-                case 31: launch_f_backward_coop<128, 3, 1>(e, b, grid, lds, seeds); break;
-                case 41: launch_f_backward_coop<128, 4, 1>(e, b, grid, lds, seeds); break;
-                default: FAIL(e, GPE_ERR_INVALID, "bad channel pair (%d,%d) for H = 128", b.C, b.E);
-            }
+        if (e->H == 128) {      // one workgroup per CU; the plain kernel adds into global slabs
+            grid = fused_grid(e, b.n, kind == 3 ? 1 : 4, 1);
+            nred = kind == 3 ? (int)grid : e->nslab_g;
+            if (kind != 3) HIPCHK(e, hipMemsetAsync(e->gslab, 0, (size_t)e->nslab_g * e->Ppad * sizeof(float), e->stream));
         }
-        else if (e->H == 128) {
-            grid = fused_grid(e, b.n, 4, 1);
-            nred = e->nslab_g;
-            HIPCHK(e, hipMemsetAsync(e->gslab, 0, (size_t)e->nslab_g * e->Ppad * sizeof(float), e->stream));
-            switch (b.C * 10 + b.E) {
-                case 10: launch_f_backward<128, 1, 0>(e, b, grid, lds, seeds); break;
-                case 31: launch_f_backward<128, 3, 1>(e, b, grid, lds, seeds); break;
-                case 41: launch_f_backward<128, 4, 1>(e, b, grid, lds, seeds); break;
-                default: FAIL(e, GPE_ERR_INVALID, "bad channel pair (%d,%d) for H = 128", b.C, b.E);
-            }
-        }
-        else if (e->H == 64) { DISPATCH_TRAIN(b, launch_f_backward<64, CC, EE>(e, b, grid, lds, seeds)); }
-        else            { DISPATCH_TRAIN(b, launch_f_backward<32, CC, EE>(e, b, grid, lds, seeds)); }
-#endif
+        const int rc = launch_hce<ce_train, ce_h128_reverse>(e, b, [&](auto HH, auto CC, auto EE) { launch_f_backward<HH, CC, EE>(e, b, grid, lds, seeds); });
+        if (rc) return rc;
         }
         if (mark) prof_mark(e, 1, false);
         HIPCHK(e, hipGetLastError());
@@ -1399,8 +1250,8 @@ static int mlp_backward(gpe_engine* e, Batch& b, const BwdOpts& o) {
                 const int64_t nchunk = (b.n + chunk - 1) / chunk;
                 dim3 gw(Ho / 128, K / 128, (unsigned)nchunk);
                 const size_t pl = (size_t)2 * b.C * 128 * 16 * sizeof(float);
-                DISPATCH_TRAIN(b, hipLaunchKernelGGL((g_bwd_weight_mfma2<CC, EE>), gw, dim3(256), pl, e->stream, nd, lin, Sprev, Zb,
-                                                    e->grad, b.n, b.ld, chunk));
+                if (int rc = launch_ce(e, b, ce_train{}, [&](auto CC, auto EE) { hipLaunchKernelGGL((g_bwd_weight_mfma2<CC, EE>), gw, dim3(256), pl, e->stream, nd, lin, Sprev, Zb,
+                                                    e->grad, b.n, b.ld, chunk); })) return rc;
             } else if (lin > 0 && Ho % 64 == 0 && K % 64 == 0 && e->gen_mfma) {
                 // wide hidden->hidden map: split-K GEMM over the points on the matrix cores
                 const int64_t want = (int64_t)e->num_cu * 16 / ((Ho / 64) * (K / 64)) + 1;          // chunks so that ~16 waves per CU exist
@@ -1411,20 +1262,20 @@ static int mlp_backward(gpe_engine* e, Batch& b, const BwdOpts& o) {
                 if (chunk < e->gen_min_chunk) chunk = e->gen_min_chunk;
                 const int64_t nchunk = (b.n + chunk - 1) / chunk;
                 dim3 gw(Ho / 64, K / 64, (unsigned)((nchunk + 3) / 4));
-                DISPATCH_TRAIN(b, hipLaunchKernelGGL((g_bwd_weight_mfma<CC, EE>), gw, dim3(256), 0, e->stream, nd, lin, Sprev, Zb,
-                                                    e->grad, b.n, b.ld, chunk));
+                if (int rc = launch_ce(e, b, ce_train{}, [&](auto CC, auto EE) { hipLaunchKernelGGL((g_bwd_weight_mfma<CC, EE>), gw, dim3(256), 0, e->stream, nd, lin, Sprev, Zb,
+                                                    e->grad, b.n, b.ld, chunk); })) return rc;
             } else if (Ho >= 64 && K >= 16) {   // wide layer: 8 rows of the weight gradient per block share the recomputed jets
                 dim3 gw(cdiv(Ho, 8), cdiv(K, G_KB));
-                DISPATCH_TRAIN(b, hipLaunchKernelGGL((g_bwd_weight<CC, EE, 8, G_KB>), gw, dim3(256), 0, e->stream, nd, lin, b.pts, Sprev,
-                                                    Zb, e->grad, b.n, b.ld));
+                if (int rc = launch_ce(e, b, ce_train{}, [&](auto CC, auto EE) { hipLaunchKernelGGL((g_bwd_weight<CC, EE, 8, G_KB>), gw, dim3(256), 0, e->stream, nd, lin, b.pts, Sprev,
+                                                    Zb, e->grad, b.n, b.ld); })) return rc;
             } else if (Ho < 8 && K >= 64) {     // output layer of a wide network: one block per (n, k) keeps K blocks in flight
                 dim3 gw(Ho, K);
-                DISPATCH_TRAIN(b, hipLaunchKernelGGL((g_bwd_weight<CC, EE, 1, 1>), gw, dim3(256), 0, e->stream, nd, lin, b.pts, Sprev,
-                                                    Zb, e->grad, b.n, b.ld));
+                if (int rc = launch_ce(e, b, ce_train{}, [&](auto CC, auto EE) { hipLaunchKernelGGL((g_bwd_weight<CC, EE, 1, 1>), gw, dim3(256), 0, e->stream, nd, lin, b.pts, Sprev,
+                                                    Zb, e->grad, b.n, b.ld); })) return rc;
             } else {
                 dim3 gw(Ho, cdiv(K, G_KB));
-                DISPATCH_TRAIN(b, hipLaunchKernelGGL((g_bwd_weight<CC, EE, 1, G_KB>), gw, dim3(256), 0, e->stream, nd, lin, b.pts, Sprev,
-                                                    Zb, e->grad, b.n, b.ld));
+                if (int rc = launch_ce(e, b, ce_train{}, [&](auto CC, auto EE) { hipLaunchKernelGGL((g_bwd_weight<CC, EE, 1, G_KB>), gw, dim3(256), 0, e->stream, nd, lin, b.pts, Sprev,
+                                                    Zb, e->grad, b.n, b.ld); })) return rc;
             }
             if (o.bucketed && close) {
                 // data-parallel step: this map's gradient slice (weights + bias, contiguous) is final -> all-reduce it on the
@@ -1437,21 +1288,21 @@ static int mlp_backward(gpe_engine* e, Batch& b, const BwdOpts& o) {
                 const bool join = skip_adj && skip_to == lin - 1;      // the skipped-from layer: its adjoint gets the saved zbar first
                 if (!join && K % 256 == 0 && Ho % 64 == 0 && e->gen_mfma && e->gen_mfma2) {
                     dim3 gd(cdiv(b.n, 16), K / 256);             // activation adjoint of layer lin-1 fused into the epilogue
-                    DISPATCH_TRAIN(b, hipLaunchKernelGGL((g_bwd_data_mfma2<CC, EE>), gd, dim3(256), 0, e->stream, nd, lin, e->theta, Zb,
-                                                        nxt, Sprev, b.n, b.ld));
+                    if (int rc = launch_ce(e, b, ce_train{}, [&](auto CC, auto EE) { hipLaunchKernelGGL((g_bwd_data_mfma2<CC, EE>), gd, dim3(256), 0, e->stream, nd, lin, e->theta, Zb,
+                                                        nxt, Sprev, b.n, b.ld); })) return rc;
                     act_done = true;
                 } else if (K % 64 == 0 && Ho % 16 == 0 && e->gen_mfma) {
                     dim3 gd(cdiv(cdiv(b.n, 16), 4), K / 64);
-                    DISPATCH_TRAIN(b, hipLaunchKernelGGL((g_bwd_data_mfma<CC>), gd, dim3(256), 0, e->stream, nd, lin, e->theta, Zb,
-                                                        nxt, b.n, b.ld));
+                    if (int rc = launch_ce(e, b, ce_train{}, [&](auto CC, auto EE) { hipLaunchKernelGGL((g_bwd_data_mfma<CC>), gd, dim3(256), 0, e->stream, nd, lin, e->theta, Zb,
+                                                        nxt, b.n, b.ld); })) return rc;
                 } else if (K >= 64) {
                     dim3 gd(cdiv(b.n, 256), cdiv(K, G_FBW));
-                    DISPATCH_TRAIN(b, hipLaunchKernelGGL((g_bwd_data<CC, G_FBW>), gd, dim3(256), 0, e->stream, nd, lin, e->theta, Zb,
-                                                        nxt, b.n, b.ld));
+                    if (int rc = launch_ce(e, b, ce_train{}, [&](auto CC, auto EE) { hipLaunchKernelGGL((g_bwd_data<CC, G_FBW>), gd, dim3(256), 0, e->stream, nd, lin, e->theta, Zb,
+                                                        nxt, b.n, b.ld); })) return rc;
                 } else {
                     dim3 gd(cdiv(b.n, 256), cdiv(K, G_FB));
-                    DISPATCH_TRAIN(b, hipLaunchKernelGGL((g_bwd_data<CC, G_FB>), gd, dim3(256), 0, e->stream, nd, lin, e->theta, Zb,
-                                                        nxt, b.n, b.ld));
+                    if (int rc = launch_ce(e, b, ce_train{}, [&](auto CC, auto EE) { hipLaunchKernelGGL((g_bwd_data<CC, G_FB>), gd, dim3(256), 0, e->stream, nd, lin, e->theta, Zb,
+                                                        nxt, b.n, b.ld); })) return rc;
                 }
                 if (join) {
                     const int64_t cnt = (int64_t)b.C * K * b.ld;
@@ -1460,7 +1311,7 @@ static int mlp_backward(gpe_engine* e, Batch& b, const BwdOpts& o) {
                 }
                 if (!act_done) {
                     dim3 ga(cdiv(b.n, 256), K);
-                    DISPATCH_TRAIN(b, hipLaunchKernelGGL((g_bwd_act<CC, EE>), ga, dim3(256), 0, e->stream, K, Sprev, nxt, b.n, b.ld));
+                    if (int rc = launch_ce(e, b, ce_train{}, [&](auto CC, auto EE) { hipLaunchKernelGGL((g_bwd_act<CC, EE>), ga, dim3(256), 0, e->stream, K, Sprev, nxt, b.n, b.ld); })) return rc;
                 }
                 Zb = nxt;
                 // next free adjoint buffer: not the one just written, not one still waiting for its skip join
@@ -1839,43 +1690,45 @@ static int alloc_state(gpe_engine* e, const AllocSwitches& sw) {
     return GPE_OK;
 }
 
-// 7. the kernels that take more dynamic LDS than the 64 KB a launch gets by default
+// 7. the kernels that take more dynamic LDS than the 64 KB a launch gets by default: every instance the launchers can pick -- the forms
+// and ranges of gpe_dispatch.h, walked with each_* where the launchers pick_* -- once, here (a first launch may sit in a stream capture)
+template <class K>
+static void lds_limit(K* kernel, int bytes) { (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes); }
+template <int HH, int CC, int EE, int NO>
+static void raise_fused_limits() {
+    constexpr int all = 160 * 1024;
+    each_int<1, 5>([](auto nh) {
+        constexpr int NH = decltype(nh)::value;
+        each_int<0, 1>([](auto r) {
+            constexpr bool RES = decltype(r)::value;
+            if constexpr (coop_form(HH, NO, NH, RES)) lds_limit(f_backward_coop<HH, CC, EE, NO, NH, false, RES>, all);
+        });
+        if constexpr (HH == 128) lds_limit(f_forward_coop<HH, CC, EE, NO, NH>, all);
+        if constexpr (HH <= 64 && NH <= 3) {
+            lds_limit(f_backward_coop<HH, CC, EE, NO, NH, true>, all);
+            lds_limit(f_backward<HH, CC, EE, NO, true, NH>, all);
+            if constexpr (pipe_form(HH, CC)) {
+                lds_limit(f_backward_pipe<HH, CC, EE, NO, NH>, all);
+                if constexpr (head_form(HH, CC, NO)) lds_limit(f_backward_pipe<HH, CC, EE, NO, NH, true>, all);
+            }
+        }
+    });
+    lds_limit(f_backward<HH, CC, EE, NO, false, 0>, all);
+    if constexpr (HH <= 64) { lds_limit(f_forward<HH, CC, EE, NO, true>, 64 * 1024); lds_limit(f_forward_b6<HH, CC, EE, NO, true>, 80 * 1024); }
+}
 static void raise_lds_limits(gpe_engine* e) {
     if (e->path == GPE_PATH_FUSED) {
         if (e->wide) wide_init();
-        const int lds_b = 160 * 1024, lds_f = 64 * 1024;
-#define SETLDS(HH, CC, EE, NO)                                                                                                                      \
-    LDS_ATTR(lds_b, f_backward<HH, CC, EE, NO, false, 0>); LDS_ATTR(lds_b, f_backward<HH, CC, EE, NO, true, 1>);                                    \
-    LDS_ATTR(lds_b, f_backward<HH, CC, EE, NO, true, 2>); LDS_ATTR(lds_b, f_backward<HH, CC, EE, NO, true, 3>);                                     \
-    LDS_ATTR(lds_b, f_backward_coop<HH, CC, EE, NO, 1>); LDS_ATTR(lds_b, f_backward_coop<HH, CC, EE, NO, 2>); LDS_ATTR(lds_b, f_backward_coop<HH, CC, EE, NO, 3>); \
-    if constexpr (NO == 1) {                                                                                                                        \
-        LDS_ATTR(lds_b, f_backward_coop<HH, CC, EE, 1, 2, false, true>); LDS_ATTR(lds_b, f_backward_coop<HH, CC, EE, 1, 4, false, true>);           \
-        LDS_ATTR(lds_b, f_backward_coop<HH, CC, EE, 1, 4>); LDS_ATTR(lds_b, f_backward_coop<HH, CC, EE, 1, 5>); }                                   \
-    set_pipe_lds<HH, CC, EE, NO>(lds_b);                                                                                                            \
-    LDS_ATTR(lds_b, f_backward_coop<HH, CC, EE, NO, 1, true>); LDS_ATTR(lds_b, f_backward_coop<HH, CC, EE, NO, 2, true>); LDS_ATTR(lds_b, f_backward_coop<HH, CC, EE, NO, 3, true>); \
-    LDS_ATTR(lds_f, f_forward<HH, CC, EE, NO, true>); LDS_ATTR(80 * 1024, f_forward_b6<HH, CC, EE, NO, true>)
-#ifdef GPE_FAST_BUILD
-        SETLDS(64, 1, 0, 1); SETLDS(64, 4, 1, 1);
-#else
-        SETLDS(64, 1, 0, 1); SETLDS(64, 3, 1, 1); SETLDS(64, 4, 1, 1); SETLDS(64, 5, 1, 1);
-        SETLDS(64, 1, 0, 2); SETLDS(64, 3, 1, 2); SETLDS(64, 4, 1, 2); SETLDS(64, 5, 1, 2);
-        SETLDS(32, 1, 0, 1); SETLDS(32, 3, 1, 1); SETLDS(32, 4, 1, 1); SETLDS(32, 5, 1, 1);
-        SETLDS(32, 1, 0, 2); SETLDS(32, 3, 1, 2); SETLDS(32, 4, 1, 2); SETLDS(32, 5, 1, 2);
-#define SETLDS128(CC, EE, NO)                                                                                                                       \
-    LDS_ATTR(lds_b, f_backward_coop<128, CC, EE, NO, 1>); LDS_ATTR(lds_b, f_backward_coop<128, CC, EE, NO, 2>); LDS_ATTR(lds_b, f_backward_coop<128, CC, EE, NO, 3>); \
-    LDS_ATTR(lds_b, f_backward_coop<128, CC, EE, NO, 4>); LDS_ATTR(lds_b, f_backward_coop<128, CC, EE, NO, 5>);                                     \
-    LDS_ATTR(lds_b, f_forward_coop<128, CC, EE, NO, 1>); LDS_ATTR(lds_b, f_forward_coop<128, CC, EE, NO, 2>); LDS_ATTR(lds_b, f_forward_coop<128, CC, EE, NO, 3>); \
-    LDS_ATTR(lds_b, f_forward_coop<128, CC, EE, NO, 4>); LDS_ATTR(lds_b, f_forward_coop<128, CC, EE, NO, 5>);                                       \
-    LDS_ATTR(lds_b, f_backward<128, CC, EE, NO, false, 0>)
-        SETLDS128(1, 0, 1); SETLDS128(3, 1, 1); SETLDS128(4, 1, 1); SETLDS128(1, 0, 2); SETLDS128(3, 1, 2); SETLDS128(4, 1, 2);
-#undef SETLDS128
-#endif
-#undef SETLDS
-    }
-    LDS_ATTR(160 * 1024, g_bwd_weight_mfma2<1, 0>); LDS_ATTR(160 * 1024, g_bwd_weight_mfma2<4, 1>);
+        each_n_out([](auto no) {
+            constexpr int NO = decltype(no)::value;
+            each_ce(ce_train{}, [](auto CC, auto EE) { raise_fused_limits<64, CC, EE, NO>(); });
 #ifndef GPE_FAST_BUILD
-    LDS_ATTR(160 * 1024, g_bwd_weight_mfma2<3, 1>); LDS_ATTR(160 * 1024, g_bwd_weight_mfma2<5, 1>);
+            each_ce(ce_train{}, [](auto CC, auto EE) { raise_fused_limits<32, CC, EE, NO>(); });
+            each_ce(ce_h128_reverse{}, [](auto CC, auto EE) { raise_fused_limits<128, CC, EE, NO>(); });      // (H = 128: the cooperative forward takes these pairs too, (5,2) goes to f_forward)
 #endif
+        });
+    }
+    each_ce(ce_train{}, [](auto CC, auto EE) { lds_limit(g_bwd_weight_mfma2<CC, EE>, 160 * 1024); });
 }
 
 extern "C" {
@@ -1917,7 +1770,7 @@ int gpe_active_kernels(gpe_engine* e, char* buf, size_t n) {
         if (wide_reverse(e, const_cast<Batch&>(b))) snprintf(r, sizeof r, "%d x w_bwd_map<%d,%d,%d,%d> (output layer fused into the top map)", maps, e->H, b.C, b.E, e->H / 128);
         else snprintf(r, sizeof r, "f_backward_coop<%d,%d,%d,%d,%d>", e->H, b.C, b.E, e->nd.n_out, maps > 5 ? 5 : maps);
     } else if (e->path == GPE_PATH_FUSED) {
-        const bool fc = fwd_coop(e, b) && (e->H <= 64 || b.C <= 4);
+        const bool fc = fwd_coop(e, b);
         if (fc) snprintf(f, sizeof f, "f_forward_coop<%d,%d,%d,%d,%d>", e->H, b.C, b.E, e->nd.n_out, maps > 5 ? 5 : maps);
         else if (e->H <= 64 && e->fwd_b6 && staged_batch(e, b)) snprintf(f, sizeof f, "f_forward_b6<%d,%d,%d,%d>", e->H, b.C, b.E, e->nd.n_out);
         else snprintf(f, sizeof f, "f_forward<%d,%d,%d,%d,%s>", e->H, b.C, b.E, e->nd.n_out,
@@ -1939,15 +1792,11 @@ int gpe_active_kernels(gpe_engine* e, char* buf, size_t n) {
         snprintf(r, sizeof r, "%s<%d,%d>", (e->gen_mfma && e->gen_mfma2 && W % 128 == 0) ? "g_bwd_weight_mfma2"
                                             : (m1 ? "g_bwd_weight_mfma" : "g_bwd_weight"), b.C, b.E);
     }
-    // uneven static tile split between the two workgroups of a CU (large batches; launch_f_forward / launch_coop_no apply the same rules)
+    // uneven static tile split between the two workgroups of a CU (large batches), where launch_f_forward / launch_f_backward_coop ask for it
     int sf = 0, sb = 0;
     if (e->path == GPE_PATH_FUSED && !e->wide && e->H <= 64) {
-        const int64_t ntiles = (b.n + 15) / 16, g2 = 2 * (int64_t)e->num_cu;
-        if (!fwd_coop(e, b) && !e->fwd_b6 && e->fwd_share > 0 && fused_grid(e, b.n, 4, e->fwd_wg_per_cu) == (unsigned)g2 && ntiles >= 4 * e->share_min_tiles * g2)
-            sf = e->fwd_share;
-        if (bwd_kind(e, b) == 3 && use_pipe(e, b.C) && !seed_in_reverse(e) && e->pipe_share > 0 &&
-            fused_grid(e, b.n, 1, e->coop_wg_per_cu) == (unsigned)g2 && ntiles >= e->share_min_tiles * g2)
-            sb = e->pipe_share;
+        if (!fwd_coop(e, b) && !e->fwd_b6) sf = fwd_tile_share(e, b, fwd_grid(e, b, false));
+        if (bwd_kind(e, b) == 3 && use_pipe(e, b.C) && !seed_in_reverse(e)) sb = pipe_tile_share(e, b, fused_grid(e, b.n, 1, e->coop_wg_per_cu));
     }
     if (e->umap.empty()) snprintf(buf, n, "fwd=%s;bwd=%s;split=fwd %d/1024, bwd %d/1024", f, r, sf, sb);
     else snprintf(buf, n, "fwd=%s;bwd=%s;split=fwd %d/1024, bwd %d/1024;padded=hidden widths up to %d run as %d", f, r, sf, sb,
@@ -3073,30 +2922,30 @@ static int launch_head_pde(gpe_engine* e, bool energy) {
     const float* none = nullptr;
     if (e->cfg.mixture && (energy || e->mix_wE != 0.f)) {
         if (e->wq) {
-            DISPATCH_TRAIN(b, hipLaunchKernelGGL((k_head_mix<CC, EE, true, true>), g, dim3(e->head_threads), 0, e->stream, e->ph, e->oc.mix, b.pts, b.V, b.O, b.u, b.Hu,
-                                                e->sums(), b.n, b.ld, e->n_pde, e->bc_target, b.Ob, e->lsums(), e->wq, b.ux));
+            if (int rc = launch_ce(e, b, ce_train{}, [&](auto CC, auto EE) { hipLaunchKernelGGL((k_head_mix<CC, EE, true, true>), g, dim3(e->head_threads), 0, e->stream, e->ph, e->oc.mix, b.pts, b.V, b.O, b.u, b.Hu,
+                                                e->sums(), b.n, b.ld, e->n_pde, e->bc_target, b.Ob, e->lsums(), e->wq, b.ux); })) return rc;
         } else {
-            DISPATCH_TRAIN(b, hipLaunchKernelGGL((k_head_mix<CC, EE, false, true>), g, dim3(e->head_threads), 0, e->stream, e->ph, e->oc.mix, b.pts, b.V, b.O, b.u, b.Hu,
-                                                e->sums(), b.n, b.ld, e->n_pde, e->bc_target, b.Ob, e->lsums(), none, b.ux));
+            if (int rc = launch_ce(e, b, ce_train{}, [&](auto CC, auto EE) { hipLaunchKernelGGL((k_head_mix<CC, EE, false, true>), g, dim3(e->head_threads), 0, e->stream, e->ph, e->oc.mix, b.pts, b.V, b.O, b.u, b.Hu,
+                                                e->sums(), b.n, b.ld, e->n_pde, e->bc_target, b.Ob, e->lsums(), none, b.ux); })) return rc;
         }
     } else
     if (e->cfg.mixture) {
         if (e->wq) {
-            DISPATCH_TRAIN(b, hipLaunchKernelGGL((k_head_mix<CC, EE, true>), g, dim3(e->head_threads), 0, e->stream, e->ph, e->oc.mix, b.pts, b.V, b.O, b.u, b.Hu,
-                                                e->sums(), b.n, b.ld, e->n_pde, e->bc_target, b.Ob, e->lsums(), e->wq, (float*)nullptr));
+            if (int rc = launch_ce(e, b, ce_train{}, [&](auto CC, auto EE) { hipLaunchKernelGGL((k_head_mix<CC, EE, true>), g, dim3(e->head_threads), 0, e->stream, e->ph, e->oc.mix, b.pts, b.V, b.O, b.u, b.Hu,
+                                                e->sums(), b.n, b.ld, e->n_pde, e->bc_target, b.Ob, e->lsums(), e->wq, (float*)nullptr); })) return rc;
         } else {
-            DISPATCH_TRAIN(b, hipLaunchKernelGGL((k_head_mix<CC, EE>), g, dim3(e->head_threads), 0, e->stream, e->ph, e->oc.mix, b.pts, b.V, b.O, b.u, b.Hu,
-                                                e->sums(), b.n, b.ld, e->n_pde, e->bc_target, b.Ob, e->lsums(), none, (float*)nullptr));
+            if (int rc = launch_ce(e, b, ce_train{}, [&](auto CC, auto EE) { hipLaunchKernelGGL((k_head_mix<CC, EE>), g, dim3(e->head_threads), 0, e->stream, e->ph, e->oc.mix, b.pts, b.V, b.O, b.u, b.Hu,
+                                                e->sums(), b.n, b.ld, e->n_pde, e->bc_target, b.Ob, e->lsums(), none, (float*)nullptr); })) return rc;
         }
     } else
     if (e->wq) {      // bound quadrature weights: the weighted instance
-        DISPATCH_TRAIN(b, hipLaunchKernelGGL((k_head_pde<CC, EE, true>), g, dim3(e->head_threads), 0, e->stream, e->ph, e->base_norm, b.pts, b.V, b.O,
+        if (int rc = launch_ce(e, b, ce_train{}, [&](auto CC, auto EE) { hipLaunchKernelGGL((k_head_pde<CC, EE, true>), g, dim3(e->head_threads), 0, e->stream, e->ph, e->base_norm, b.pts, b.V, b.O,
                                             (const float* const*)e->orth_dev, b.u, b.Hu, b.ux, e->sums(), b.n, b.ld, e->n_pde,
-                                            e->bc_target, b.Ob, e->lsums(), e->wq));
+                                            e->bc_target, b.Ob, e->lsums(), e->wq); })) return rc;
     } else {
-        DISPATCH_TRAIN(b, hipLaunchKernelGGL((k_head_pde<CC, EE>), g, dim3(e->head_threads), 0, e->stream, e->ph, e->base_norm, b.pts, b.V, b.O,
+        if (int rc = launch_ce(e, b, ce_train{}, [&](auto CC, auto EE) { hipLaunchKernelGGL((k_head_pde<CC, EE>), g, dim3(e->head_threads), 0, e->stream, e->ph, e->base_norm, b.pts, b.V, b.O,
                                             (const float* const*)e->orth_dev, b.u, b.Hu, b.ux, e->sums(), b.n, b.ld, e->n_pde,
-                                            e->bc_target, b.Ob, e->lsums(), none));
+                                            e->bc_target, b.Ob, e->lsums(), none); })) return rc;
     }
     HIPCHK(e, hipGetLastError());
     return GPE_OK;
@@ -3108,32 +2957,32 @@ static int launch_seed_pde(gpe_engine* e, float* d_resid, int want_seeds, int he
     const float* none = nullptr;
     if (e->cfg.mixture && e->mix_wE != 0.f && want_seeds) {      // the seeds of the energy term ride in the EN instance
         if (e->wq) {
-            DISPATCH_TRAIN(b, hipLaunchKernelGGL((k_seed_mix<CC, EE, true, true>), g, dim3(e->head_threads), 0, e->stream, e->ph, e->oc.mix, b.pts, b.V, b.u, b.Hu,
-                                                e->sums(), b.Ob, d_resid, e->dsc(), e->n_pde, b.ld, want_seeds, e->wq, (const float*)b.ux));
+            if (int rc = launch_ce(e, b, ce_train{}, [&](auto CC, auto EE) { hipLaunchKernelGGL((k_seed_mix<CC, EE, true, true>), g, dim3(e->head_threads), 0, e->stream, e->ph, e->oc.mix, b.pts, b.V, b.u, b.Hu,
+                                                e->sums(), b.Ob, d_resid, e->dsc(), e->n_pde, b.ld, want_seeds, e->wq, (const float*)b.ux); })) return rc;
         } else {
-            DISPATCH_TRAIN(b, hipLaunchKernelGGL((k_seed_mix<CC, EE, false, true>), g, dim3(e->head_threads), 0, e->stream, e->ph, e->oc.mix, b.pts, b.V, b.u, b.Hu,
-                                                e->sums(), b.Ob, d_resid, e->dsc(), e->n_pde, b.ld, want_seeds, none, (const float*)b.ux));
+            if (int rc = launch_ce(e, b, ce_train{}, [&](auto CC, auto EE) { hipLaunchKernelGGL((k_seed_mix<CC, EE, false, true>), g, dim3(e->head_threads), 0, e->stream, e->ph, e->oc.mix, b.pts, b.V, b.u, b.Hu,
+                                                e->sums(), b.Ob, d_resid, e->dsc(), e->n_pde, b.ld, want_seeds, none, (const float*)b.ux); })) return rc;
         }
     } else
     if (e->cfg.mixture) {      // (head_slots is 0: a mixture's head never rides in the forward kernel)
         if (e->wq) {
-            DISPATCH_TRAIN(b, hipLaunchKernelGGL((k_seed_mix<CC, EE, true>), g, dim3(e->head_threads), 0, e->stream, e->ph, e->oc.mix, b.pts, b.V, b.u, b.Hu,
-                                                e->sums(), b.Ob, d_resid, e->dsc(), e->n_pde, b.ld, want_seeds, e->wq, none));
+            if (int rc = launch_ce(e, b, ce_train{}, [&](auto CC, auto EE) { hipLaunchKernelGGL((k_seed_mix<CC, EE, true>), g, dim3(e->head_threads), 0, e->stream, e->ph, e->oc.mix, b.pts, b.V, b.u, b.Hu,
+                                                e->sums(), b.Ob, d_resid, e->dsc(), e->n_pde, b.ld, want_seeds, e->wq, none); })) return rc;
         } else {
-            DISPATCH_TRAIN(b, hipLaunchKernelGGL((k_seed_mix<CC, EE>), g, dim3(e->head_threads), 0, e->stream, e->ph, e->oc.mix, b.pts, b.V, b.u, b.Hu,
-                                                e->sums(), b.Ob, d_resid, e->dsc(), e->n_pde, b.ld, want_seeds, none, none));
+            if (int rc = launch_ce(e, b, ce_train{}, [&](auto CC, auto EE) { hipLaunchKernelGGL((k_seed_mix<CC, EE>), g, dim3(e->head_threads), 0, e->stream, e->ph, e->oc.mix, b.pts, b.V, b.u, b.Hu,
+                                                e->sums(), b.Ob, d_resid, e->dsc(), e->n_pde, b.ld, want_seeds, none, none); })) return rc;
         }
     } else
     if (e->wq) {      // bound quadrature weights: the weighted instance (the head never rode in the forward kernel: head_class)
-        DISPATCH_TRAIN(b, hipLaunchKernelGGL((k_seed_pde<CC, EE, true>), g, dim3(e->head_threads), 0, e->stream, e->ph, b.pts, b.V,
+        if (int rc = launch_ce(e, b, ce_train{}, [&](auto CC, auto EE) { hipLaunchKernelGGL((k_seed_pde<CC, EE, true>), g, dim3(e->head_threads), 0, e->stream, e->ph, b.pts, b.V,
                                             (const float* const*)e->orth_dev, b.u, b.Hu, b.ux, e->sums(), b.Ob, d_resid, e->dsc(),
                                             e->n_pde, b.ld, want_seeds, head_slots ? (const double*)e->head_slots : (const double*)nullptr,
-                                            head_slots, e->sums(), e->lsums(), e->wq));
+                                            head_slots, e->sums(), e->lsums(), e->wq); })) return rc;
     } else {
-        DISPATCH_TRAIN(b, hipLaunchKernelGGL((k_seed_pde<CC, EE>), g, dim3(e->head_threads), 0, e->stream, e->ph, b.pts, b.V,
+        if (int rc = launch_ce(e, b, ce_train{}, [&](auto CC, auto EE) { hipLaunchKernelGGL((k_seed_pde<CC, EE>), g, dim3(e->head_threads), 0, e->stream, e->ph, b.pts, b.V,
                                             (const float* const*)e->orth_dev, b.u, b.Hu, b.ux, e->sums(), b.Ob, d_resid, e->dsc(),
                                             e->n_pde, b.ld, want_seeds, head_slots ? (const double*)e->head_slots : (const double*)nullptr,
-                                            head_slots, e->sums(), e->lsums(), none));      // collocation rows only; boundary rows were seeded by the head kernel
+                                            head_slots, e->sums(), e->lsums(), none); })) return rc;      // collocation rows only; boundary rows were seeded by the head kernel
     }
     HIPCHK(e, hipGetLastError());
     return GPE_OK;
@@ -3151,8 +3000,7 @@ static int step_begin(gpe_engine* e, StepOpts o) {
     if ((rc = launch_begin(e))) return rc;
     if ((rc = bc_fork(e, true))) return rc;
     // the head rides in the forward kernel, one triple per workgroup of that launch
-    const int slots = !(o.head_may_fuse && head_fusable(e)) ? 0
-                    : (int)(head_fusable_coop(e) ? fused_grid(e, e->main.n, 1, 2) : fused_grid(e, e->main.n, 4, e->fwd_wg_per_cu));
+    const int slots = o.head_may_fuse && head_fusable(e) ? (int)fwd_grid(e, e->main, head_fusable_coop(e)) : 0;
     rc = mlp_forward(e, e->main, true, nullptr, slots);
     if (!rc && !slots) rc = launch_head_pde(e);
     if (!rc && e->cfg.w_sym != 0.f) {

@@ -37,8 +37,7 @@ def test_the_conditions_compare_the_way_the_table_says():
     for text in ("e->main.n <= e->fuse_head_max", "e->main.n >= e->fuse_head_tile_min", "e->n_pde <= e->fuse_seed_max",
                  "(b.n + 15) / 16 <= e->coop_fwd_max_tiles", "(b.n + 15) / 16 >= e->wide_min_tiles",
                  "e->main.n <= e->graph_max_points", "(b.n + 15) / 16 >= e->share_min_tiles * (int64_t)grid",
-                 "(b.n + 15) / 16 >= 4 * e->share_min_tiles * (int64_t)grid", "ntiles >= 4 * e->share_min_tiles * g2",
-                 "ntiles >= e->share_min_tiles * g2", "dim3 g(head_grid(e, e->n_pde));", "dim3 g(head_grid(e, b.n));",
+                 "(b.n + 15) / 16 >= 4 * e->share_min_tiles * (int64_t)grid", "dim3 g(head_grid(e, e->n_pde));", "dim3 g(head_grid(e, b.n));",
                  "fused_grid(e, e->main.n, 1, 2) <= HEAD_SLOTS", "fused_grid(e, e->main.n, 4, e->fwd_wg_per_cu) <= HEAD_SLOTS",
                  "(seed_in_reverse(e) || deep)", "cdiv(n, OBS_THREADS), OBS_MAX_WG)", "int64_t nchunk = (b.n + chunk - 1) / chunk;",
                  "(unsigned)((nchunk + 3) / 4)"):
