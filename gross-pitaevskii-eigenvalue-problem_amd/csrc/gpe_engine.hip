@@ -65,408 +65,8 @@ static thread_local std::string g_create_error;
 static inline int64_t round_up(int64_t a, int64_t b) { return (a + b - 1) / b * b; }
 static inline unsigned cdiv(int64_t a, int64_t b) { return (unsigned)((a + b - 1) / b); }
 
-// ------------------------------------------------------------------------------------------------
-// update kernel: clip_grad_norm_ + Adam + scheduler + record   (refine/...:359-361, 364-381)
-// ------------------------------------------------------------------------------------------------
-// Large parameter vectors (P >= UPD_MULTI_MIN: [2,128x5,1] and up) run the update on UPD_G workgroups -- one workgroup took 0.40 ms
-// per step at P = 330 241.  k_update_part: per-workgroup partial sums of |g|^2 over contiguous chunks (fixed order: deterministic
-// for a given P) + a snapshot of the step sums and of the optimiser state; k_update<true>: every workgroup adds the partial sums in the
-// same order and derives the same clip factor / step size from the SNAPSHOTS (workgroup 0 alone writes the optimiser state, the
-// record and the history, and zeroes the step sums), then updates its chunk.  The repacking of the hidden-hidden weights needs ALL
-// updated parameters, so it is left to the next step's k_begin in this mode.
-#define UPD_G 64
-#define UPD_MULTI_MIN 32768
-struct UpdSnap { double sums[S_COUNT]; double lsums[LS_COUNT]; OptDev od; double part[UPD_G]; };
-GPE_DEV int upd_chunk(int P) { return (((P + UPD_G - 1) / UPD_G) + 3) & ~3; }
-static int upd_chunk_host(int P) { return (((P + UPD_G - 1) / UPD_G) + 3) & ~3; }
-__global__ __launch_bounds__(1024) void k_update_part(int P, const float* __restrict__ grad, const double* __restrict__ sums,
-                                                       const double* __restrict__ lsums, const OptDev* __restrict__ od,
-                                                       UpdSnap* __restrict__ snap) {
-    __shared__ double red[16];
-    const int chunk = upd_chunk(P), lo = blockIdx.x * chunk, hi = min(P, lo + chunk);
-    double acc = 0.0;
-    for (int i = lo + threadIdx.x; i < hi; i += 1024) { double g = grad[i]; acc += g * g; }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double tot = 0.0;
-        for (int i = 0; i < 16; ++i) tot += red[i];
-        snap->part[blockIdx.x] = tot;
-    }
-    if (blockIdx.x == 0) {
-        if (threadIdx.x < S_COUNT) snap->sums[threadIdx.x] = sums[threadIdx.x];
-        if (threadIdx.x < LS_COUNT) snap->lsums[threadIdx.x] = lsums[threadIdx.x];
-        if (threadIdx.x == 64) snap->od = *od;
-    }
-}
-
-// one Adam element, torch's op order (refine/...:359-361): shared by every update loop so that they agree bit for bit
-GPE_DEV void adam_element(float graw, float& m, float& v, float& th, float coef, float ss, float b2s, float b1, float b2, float eps) {
-#pragma clang fp contract(off)      // torch's kernels round every product before the add; and every call site must round alike
-    const float g = graw * coef;
-    m = m + (g - m) * (1.0f - b1);                 // exp_avg.lerp_(grad, 1-beta1)
-    v = v * b2 + (1.0f - b2) * g * g;              // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1-beta2)
-    const float denom = sqrtf(v) / b2s + eps;
-    th = th - ss * (m / denom);                    // param.addcdiv_(exp_avg, denom, value=-step_size)
-}
-
-// gradient element as the update reads it.  SC1 (the update runs inside the slab-reduction launch, k_reduce_update below): the values
-// were stored by OTHER workgroups of this launch with write-through (sc1) stores -- read them past this CU's L1
-template <bool SC1>
-GPE_DEV float grad_load(const float* p) {
-    if constexpr (SC1) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else return *p;
-}
-
-// W_j[n][kk] of a hidden-hidden map -> its slots in the two packed copies (pack_weight_element inverted): the update SCATTERS the new
-// weights instead of a gather pass behind a barrier
-GPE_DEV void scatter_pack(const NetDesc& nd, int H, int i, float th, float* __restrict__ Wpk, float* __restrict__ WpkT) {
-    const int lg = H == 64 ? 6 : (H == 32 ? 5 : (H == 128 ? 7 : 8)), NT = H >> 4, maps = nd.n_lin - 2;
-    for (int j = 1; j <= maps; ++j) {
-        const int e = i - nd.offW[j];
-        if (e >= 0 && e < H * H) {
-            const int n = e >> lg, kk = e & (H - 1);
-            const int nt = n >> 4, kt = kk >> 4;
-            Wpk[(((j - 1) * NT + nt) * NT + kt) * 256 + ((n & 15) + 16 * ((kk & 15) >> 2)) * 4 + (kk & 3)] = th;
-            WpkT[(((j - 1) * NT + kt) * NT + nt) * 256 + ((kk & 15) + 16 * ((n & 15) >> 2)) * 4 + (n & 3)] = th;
-        }
-    }
-}
-
-template <bool MULTI, bool SC1 = false>
-GPE_DEV void update_core(int P, float* __restrict__ theta, float* __restrict__ am,
-                         float* __restrict__ av, const float* __restrict__ grad,
-                         const double* __restrict__ sums_in, const double* __restrict__ lsums_in,
-                         const Phys& ph, const OptCfg& oc, OptDev* __restrict__ od,
-                         gpe_scalars* __restrict__ hist, int cap, gpe_scalars* __restrict__ last,
-                         double bc_cnt, int do_update, int mse_mode, const NetDesc& nd, int H,
-                         float* __restrict__ Wpk, float* __restrict__ WpkT, int n_pack,
-                         double* __restrict__ dbl, int n_dbl, double* __restrict__ dbl_keep,
-                         const UpdSnap* __restrict__ snap, int pack_mode) {
-    // pack_mode (one workgroup): 1 = repack the hidden-hidden weights by a gather pass over the updated parameters (also writes the
-    // bf16 pieces the opt-in split-bf16 kernels read); 2 = every thread SCATTERS its updated weights into the two packed copies inside
-    // the Adam loop (no second pass, no barrier, no bf16 pieces).  REG_E: up to this many elements per thread are loaded ONCE, at the
-    // top, into registers (gradient for the norm, Adam moments and parameters behind it): at the reference's batch sizes this kernel
-    // is a chain of dependent round trips to L2 -- it took 16.6 us of a 52 us step at 4 000 points -- and every load issued early is
-    // one round trip less.
-    constexpr int REG_E = 13;                                 // (13 312 parameters: the 4 x 64 networks of BASELINE; 16 would spill at 128 registers)
-    const bool cached = !MULTI && P <= REG_E * 1024 && !(pack_mode & 4);      // (bit 2 of pack_mode: tuning switch GPE_UPDATE_CACHE=0)
-    pack_mode &= 3;
-    float cg[REG_E], cm[REG_E], cv[REG_E], ct[REG_E];
-    __shared__ double red[16];
-    __shared__ float s_coef, s_ss, s_b2s;
-    __shared__ int s_skip, s_book, s_frozen;
-    __shared__ long long s_step;
-    __shared__ gpe_scalars s_rec;
-    const double* sums = MULTI ? snap->sums : sums_in;
-    const double* lsums = MULTI ? snap->lsums : lsums_in;
-    const OptDev* odr = MULTI ? &snap->od : od;                    // state the step size is derived from
-    const bool lead = !MULTI || blockIdx.x == 0;                   // the workgroup that writes the optimiser state / record / history
-    const int lo = MULTI ? blockIdx.x * upd_chunk(P) : 0, hi = MULTI ? min(P, lo + upd_chunk(P)) : P;
-    // the scalars thread 0 needs behind the norm are requested NOW, beside the elements: one round trip less in its serial section
-    double p_num = 0.0, p_den = 0.0, p_bcse = 0.0, p_lr = 0.0, p_b1p = 0.0, p_b2p = 0.0;
-    float p_sr2 = 0.f;
-    long long p_step = 0;
-    int p_stopped = 0;
-    if (threadIdx.x == 0) {
-        p_num = sums[S_NUM]; p_den = sums[S_DEN]; p_bcse = lsums[LS_BC_SE2]; p_sr2 = grad_load<SC1>(&grad[P + GT_SUM_R2]);
-        p_lr = odr->lr; p_b1p = odr->b1p; p_b2p = odr->b2p; p_step = odr->step; p_stopped = odr->stopped;
-    }
-    // mixture energy term: in the single-workgroup forms E is formed by the first thread of wave 1 ahead of the barrier below -- inside thread
-    // 0's serial section, the kernel's register peak, it cost four more spilled VGPRs and 0.7 % of the headline step
-    const bool mix_en = oc.mix.on && oc.mix.wE != 0.f;
-    __shared__ double s_mixE;
-    if constexpr (!MULTI) {
-        if (mix_en && threadIdx.x == 64) s_mixE = mix_energy_of(oc.mix.g, oc.mix.n, (double)ph.dx, sums).E;
-        double acc = 0.0;
-        if (cached) {
-#pragma unroll
-            for (int k = 0; k < REG_E; ++k) { const int i = threadIdx.x + k * 1024; cg[k] = i < P ? grad_load<SC1>(&grad[i]) : 0.f; }
-#pragma unroll
-            for (int k = 0; k < REG_E; ++k) {
-                const int i = threadIdx.x + k * 1024;
-                if (i < P) { cm[k] = am[i]; cv[k] = av[i]; ct[k] = theta[i]; }
-            }
-#pragma unroll
-            for (int k = 0; k < REG_E; ++k) { const double g = cg[k]; acc += g * g; }          // (same order as the loop below)
-        } else
-        for (int i = threadIdx.x; i < P; i += 1024) { double g = grad_load<SC1>(&grad[i]); acc += g * g; }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        double tot = 0.0;
-        if constexpr (MULTI) { for (int i = 0; i < UPD_G; ++i) tot += snap->part[i]; }
-        else { for (int i = 0; i < 16; ++i) tot += red[i]; }
-        double gn = sqrt(tot);
-        double num = p_num, den = p_den;
-        double lam = (double)(float)lambda_of(ph, sums, num, den);
-        double I = (double)((float)den * ph.dx);
-        double sr2 = (double)p_sr2;
-        double pde = sr2 / ph.n_global;
-        double nrm = (I - 1.0) * (I - 1.0);
-        if (oc.mix.on) {                  // two real components: one Rayleigh quotient and one norm term each; the record carries component 1
-            const double num2 = sums[S_MIX_NUM2], den2 = sums[S_MIX_DEN2];
-            const double lam2 = (double)(float)(num2 / den2), I2 = (double)((float)den2 * ph.dx);
-            lam = (double)(float)(num / den);
-            const double d1 = I - (double)oc.mix.n[0], d2 = I2 - (double)oc.mix.n[1];
-            nrm = d1 * d1 + d2 * d2;
-            if (lead && !mse_mode && !(do_update && p_stopped)) {
-                od->mix[0] = lam; od->mix[1] = lam2; od->mix[2] = I; od->mix[3] = I2;
-                od->mix[4] = num; od->mix[5] = den; od->mix[6] = num2; od->mix[7] = den2;
-            }
-        }
-        double bc = bc_cnt > 0 ? p_bcse / bc_cnt : 0.0;
-        double sym = ph.w_sym != 0.f ? sums[S_SYM] / ph.n_global : 0.0;
-        double orth = 0.0;
-        for (int j = 0; j < ph.n_orth; ++j) { double oj = sums[S_ORTH0 + j] * ph.dx; orth += oj * oj; }
-        double riesz = 0.0;
-        if (ph.w_riesz != 0.f) {          // (the sums are also filed for the energy-functional lambda; the TERM only with its weight)
-            const double fI = ph.riesz_kind == GPE_RIESZ_VARIATIONAL ? pow(I, -0.5 * (double)(ph.p - 1)) : 1.0;
-            const double Lrot = ph.complex_psi ? (double)ph.omega_rot * sums[S_RZ_L] : 0.0;      // rotating frame: - Omega <L_z>
-            riesz = (sums[S_RZ_K] + sums[S_RZ_P] + fI * sums[S_RZ_I] - Lrot) / (ph.riesz_kind == GPE_RIESZ_SUM ? 1.0 : den);
-        }
-        double reg = reg_terms(ph, den, lam);
-        double loss = ph.w_pde * pde + ph.w_bc * bc + ph.w_norm * nrm + ph.w_sym * sym + ph.w_orth * orth + ph.w_riesz * riesz + reg;
-        if (mix_en) {        // mixture energy term: E of the state normalised to the target norms, reported as riesz
-            if constexpr (MULTI) riesz = mix_energy_of(oc.mix.g, oc.mix.n, (double)ph.dx, sums).E;
-            else riesz = s_mixE;
-            loss += (double)oc.mix.wE * riesz;
-        }
-        if (mse_mode) {           // pre-training: loss = mean((NN - target)^2); plain Adam (no clip, no scheduler, no early stop)
-            loss = (double)grad_load<SC1>(&grad[P + GT_MSE_SE2]) / (ph.n_global * ph.n_out);
-            lam = 0.0; pde = 0.0; nrm = 0.0; bc = 0.0; sym = 0.0; orth = 0.0; riesz = 0.0; reg = 0.0;
-        }
-        int skip = !(isfinite(loss) && isfinite(gn));
-        const int frozen = do_update && p_stopped;
-        long long step = p_step + (do_update && !skip && !frozen ? 1 : 0);
-        double lr = p_lr;
-        float coef = 1.0f;
-        if (oc.clip_norm > 0.f && !mse_mode) coef = (float)fmin(1.0, (double)oc.clip_norm / (gn + 1e-6));
-        const bool commit = do_update && !skip && !frozen;
-        const double b1p = commit ? p_b1p * (double)oc.beta1 : p_b1p, b2p = commit ? p_b2p * (double)oc.beta2 : p_b2p;
-        if (commit && lead) { od->b1p = b1p; od->b2p = b2p; }
-        double bc1 = 1.0 - b1p;
-        double bc2 = 1.0 - b2p;
-        s_coef = coef;
-        s_ss = (float)(lr / bc1);
-        s_b2s = (float)sqrt(bc2);
-        s_skip = skip || !do_update || frozen;
-        gpe_scalars r;
-        r.loss = loss; r.pde = pde; r.bc = bc; r.norm = nrm; r.sym = sym; r.orth = orth; r.mu = lam;
-        r.num = num; r.den = den; r.sum_r2 = sr2; r.integral = I; r.grad_norm = gn; r.lr = lr;
-        r.step = (double)step; r.nonfinite = skip ? 1.0 : 0.0; r.riesz = riesz; r.reg = reg;
-        s_rec = r; s_step = step; s_frozen = frozen; s_book = 1;
-    }
-    __syncthreads();
-    // bookkeeping (record, history, early stop, scheduler: double-precision log / pow / cos) on the last thread, concurrently
-    // with the Adam loop of the others
-    if (threadIdx.x == 1023 && s_book && lead) {
-        const gpe_scalars r = s_rec;
-        const long long step = s_step;
-        const int frozen = s_frozen, skip = r.nonfinite != 0.0;
-        const double loss = r.loss;
-        if (!frozen) *last = r;
-        if (do_update && !frozen) {
-            if (!skip) {
-                hist[(step - 1) % cap] = r;
-                od->step = step;
-                if (mse_mode) { /* no scheduler / early-stop bookkeeping while pre-training */ }
-                else {
-                // early stopping bookkeeping (refine/...:366-372, 389-400)
-                if (loss < od->es_best) { od->es_best = loss; od->es_count = 0; } else od->es_count += 1;
-                if ((oc.stop_tol > 0.f && loss <= (double)oc.stop_tol) ||
-                    (oc.stop_patience > 0 && od->es_count >= oc.stop_patience)) { od->stopped = 1; od->stop_step = step; }
-                // scheduler.step(total_loss)
-                if (oc.sched == GPE_SCHED_COSINE_LOSS) {           // quirk Q4: the loss value is the epoch
-                    double epoch = (double)(float)loss, T_cur, T_i;
-                    if (epoch >= oc.T_0) {
-                        if (oc.T_mult == 1.0f) { T_cur = fmod(epoch, (double)oc.T_0); T_i = oc.T_0; }
-                        else {
-                            int n = (int)(log(epoch / oc.T_0 * (oc.T_mult - 1.0) + 1.0) / log((double)oc.T_mult));
-                            T_cur = epoch - oc.T_0 * (pow((double)oc.T_mult, n) - 1.0) / (oc.T_mult - 1.0);
-                            T_i = oc.T_0 * pow((double)oc.T_mult, n);
-                        }
-                    } else { T_i = oc.T_0; T_cur = epoch; }
-                    od->lr = oc.eta_min + (od->lr0 - oc.eta_min) * (1.0 + cos(M_PI * T_cur / T_i)) / 2.0;
-                } else if (oc.sched == GPE_SCHED_PLATEAU) {        // ReduceLROnPlateau(mode='min', rel threshold)
-                    if (loss < od->best * (1.0 - oc.threshold)) { od->best = loss; od->num_bad = 0; }
-                    else od->num_bad += 1;
-                    if (od->num_bad > oc.patience) {
-                        double nl = fmax(od->lr * oc.factor, (double)oc.min_lr);
-                        if (od->lr - nl > 1e-8) od->lr = nl;
-                        od->num_bad = 0;
-                    }
-                }
-                }
-            } else {
-                od->nonfinite = 1;
-            }
-        }
-    }
-    if (!s_skip && cached) {
-        const float coef = s_coef, ss = s_ss, b2s = s_b2s;
-        const float b1 = oc.beta1, b2 = oc.beta2, eps = oc.eps;
-#pragma unroll
-        for (int k = 0; k < REG_E; ++k) {
-            const int i = threadIdx.x + k * 1024;
-            if (i < P) {
-                float m = cm[k], v = cv[k], th = ct[k];
-                adam_element(cg[k], m, v, th, coef, ss, b2s, b1, b2, eps);
-                theta[i] = th;
-                am[i] = m; av[i] = v;
-                if (pack_mode == 2 && n_pack > 0) scatter_pack(nd, H, i, th, Wpk, WpkT);
-            }
-        }
-    } else if (!s_skip) {
-        const float coef = s_coef, ss = s_ss, b2s = s_b2s;
-        const float b1 = oc.beta1, b2 = oc.beta2, eps = oc.eps;
-        for (int i = lo + threadIdx.x; i < hi; i += 1024) {
-            float m = am[i], v = av[i], th = theta[i];
-            adam_element(grad_load<SC1>(&grad[i]), m, v, th, coef, ss, b2s, b1, b2, eps);
-            theta[i] = th;
-            am[i] = m; av[i] = v;
-            if (MULTI && pack_mode == 2 && n_pack > 0) scatter_pack(nd, H, i, th, Wpk, WpkT);      // (small networks on the split update)
-        }
-    }
-    // Prepare the NEXT step, so that it can start with its forward kernel: the step sums are consumed (thread 0 read them
-    // before the barrier above) -> zero them; repack the hidden-hidden weights in MFMA fragment order from the new parameters.
-    __syncthreads();
-    // (stale-gradient mode: this step's sums are kept for the NEXT update, which applies this step's gradient)
-    if (lead) for (int i = threadIdx.x; i < n_dbl; i += 1024) { if (dbl_keep) dbl_keep[i] = dbl[i]; dbl[i] = 0.0; }
-    if constexpr (!MULTI) {
-        if (pack_mode != 2 || !cached || s_skip)                  // (a skipped update leaves the parameters, and with them the packed copies, as they were -- but a repack is harmless)
-            for (int i = threadIdx.x; i < n_pack; i += 1024) pack_weight_element(nd, H, theta, Wpk, WpkT, i);
-    }
-}
-
-template <bool MULTI>
-__global__ __launch_bounds__(1024) void k_update(int P, float* __restrict__ theta, float* __restrict__ am,
-                                                  float* __restrict__ av, const float* __restrict__ grad,
-                                                  const double* __restrict__ sums_in, const double* __restrict__ lsums_in,
-                                                  Phys ph, OptCfg oc, OptDev* __restrict__ od,
-                                                  gpe_scalars* __restrict__ hist, int cap, gpe_scalars* __restrict__ last,
-                                                  double bc_cnt, int do_update, int mse_mode, NetDesc nd, int H,
-                                                  float* __restrict__ Wpk, float* __restrict__ WpkT, int n_pack,
-                                                  double* __restrict__ dbl, int n_dbl, double* __restrict__ dbl_keep,
-                                                  const UpdSnap* __restrict__ snap, int pack_mode) {
-    update_core<MULTI>(P, theta, am, av, grad, sums_in, lsums_in, ph, oc, od, hist, cap, last, bc_cnt, do_update, mse_mode, nd, H,
-                       Wpk, WpkT, n_pack, dbl, n_dbl, dbl_keep, snap, pack_mode);
-}
-
-// closes the reverse phase: adds the boundary-batch gradient (computed on the side stream) and fills the exchange tail
-__global__ void k_tail(float* __restrict__ grad, const float* __restrict__ add, int P, const double* dsc) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (add && i < P) grad[i] += add[i];
-    if (i == 0) { grad[P + GT_SUM_R2] = (float)dsc[0]; grad[P + GT_MSE_SE2] = (float)dsc[2]; }
-}
-
-// Slab reduction AND update in one launch (small parameter vectors, whole steps: gpe_step / gpe_run).  At the reference's batch sizes
-// the update was a launch of its own whose ONE workgroup started only when the whole reduction grid had drained: 2.6 us of launch plus a
-// chain of dependent L2 round trips (10.4 of a 40.5 us step at 4 000 points).  Here every workgroup reduces its 64 columns as
-// k_grad_reduce does and stores them write-through (sc1: no L2 write-back fence -- the release fence in every workgroup is what made the
-// round-3 attempt at this fusion slower), takes a ticket, and the workgroup whose ticket is the last runs the single-workgroup update on
-// the spot, reading the gradient past its L1 (hand-off form of MI355X_MICROARCH.md, "Valid forms": sc1 stores, every storing wave's
-// vmcnt(0), workgroup barrier, one agent-scope atomic add per workgroup, the last adder loads sc1 behind a barrier).  Same arithmetic in
-// the same order as k_grad_reduce + k_update<false>: bit-identical results (test_update_kernel_forms_are_bit_identical).
-__global__ __launch_bounds__(1024) void k_reduce_update(const float* __restrict__ gslab, int nslab, int Ppad, int P, float* __restrict__ grad,
-                                                         const float* __restrict__ add, const double* __restrict__ tail_dsc,
-                                                         unsigned* __restrict__ ticket,
-                                                         float* __restrict__ theta, float* __restrict__ am, float* __restrict__ av,
-                                                         const double* __restrict__ sums_in, const double* __restrict__ lsums_in,
-                                                         Phys ph, OptCfg oc, OptDev* __restrict__ od, gpe_scalars* __restrict__ hist, int cap,
-                                                         gpe_scalars* __restrict__ last, double bc_cnt, NetDesc nd, int H,
-                                                         float* __restrict__ Wpk, float* __restrict__ WpkT, int n_pack,
-                                                         double* __restrict__ dbl, int n_dbl, int pack_mode) {
-    __shared__ float red[16][64];
-    __shared__ int s_last;
-    const int lane = threadIdx.x & 63, g = threadIdx.x >> 6;
-    const int i = blockIdx.x * 64 + lane;
-    const float s = i < P ? slab_column_sum(gslab, nslab, Ppad, i, g) : 0.f;
-    red[g][lane] = s;
-    __syncthreads();
-    if (g == 0 && i < P) {
-        float t = 0.f;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) t += red[k][lane];
-        if (add) t += add[i];
-        __hip_atomic_store(&grad[i], t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        __hip_atomic_store(&grad[P + GT_SUM_R2], (float)tail_dsc[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(&grad[P + GT_MSE_SE2], (float)tail_dsc[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // every storing wave: its stores have left the CU
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const unsigned old = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        s_last = old == gridDim.x - 1;
-        if (s_last) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);       // every other workgroup has drawn: ready for the next launch
-    }
-    __syncthreads();
-    if (!s_last) return;
-    update_core<false, true>(P, theta, am, av, grad, sums_in, lsums_in, ph, oc, od, hist, cap, last, bc_cnt, 1, 0, nd, H, Wpk, WpkT, n_pack, dbl,
-                             n_dbl, nullptr, nullptr, pack_mode);
-}
-
-// Slab reduction of SMALL parameter vectors for whole steps (gpe_step / gpe_run), in the partition of the multi-workgroup update: UPD_G
-// workgroups, workgroup b owns the parameters [b chunk, (b+1) chunk), chunk = upd_chunk(P) <= 1024.  Besides the gradient it leaves what
-// k_update_part would: the partial sums of |g|^2 (fixed order) and the snapshot of the step sums / optimiser state -- so the update that
-// follows is k_update<true> on UPD_G workgroups, a handful of elements per thread, instead of ONE workgroup walking all P parameters through
-// a chain of dependent L2 round trips (10.4 us of a 40.5 us step at 4 000 points).  Threads: column = t % chunk, slab group = t / chunk.
-__global__ __launch_bounds__(1024) void k_grad_reduce_part(const float* __restrict__ gslab, int nslab, int Ppad, int P, float* __restrict__ grad,
-                                                            const float* __restrict__ add, const double* __restrict__ tail_dsc,
-                                                            const double* __restrict__ sums, const double* __restrict__ lsums,
-                                                            const OptDev* __restrict__ od, UpdSnap* __restrict__ snap) {
-    __shared__ float red[1024];
-    __shared__ double red2[16];
-    const int chunk = upd_chunk(P), lo = blockIdx.x * chunk;
-    const int ng = 1024 / chunk;                                  // slab groups (>= 1: chunk <= 1024 is checked by the launcher)
-    const int col = threadIdx.x % chunk, grp = threadIdx.x / chunk;
-    const int i = lo + col;
-    float s = 0.f;
-    if (grp < ng && i < P) {
-        float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;            // four loads in flight per thread (fixed order of the final sum)
-        int b = grp;
-        for (; b + 3 * ng < nslab; b += 4 * ng) {
-            s0 += gslab[(size_t)b * Ppad + i];
-            s1 += gslab[(size_t)(b + ng) * Ppad + i];
-            s2 += gslab[(size_t)(b + 2 * ng) * Ppad + i];
-            s3 += gslab[(size_t)(b + 3 * ng) * Ppad + i];
-        }
-        for (; b < nslab; b += ng) s0 += gslab[(size_t)b * Ppad + i];
-        s = (s0 + s1) + (s2 + s3);
-    }
-    red[threadIdx.x] = s;
-    __syncthreads();
-    double gsq = 0.0;
-    if (grp == 0 && i < P) {
-        float t = 0.f;
-        for (int k = 0; k < ng; ++k) t += red[k * chunk + col];
-        if (add) t += add[i];
-        grad[i] = t;
-        gsq = (double)t * (double)t;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) gsq += __shfl_down(gsq, o, 64);
-    if ((threadIdx.x & 63) == 0) red2[threadIdx.x >> 6] = gsq;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double tot = 0.0;
-        for (int k = 0; k < 16; ++k) tot += red2[k];
-        snap->part[blockIdx.x] = tot;
-    }
-    if (blockIdx.x == 0) {
-        if (threadIdx.x < S_COUNT) snap->sums[threadIdx.x] = sums[threadIdx.x];
-        if (threadIdx.x < LS_COUNT) snap->lsums[threadIdx.x] = lsums[threadIdx.x];
-        if (threadIdx.x == 64) snap->od = *od;
-        if (threadIdx.x == 65) { grad[P + GT_SUM_R2] = (float)tail_dsc[0]; grad[P + GT_MSE_SE2] = (float)tail_dsc[2]; }
-    }
-}
+#include "gpe_update.h"
+#define DBL_COUNT (S_COUNT + LS_COUNT + 4)      // doubles of gpe_engine::dbl: [S_COUNT sums | LS_COUNT local | 4 misc]
 
 // ------------------------------------------------------------------------------------------------
 struct Batch {
@@ -634,29 +234,33 @@ struct gpe_engine {
     int num_cu = 256;
     int head_wg_per_cu = 1;        // head / seed kernels: workgroups per CU (each ends in one double atomic per global sum: ~22 ns apiece at one address)
     int head_threads = 1024;       // ... and threads per workgroup (GPE_HEAD_THREADS; 256 x 2 per CU until round 3: half the loads in flight, twice the atomics)
-    // ---- data-parallel exchange inside the engine: RCCL on a dedicated stream (gpe_comm_init) ----
-    struct Rccl {
-        void* dl = nullptr;
-        ncclResult_t (*GetUniqueId)(ncclUniqueId*) = nullptr;
-        ncclResult_t (*CommInitRank)(ncclComm_t*, int, ncclUniqueId, int) = nullptr;
-        ncclResult_t (*CommDestroy)(ncclComm_t) = nullptr;
-        ncclResult_t (*AllReduce)(const void*, void*, size_t, ncclDataType_t, ncclRedOp_t, ncclComm_t, hipStream_t) = nullptr;
-        const char* (*GetErrorString)(ncclResult_t) = nullptr;
-    } rccl;
-    ncclComm_t comm = nullptr;
-    int comm_rank = 0, comm_world = 1;
-    hipStream_t comm_stream = nullptr;
-    hipEvent_t ev_x0 = nullptr, ev_x1 = nullptr;      // compute -> exchange, exchange -> compute
-    std::vector<hipEvent_t> ev_bucket;                // one per linear map: its gradient slice is final
-    // opt-in one-step-stale gradient (gpe_comm_set_async): the all-reduce of g_t runs on the exchange stream behind the forward of
-    // step t+1, whose update applies g_t; changes the trajectory -- never on by default
-    bool async_grad = false;
-    float* grad_alt = nullptr;                        // second gradient buffer (P + GT_COUNT)
-    double* dbl_prev = nullptr;                       // sums of the step whose gradient is in flight
-    hipEvent_t ev_g[2] = {nullptr, nullptr};
-    int64_t async_t = 0;
-    int64_t dp_collectives = 0;                       // all-reduces issued since gpe_comm_init (bench / tests)
-    bool dp_inline = true;                            // synchronous step on the fused / wide sets: collectives on the compute stream (GPE_DP_INLINE=0: exchange stream)
+    // ---- data-parallel exchange inside the engine: RCCL on a dedicated stream (gpe_comm_init); gpe_comm_destroy resets all of it ----
+    struct Dp {
+        struct Rccl {
+            void* dl = nullptr;
+            ncclResult_t (*GetUniqueId)(ncclUniqueId*) = nullptr;
+            ncclResult_t (*CommInitRank)(ncclComm_t*, int, ncclUniqueId, int) = nullptr;
+            ncclResult_t (*CommDestroy)(ncclComm_t) = nullptr;
+            ncclResult_t (*AllReduce)(const void*, void*, size_t, ncclDataType_t, ncclRedOp_t, ncclComm_t, hipStream_t) = nullptr;
+            const char* (*GetErrorString)(ncclResult_t) = nullptr;
+        } rccl;
+        ncclComm_t comm = nullptr;
+        int rank = 0, world = 1;
+        hipStream_t stream = nullptr;                     // the exchange stream
+        hipEvent_t ev_x0 = nullptr, ev_x1 = nullptr;      // compute -> exchange, exchange -> compute
+        std::vector<hipEvent_t> ev_bucket;                // one per linear map: its gradient slice is final
+        // opt-in one-step-stale gradient (gpe_comm_set_async): the all-reduce of g_t runs on the exchange stream behind the forward of
+        // step t+1, whose update applies g_t; changes the trajectory -- never on by default
+        bool async_grad = false;
+        float* grad_alt = nullptr;                        // second gradient buffer (P + GT_COUNT)
+        double* dbl_prev = nullptr;                       // sums of the step whose gradient is in flight
+        hipEvent_t ev_g[2] = {nullptr, nullptr};
+        int64_t async_t = 0;
+        int64_t collectives = 0;                          // all-reduces issued since gpe_comm_init (bench / tests)
+        bool inline_sync = true;                          // synchronous step on the fused / wide sets: collectives on the compute stream (GPE_DP_INLINE=0: exchange stream)
+        bool on() const { return comm != nullptr; }
+        bool async() const { return async_grad; }
+    } dp;
     // ---- observables (gpe_observe.h) ----
     const ObsKind* obs_kind = nullptr;                // the engine's kind of record, chosen at the create for life
     double* obs_buf = nullptr;                        // [pass-1 slab | pass-2 slab | raw totals], allocated on first use
@@ -736,7 +340,7 @@ struct gpe_engine {
     std::string err;
     double* sums() { return dbl; }
     double* lsums() { return dbl + S_COUNT; }
-    double* dsc() { return dbl + S_COUNT + LS_COUNT; }
+    double* dsc() { return dbl + DBL_COUNT - 4; }
 };
 
 // Every launcher enqueues on e->stream and writes the gradient through e->grad / e->gslab.  The boundary batch (side stream, grad_bc),
@@ -768,6 +372,14 @@ static int dev_alloc(gpe_engine* e, Batch* b, T** out, size_t count) {
     HIPCHK(e, hipMemsetAsync(p, 0, count * sizeof(T) + 256, e->stream));
     if (b) b->allocs.push_back(p);
     *out = (T*)p;
+    return GPE_OK;
+}
+
+// one device record as the work enqueued so far leaves it, to the host -- or replaced from the host; every reader and writer synchronises here
+template <typename T>
+static int record_copy(gpe_engine* e, T* dst, const T* src, hipMemcpyKind kind) {
+    HIPCHK(e, hipMemcpyAsync(dst, src, sizeof(T), kind, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
     return GPE_OK;
 }
 
@@ -1070,11 +682,12 @@ static size_t fused_bwd_lds(gpe_engine* e, int C, int kind) {
            (w ? fused_w_bytes(e) : 0);
 }
 
+// elements of a packed copy of the hidden-hidden weights (fused path; the generic set packs nothing)
+static int pack_count(const gpe_engine* e) { return e->path == GPE_PATH_FUSED ? (e->nd.n_lin - 2) * e->H * e->H : 0; }
+
 static int ensure_packed(gpe_engine* e) {
     if (e->path != GPE_PATH_FUSED || !e->packed_dirty) return GPE_OK;
-    const int L = e->nd.n_lin - 1;
-    int total = (L - 1) * e->H * e->H;
-    hipLaunchKernelGGL(k_pack_weights, dim3(cdiv(total, 256)), dim3(256), 0, e->stream, e->nd, e->H, e->theta, e->Wpk,
+    hipLaunchKernelGGL(k_pack_weights, dim3(cdiv(pack_count(e), 256)), dim3(256), 0, e->stream, e->nd, e->H, e->theta, e->Wpk,
                        e->WpkT);
     HIPCHK(e, hipGetLastError());
     e->packed_dirty = false;
@@ -1086,9 +699,8 @@ static int launch_begin(gpe_engine* e, bool force = false) {
     // fused path: k_update zeroed the sums and repacked the weights, and the first slab reduction assigns -> nothing to do
     if (!force && e->path == GPE_PATH_FUSED && e->acc_clean && !e->packed_dirty) { e->acc_clean = false; return GPE_OK; }
     e->acc_clean = false;
-    int n_pack = 0;
-    if (e->path == GPE_PATH_FUSED && e->packed_dirty) n_pack = (e->nd.n_lin - 2) * e->H * e->H;
-    const int n_dbl = S_COUNT + LS_COUNT + 4, n_grad = e->P + GT_COUNT, n_bc = e->P;
+    const int n_pack = e->packed_dirty ? pack_count(e) : 0;
+    const int n_dbl = DBL_COUNT, n_grad = e->P + GT_COUNT, n_bc = e->P;
     const int n = std::max(std::max(n_pack, n_dbl), n_grad);
     hipLaunchKernelGGL(k_begin, dim3(cdiv(n, 256)), dim3(256), 0, e->stream, e->nd, e->H, e->theta, e->Wpk, e->WpkT, n_pack,
                        e->dbl, n_dbl, e->grad, n_grad, e->grad_bc, n_bc);
@@ -1175,7 +787,18 @@ static int mlp_forward(gpe_engine* e, Batch& b, bool store, const FwdWeights* fr
 static int bc_join(gpe_engine* e);
 static double bc_count(gpe_engine* e);
 static int launch_tail(gpe_engine* e, bool add_bc);
-static int dp_allreduce_after(gpe_engine* e, void* buf, size_t count, ncclDataType_t dt, hipEvent_t ev);
+static int dp_allreduce(gpe_engine* e, void* buf, size_t count, ncclDataType_t dt, hipEvent_t behind);
+// pack_mode of the single-workgroup update (update_core): 1 gather pass, 2 scatter in the Adam loop; bits 0 and 2: GPE_UPDATE_CACHE=0
+static int update_pack_mode(const gpe_engine* e) { return ((e->fwd_b6 || e->bwd_b6 || e->H > 64) ? 1 : 2) | (e->update_cache ? 0 : 5); }
+// whole steps on small parameter vectors: the slab reduction that closes the step runs the update itself (k_reduce_update) ...
+static bool reduce_runs_update(const gpe_engine* e, const BwdOpts& o) {
+    return o.close && o.assign && o.update_may_fuse && e->fuse_update && e->upd_ticket && !e->upd_snap && e->update_cache && e->P <= UPD_REG_E * 1024 && !e->dp.on();
+}
+// ... or leaves partial norms and the snapshot for the update on UPD_G workgroups (k_grad_reduce_part)
+static bool reduce_leaves_parts(const gpe_engine* e, const BwdOpts& o) {
+    return o.close && o.assign && o.update_may_fuse && e->split_update && e->upd_snap_small && !e->upd_snap && !e->dp.on() && !e->ext_exchange &&
+           !e->fwd_b6 && !e->bwd_b6 && e->H <= 64;
+}
 // Gradient of one batch into e->grad: assigned (first reverse pass of the step) or accumulated.  o.close: this is the last reverse pass of the step -- join the boundary batch's side stream, add its
 // gradient and write the exchange tail (folded into the slab reduction on the fused path)
 static int mlp_backward(gpe_engine* e, Batch& b, const BwdOpts& o) {
@@ -1217,15 +840,13 @@ static int mlp_backward(gpe_engine* e, Batch& b, const BwdOpts& o) {
             if (e->st.bc_inflight) add = e->grad_bc;
             e->st.bc_inflight = false;
         }
-        if (close && assign && o.update_may_fuse && e->fuse_update && e->upd_ticket && !e->upd_snap && e->update_cache && e->P <= 13 * 1024 && !e->comm) {
-            const int n_pack = (e->nd.n_lin - 2) * e->H * e->H;
+        if (reduce_runs_update(e, o)) {
             hipLaunchKernelGGL(k_reduce_update, dim3(cdiv(e->P, 64)), dim3(1024), 0, e->stream, e->gslab, nred, e->Ppad, e->P, e->grad, add,
                                (const double*)e->dsc(), e->upd_ticket, e->theta, e->am, e->av, (const double*)e->sums(), (const double*)e->lsums(),
-                               e->ph, e->oc, e->od, e->hist, e->cap, e->last, bc_count(e), e->nd, e->H, e->Wpk, e->WpkT, n_pack, e->dbl,
-                               (int)(S_COUNT + LS_COUNT + 4), ((e->fwd_b6 || e->bwd_b6 || e->H > 64) ? 1 : 2));
+                               e->ph, e->oc, e->od, e->hist, e->cap, e->last, bc_count(e), e->nd, e->H, e->Wpk, e->WpkT, pack_count(e), e->dbl,
+                               (int)DBL_COUNT, update_pack_mode(e));
             e->st.update_done = true;
-        } else if (close && assign && o.update_may_fuse && e->split_update && e->upd_snap_small && !e->upd_snap && !e->comm && !e->ext_exchange &&
-                   !e->fwd_b6 && !e->bwd_b6 && e->H <= 64) {
+        } else if (reduce_leaves_parts(e, o)) {
             hipLaunchKernelGGL(k_grad_reduce_part, dim3(UPD_G), dim3(1024), 0, e->stream, e->gslab, nred, e->Ppad, e->P, e->grad, add,
                                (const double*)e->dsc(), (const double*)e->sums(), (const double*)e->lsums(), (const OptDev*)e->od, e->upd_snap_small);
             e->st.update_parts = true;
@@ -1280,7 +901,7 @@ static int mlp_backward(gpe_engine* e, Batch& b, const BwdOpts& o) {
             if (o.bucketed && close) {
                 // data-parallel step: this map's gradient slice (weights + bias, contiguous) is final -> all-reduce it on the
                 // exchange stream behind the remaining reverse pass (output map first)
-                int rcb = dp_allreduce_after(e, e->grad + nd.offW[lin], (size_t)K * Ho + Ho, ncclFloat, e->ev_bucket[lin]);
+                int rcb = dp_allreduce(e, e->grad + nd.offW[lin], (size_t)K * Ho + Ho, ncclFloat, e->dp.ev_bucket[lin]);
                 if (rcb) return rcb;
             }
             if (lin > 0) {
@@ -1665,7 +1286,7 @@ static int alloc_state(gpe_engine* e, const AllocSwitches& sw) {
     };
     bool ok = alloc((void**)&e->theta, (size_t)e->P * 4) && alloc((void**)&e->am, (size_t)e->P * 4) &&
               alloc((void**)&e->av, (size_t)e->P * 4) && alloc((void**)&e->grad, ((size_t)e->P + GT_COUNT) * 4) &&
-              alloc((void**)&e->dbl, (S_COUNT + LS_COUNT + 4) * sizeof(double)) && alloc((void**)&e->od, sizeof(OptDev)) &&
+              alloc((void**)&e->dbl, DBL_COUNT * sizeof(double)) && alloc((void**)&e->od, sizeof(OptDev)) &&
               alloc((void**)&e->hist, (size_t)e->cap * sizeof(gpe_scalars)) && alloc((void**)&e->last, sizeof(gpe_scalars)) &&
               alloc((void**)&e->orth_dev, 8 * sizeof(float*));
     if (ok && sw.update_multi) ok = alloc((void**)&e->upd_snap, sizeof(UpdSnap));
@@ -1739,11 +1360,11 @@ size_t gpe_sizeof_scalars(void) { return sizeof(gpe_scalars); }
 size_t gpe_sizeof_observables(void) { return sizeof(struct gpe_observables); }
 size_t gpe_sizeof_mixture_observables(void) { return sizeof(struct gpe_mixture_observables); }
 size_t gpe_sizeof_sampler_spec(void) { return sizeof(gpe_sampler_spec); }
-int64_t gpe_exchange_dbl_count(void) { return S_COUNT + LS_COUNT + 4; }
+int64_t gpe_exchange_dbl_count(void) { return DBL_COUNT; }
 
 int gpe_use_external_exchange(gpe_engine* e, void* d_dbl, int64_t n_dbl, void* d_grad, int64_t n_grad) {
     if (!e || !d_dbl || !d_grad) return GPE_ERR_INVALID;
-    if (n_dbl < S_COUNT + LS_COUNT + 4 || n_grad < e->P + GT_COUNT) FAIL(e, GPE_ERR_INVALID, "external exchange buffers too small");
+    if (n_dbl < DBL_COUNT || n_grad < e->P + GT_COUNT) FAIL(e, GPE_ERR_INVALID, "external exchange buffers too small");
     HIPCHK(e, hipStreamSynchronize(e->stream));
     if (!e->ext_exchange) { (void)hipFree(e->dbl); (void)hipFree(e->grad); }
     e->dbl = (double*)d_dbl; e->grad = (float*)d_grad; e->ext_exchange = true;
@@ -1917,6 +1538,9 @@ int gpe_get_grad(gpe_engine* e, float* h, size_t n) {
     HIPCHK(e, hipStreamSynchronize(e->stream));
     return GPE_OK;
 }
+static int opt_state_read(gpe_engine* e, OptDev* h) { return record_copy(e, h, (const OptDev*)e->od, hipMemcpyDeviceToHost); }
+static int opt_state_write(gpe_engine* e, const OptDev& h) { return record_copy(e, e->od, &h, hipMemcpyHostToDevice); }
+static int last_record_read(gpe_engine* e, gpe_scalars* out) { return record_copy(e, out, (const gpe_scalars*)e->last, hipMemcpyDeviceToHost); }
 int gpe_get_adam_state(gpe_engine* e, float* hm, float* hv, size_t n, int64_t* step) {
     if (!e) return GPE_ERR_INVALID;
     if ((int64_t)n != e->P_user) FAIL(e, GPE_ERR_INVALID, "get_adam_state: size mismatch");
@@ -1924,8 +1548,7 @@ int gpe_get_adam_state(gpe_engine* e, float* hm, float* hv, size_t n, int64_t* s
     int rc;
     if (hm && (rc = flat_from_device(e, e->am, hm))) return rc;
     if (hv && (rc = flat_from_device(e, e->av, hv))) return rc;
-    HIPCHK(e, hipMemcpyAsync(&h, e->od, sizeof h, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
+    if ((rc = opt_state_read(e, &h))) return rc;
     if (step) *step = h.step;
     return GPE_OK;
 }
@@ -1933,16 +1556,13 @@ int gpe_set_adam_state(gpe_engine* e, const float* hm, const float* hv, size_t n
     if (!e || !hm || !hv) return GPE_ERR_INVALID;
     if ((int64_t)n != e->P_user) FAIL(e, GPE_ERR_INVALID, "set_adam_state: size mismatch");
     OptDev h;
-    HIPCHK(e, hipMemcpyAsync(&h, e->od, sizeof h, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
+    if (int rc = opt_state_read(e, &h)) return rc;
     h.step = step;
     h.b1p = pow((double)e->oc.beta1, (double)step); h.b2p = pow((double)e->oc.beta2, (double)step);
     int rc;
     if ((rc = flat_to_device(e, e->am, hm))) return rc;
     if ((rc = flat_to_device(e, e->av, hv))) return rc;
-    HIPCHK(e, hipMemcpyAsync(e->od, &h, sizeof h, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-    return GPE_OK;
+    return opt_state_write(e, h);
 }
 int gpe_reset_optimizer(gpe_engine* e, float lr) {
     if (!e) return GPE_ERR_INVALID;
@@ -1950,10 +1570,11 @@ int gpe_reset_optimizer(gpe_engine* e, float lr) {
     return reset_opt(e, lr);
 }
 
+static bool precomputed_base(const gpe_engine* e) { return e->cfg.base_mode >= 0 && e->cfg.base_kind == GPE_BASE_PRECOMPUTED; }
 // (re)build the collocation batch from what is bound; decides whether the boundary points ride in it
 // a precomputed base lives on the bound points: a monitor on them (the only one allowed then) does not outlive a new bind
 static void monitor_drop_if_on_bound_points(gpe_engine* e) {
-    if (e->mon.bound() && e->cfg.base_mode >= 0 && e->cfg.base_kind == GPE_BASE_PRECOMPUTED) monitor_free(e);
+    if (e->mon.bound() && precomputed_base(e)) monitor_free(e);
 }
 
 static int rebuild_main(gpe_engine* e) {
@@ -1970,7 +1591,6 @@ static int rebuild_main(gpe_engine* e) {
     return GPE_OK;
 }
 
-static bool precomputed_base(const gpe_engine* e);
 static void weights_clear(gpe_engine* e) { e->wq = nullptr; e->wq_local = 0.0; e->wq_total = 0.0; }      // (callers run fill_phys)
 static int orth_resize(gpe_engine* e);
 static int orth_refill(gpe_engine* e);
@@ -2122,7 +1742,7 @@ static int weights_total(gpe_engine* e, const float* d_q, int64_t n, double* tot
 
 // 1. what the engine's own state rules out; nothing is touched
 static int sampler_refuse_state(gpe_engine* e, const char* who, bool adaptive) {
-    if (adaptive && e->comm) FAIL(e, GPE_ERR_STATE, "%s: the engine has a communicator, and a data-parallel allocation needs a mass exchange", who);
+    if (adaptive && e->dp.on()) FAIL(e, GPE_ERR_STATE, "%s: the engine has a communicator, and a data-parallel allocation needs a mass exchange", who);
     if (e->cfg.potential == GPE_POT_PRECOMPUTED) FAIL(e, GPE_ERR_INVALID, "%s: a precomputed potential lives on fixed points", who);
     if (precomputed_base(e)) FAIL(e, GPE_ERR_INVALID, "%s: a precomputed base lives on fixed points", who);
     for (int k = 0; k < GPE_MAX_ORTH; ++k)       // (a frozen state is re-evaluated behind every redraw: only caller arrays are refused)
@@ -2597,7 +2217,6 @@ static int obs_ensure(gpe_engine* e) {
     if ((rc = dev_alloc(e, (Batch*)nullptr, &e->obs_buf, (size_t)2 * OBS_MAX_WG * e->obs_kind->row + e->obs_kind->row))) return rc;
     return dev_alloc(e, (Batch*)nullptr, &e->obs_out, (size_t)e->obs_kind->rec_doubles);
 }
-static bool precomputed_base(const gpe_engine* e) { return e->cfg.base_mode >= 0 && e->cfg.base_kind == GPE_BASE_PRECOMPUTED; }
 // which points an observables call / a monitor may look at: any, unless something exists on the bound points only
 static int obs_check_points(gpe_engine* e, const char* who, const float* d_x, int64_t n, const float* d_V) {
     if (n <= 0) FAIL(e, GPE_ERR_INVALID, "%s: need n > 0 points", who);
@@ -2691,9 +2310,7 @@ static int keeper_reset(gpe_engine* e, KeepDev* kd) {
 }
 static int keeper_state(gpe_engine* e, const char* who, KeepDev* h) {      // synchronises
     if (!e->keep.armed()) FAIL(e, GPE_ERR_STATE, "%s: no keeper bound (gpe_bind_keeper)", who);
-    HIPCHK(e, hipMemcpyAsync(h, e->keep.dev, sizeof *h, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-    return GPE_OK;
+    return record_copy(e, h, (const KeepDev*)e->keep.dev, hipMemcpyDeviceToHost);
 }
 
 static void monitor_free(gpe_engine* e) {
@@ -2765,7 +2382,7 @@ static int keeper_bind(gpe_engine* e, int metric, double min_delta, int64_t pati
     if (!e->mon.bound()) FAIL(e, GPE_ERR_INVALID, "keeper: needs a bound monitor (gpe_bind_monitor): it judges the monitor's records");
     if (!(min_delta >= 0.0) || !__builtin_isfinite(min_delta)) FAIL(e, GPE_ERR_INVALID, "keeper: min_delta must be finite and >= 0");
     if (patience < 0) FAIL(e, GPE_ERR_INVALID, "keeper: patience must be >= 0 (0: never stop)");
-    if (e->comm)
+    if (e->dp.on())
         FAIL(e, GPE_ERR_INVALID, "keeper: this engine has a communicator (gpe_comm_init): every rank's monitor sees its own points, so the ranks would keep "
                                  "and stop at different records; data-parallel keepers are not supported");
     HIPCHK(e, hipStreamSynchronize(e->stream));
@@ -2988,10 +2605,16 @@ static int launch_seed_pde(gpe_engine* e, float* d_resid, int want_seeds, int he
     return GPE_OK;
 }
 
+static int launch_head_sym(gpe_engine* e) {
+    hipLaunchKernelGGL(k_head_sym, dim3(cdiv(e->n_pde, 256)), dim3(256), 0, e->stream, e->ph, e->sym.O, e->sums(), e->n_pde, e->sym.ld);
+    if (hipGetLastError() != hipSuccess) FAIL(e, GPE_ERR_HIP, "k_head_sym launch failed");
+    return GPE_OK;
+}
+
 static int bc_fork(gpe_engine* e, bool with_backward);
 static int step_begin(gpe_engine* e, StepOpts o) {
     if (e->main.n <= 0) FAIL(e, GPE_ERR_STATE, "step before bind_points");
-    if (e->cfg.base_mode >= 0 && e->cfg.base_kind == GPE_BASE_PRECOMPUTED && !e->orth_host[4])
+    if (precomputed_base(e) && !e->orth_host[4])
         FAIL(e, GPE_ERR_STATE, "precomputed base requested but gpe_bind_base was not called");
     int rc;
     e->st = StepState{};
@@ -3004,11 +2627,7 @@ static int step_begin(gpe_engine* e, StepOpts o) {
     rc = mlp_forward(e, e->main, true, nullptr, slots);
     if (!rc && !slots) rc = launch_head_pde(e);
     if (!rc && e->cfg.w_sym != 0.f) {
-        if (!(rc = mlp_forward(e, e->sym, true))) {
-            hipLaunchKernelGGL(k_head_sym, dim3(cdiv(e->n_pde, 256)), dim3(256), 0, e->stream, e->ph, e->sym.O, e->sums(),
-                               e->n_pde, e->sym.ld);
-            if (hipGetLastError() != hipSuccess) { e->err = "k_head_sym launch failed"; rc = GPE_ERR_HIP; }
-        }
+        if (!(rc = mlp_forward(e, e->sym, true))) rc = launch_head_sym(e);
     }
     if (rc) return rc;
     e->st.phase = 1; e->st.head_slots = slots;
@@ -3083,20 +2702,22 @@ static void after_update(gpe_engine* e) {          // host-side mirror of what k
 }
 // the pre-training loss is and stays unweighted: its mean is over the point count whatever gpe_bind_weights published as W
 static Phys phys_counted(const gpe_engine* e) { Phys ph = e->ph; ph.n_global = counted_n_global(e); return ph; }
-static void launch_update(gpe_engine* e, const float* grad, const double* sums, const double* lsums, double bc_cnt, int do_update,
-                          int mse_mode, double* dbl_keep) {
-    const int n_pack = e->path == GPE_PATH_FUSED ? (e->nd.n_lin - 2) * e->H * e->H : 0;
+// The update launch and its tail (error check, after_update).  Forms: one workgroup; UPD_G workgroups behind k_update_part (upd_snap); UPD_G
+// workgroups on the snapshot the slab reduction left (k_grad_reduce_part, upd_snap_small), new weights scattered into the packed copies
+enum UpdForm { UPD_ONE, UPD_MULTI, UPD_PARTS };
+static UpdForm update_form(const gpe_engine* e) { return e->upd_snap ? UPD_MULTI : UPD_ONE; }
+static int launch_update(gpe_engine* e, UpdForm form, const float* grad, const double* sums, const double* lsums, double bc_cnt, int do_update,
+                         int mse_mode, double* dbl_keep) {
     const Phys ph = mse_mode ? phys_counted(e) : e->ph;
-    if (e->upd_snap) {
-        hipLaunchKernelGGL(k_update_part, dim3(UPD_G), dim3(1024), 0, e->stream, e->P, grad, sums, lsums, e->od, e->upd_snap);
-        hipLaunchKernelGGL(k_update<true>, dim3(UPD_G), dim3(1024), 0, e->stream, e->P, e->theta, e->am, e->av, grad, sums, lsums, ph,
-                           e->oc, e->od, e->hist, e->cap, e->last, bc_cnt, do_update, mse_mode, e->nd, e->H, e->Wpk, e->WpkT, n_pack, e->dbl,
-                           (int)(S_COUNT + LS_COUNT + 4), dbl_keep, (const UpdSnap*)e->upd_snap, 1);
-    } else {
-        hipLaunchKernelGGL(k_update<false>, dim3(1), dim3(1024), 0, e->stream, e->P, e->theta, e->am, e->av, grad, sums, lsums, ph,
-                           e->oc, e->od, e->hist, e->cap, e->last, bc_cnt, do_update, mse_mode, e->nd, e->H, e->Wpk, e->WpkT, n_pack, e->dbl,
-                           (int)(S_COUNT + LS_COUNT + 4), dbl_keep, (const UpdSnap*)nullptr, ((e->fwd_b6 || e->bwd_b6 || e->H > 64) ? 1 : 2) | (e->update_cache ? 0 : 5));
-    }
+    const UpdSnap* snap = form == UPD_ONE ? nullptr : (form == UPD_MULTI ? e->upd_snap : e->upd_snap_small);
+    const int pack_mode = form == UPD_ONE ? update_pack_mode(e) : (form == UPD_MULTI ? 1 : 2);
+    if (form == UPD_MULTI) hipLaunchKernelGGL(k_update_part, dim3(UPD_G), dim3(1024), 0, e->stream, e->P, grad, sums, lsums, e->od, e->upd_snap);
+    hipLaunchKernelGGL(form == UPD_ONE ? k_update<false> : k_update<true>, dim3(form == UPD_ONE ? 1 : UPD_G), dim3(1024), 0, e->stream, e->P, e->theta,
+                       e->am, e->av, grad, sums, lsums, ph, e->oc, e->od, e->hist, e->cap, e->last, bc_cnt, do_update, mse_mode, e->nd, e->H, e->Wpk,
+                       e->WpkT, pack_count(e), e->dbl, (int)DBL_COUNT, dbl_keep, snap, pack_mode);
+    HIPCHK(e, hipGetLastError());
+    after_update(e);
+    return GPE_OK;
 }
 static double bc_count(gpe_engine* e) {
     const int64_t nb = e->nb_merged > 0 ? e->nb_merged : e->bc.n;
@@ -3107,20 +2728,7 @@ static int step_update(gpe_engine* e) {
     if (e->st.phase != 2) FAIL(e, GPE_ERR_STATE, "step_update without step_backward");
     StepScope seq{e};               // the step ends here
     if (e->st.update_done) { after_update(e); return GPE_OK; }      // the slab reduction's last workgroup ran it
-    if (e->st.update_parts) {          // the slab reduction left partial norms + snapshot: the update on UPD_G workgroups, new weights scattered into the packed copies
-        const int n_pack = (e->nd.n_lin - 2) * e->H * e->H;
-        hipLaunchKernelGGL(k_update<true>, dim3(UPD_G), dim3(1024), 0, e->stream, e->P, e->theta, e->am, e->av, (const float*)e->grad,
-                           (const double*)e->sums(), (const double*)e->lsums(), e->ph, e->oc, e->od, e->hist, e->cap, e->last, bc_count(e), 1, 0,
-                           e->nd, e->H, e->Wpk, e->WpkT, n_pack, e->dbl, (int)(S_COUNT + LS_COUNT + 4), (double*)nullptr,
-                           (const UpdSnap*)e->upd_snap_small, 2);
-        HIPCHK(e, hipGetLastError());
-        after_update(e);
-        return GPE_OK;
-    }
-    launch_update(e, e->grad, e->sums(), e->lsums(), bc_count(e), 1, 0, nullptr);
-    HIPCHK(e, hipGetLastError());
-    after_update(e);
-    return GPE_OK;
+    return launch_update(e, e->st.update_parts ? UPD_PARTS : update_form(e), e->grad, e->sums(), e->lsums(), bc_count(e), 1, 0, nullptr);
 }
 int gpe_step_update(gpe_engine* e) { return e ? step_update(e) : GPE_ERR_INVALID; }
 
@@ -3156,10 +2764,7 @@ static int mse_finish(gpe_engine* e, int do_update) {
     if (e->st.phase != 3) FAIL(e, GPE_ERR_STATE, "mse update without mse begin");
     StepScope seq{e};
     // sums[S_DEN] must be non-zero for the (unused) Rayleigh quotient of the shared update kernel
-    launch_update(e, e->grad, e->sums(), e->lsums(), 0.0, do_update, 1, nullptr);
-    HIPCHK(e, hipGetLastError());
-    after_update(e);
-    return GPE_OK;
+    return launch_update(e, update_form(e), e->grad, e->sums(), e->lsums(), 0.0, do_update, 1, nullptr);
 }
 
 int gpe_mse_update(gpe_engine* e) { return e ? mse_finish(e, 1) : GPE_ERR_INVALID; }
@@ -3177,8 +2782,7 @@ int gpe_mse_loss_grad(gpe_engine* e, double* loss) {
     if ((rc = gpe_mse_begin(e))) return rc;
     if ((rc = mse_finish(e, 0))) return rc;
     gpe_scalars sc;
-    HIPCHK(e, hipMemcpyAsync(&sc, e->last, sizeof sc, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
+    if ((rc = last_record_read(e, &sc))) return rc;
     if (loss) *loss = sc.loss;
     return GPE_OK;
 }
@@ -3196,7 +2800,7 @@ int gpe_lbfgs_config(gpe_engine* e, double lr, int history, double tolerance_gra
     if (!(__builtin_isfinite(tolerance_grad) && tolerance_grad >= 0.0) || !(__builtin_isfinite(tolerance_change) && tolerance_change >= 0.0) ||
         !(__builtin_isfinite(stop_loss) && stop_loss >= 0.0))
         FAIL(e, GPE_ERR_INVALID, "lbfgs_config: tolerance_grad, tolerance_change and stop_loss must be finite and not negative");
-    if (e->cfg.world_size > 1 || e->comm) FAIL(e, GPE_ERR_INVALID, "lbfgs_config: a data-parallel engine has no L-BFGS (the history is per rank)");
+    if (e->cfg.world_size > 1 || e->dp.on()) FAIL(e, GPE_ERR_INVALID, "lbfgs_config: a data-parallel engine has no L-BFGS (the history is per rank)");
     if (!e->lb.st || e->lb.cfg.m != history) {
         HIPCHK(e, hipStreamSynchronize(e->stream));
         lbfgs_free_history(e);                        // the line search, gpe_lbfgs_monitor and their buffers do not depend on `history`
@@ -3220,17 +2824,14 @@ int gpe_lbfgs_config(gpe_engine* e, double lr, int history, double tolerance_gra
 // Refuses an engine without L-BFGS; h: the state as the work enqueued so far leaves it, on the host (every reader synchronises here)
 static int lbfgs_state(gpe_engine* e, const char* who, LbfgsDev* h = nullptr) {
     if (!e->lb.on) FAIL(e, GPE_ERR_STATE, "%s: L-BFGS is not configured (gpe_lbfgs_config)", who);
-    if (!h) return GPE_OK;
-    HIPCHK(e, hipMemcpyAsync(h, e->lb.st, sizeof *h, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-    return GPE_OK;
+    return h ? record_copy(e, h, (const LbfgsDev*)e->lb.st, hipMemcpyDeviceToHost) : GPE_OK;
 }
 
 static int lbfgs_refusals(gpe_engine* e, const char* who) {
     int rc;
     if ((rc = lbfgs_state(e, who))) return rc;
     if (e->smp.bound()) FAIL(e, GPE_ERR_STATE, "%s: a sampler with every > 0 is bound, the objective would change under the history", who);
-    if (e->comm) FAIL(e, GPE_ERR_STATE, "%s: the engine has a communicator, L-BFGS is single-rank", who);
+    if (e->dp.on()) FAIL(e, GPE_ERR_STATE, "%s: the engine has a communicator, L-BFGS is single-rank", who);
     return GPE_OK;
 }
 
@@ -3254,8 +2855,7 @@ int gpe_lbfgs_update(gpe_engine* e) {
     if (e->st.phase != 2 && e->st.phase != 3) FAIL(e, GPE_ERR_STATE, "lbfgs_update without step_backward or mse_begin");
     const int mse = e->st.phase == 3;
     StepScope seq{e};               // the step ends here
-    launch_update(e, e->grad, e->sums(), e->lsums(), mse ? 0.0 : bc_count(e), /*do_update=*/0, mse, nullptr);
-    HIPCHK(e, hipGetLastError());
+    if ((rc = launch_update(e, update_form(e), e->grad, e->sums(), e->lsums(), mse ? 0.0 : bc_count(e), /*do_update=*/0, mse, nullptr))) return rc;
     if (e->lb.ls.kind) {                                // one tick: the same five launches whatever the decision is
         hipLaunchKernelGGL(k_ls_dots, dim3(e->lb.n_part), dim3(64), 0, e->stream, e->P, e->lb.ld, (const float*)e->grad, (const float*)e->lb.h.d,
                            (const LbfgsDev*)e->lb.st, e->lb.ls_part);
@@ -3264,7 +2864,6 @@ int gpe_lbfgs_update(gpe_engine* e) {
         launch_lbfgs_iteration<true>(e);
     } else launch_lbfgs_iteration<false>(e);
     HIPCHK(e, hipGetLastError());
-    after_update(e);
     e->packed_dirty = e->path == GPE_PATH_FUSED;      // theta moved behind the record launch's repack: the next k_begin repacks
     return GPE_OK;
 }
@@ -3393,20 +2992,20 @@ int gpe_lbfgs_history(gpe_engine* e, float* h_S, float* h_Y, float* h_g_prev, fl
 // One process per GPU.  librccl is dlopen'ed here (the copy already mapped into the process -- PyTorch-ROCm's -- if there is one,
 // else ROCm's), so libgpe_hip.so has no link-time dependency on it and single-GPU users never load it.
 static int rccl_load(gpe_engine* e) {
-    if (e->rccl.dl) return GPE_OK;
+    if (e->dp.rccl.dl) return GPE_OK;
     const char* names[] = {"librccl.so", "librccl.so.1", "/opt/rocm/lib/librccl.so.1"};
     void* h = nullptr;
     for (const char* n : names) if ((h = dlopen(n, RTLD_NOW | RTLD_NOLOAD))) break;      // reuse a mapped copy
     if (!h) for (const char* n : names) if ((h = dlopen(n, RTLD_NOW | RTLD_LOCAL))) break;
     if (!h) FAIL(e, GPE_ERR_STATE, "librccl.so not found: %s", dlerror());
-    e->rccl.dl = h;
-    *(void**)&e->rccl.GetUniqueId = dlsym(h, "ncclGetUniqueId");
-    *(void**)&e->rccl.CommInitRank = dlsym(h, "ncclCommInitRank");
-    *(void**)&e->rccl.CommDestroy = dlsym(h, "ncclCommDestroy");
-    *(void**)&e->rccl.AllReduce = dlsym(h, "ncclAllReduce");
-    *(void**)&e->rccl.GetErrorString = dlsym(h, "ncclGetErrorString");
-    if (!e->rccl.GetUniqueId || !e->rccl.CommInitRank || !e->rccl.CommDestroy || !e->rccl.AllReduce || !e->rccl.GetErrorString) {
-        e->rccl.dl = nullptr;
+    e->dp.rccl.dl = h;
+    *(void**)&e->dp.rccl.GetUniqueId = dlsym(h, "ncclGetUniqueId");
+    *(void**)&e->dp.rccl.CommInitRank = dlsym(h, "ncclCommInitRank");
+    *(void**)&e->dp.rccl.CommDestroy = dlsym(h, "ncclCommDestroy");
+    *(void**)&e->dp.rccl.AllReduce = dlsym(h, "ncclAllReduce");
+    *(void**)&e->dp.rccl.GetErrorString = dlsym(h, "ncclGetErrorString");
+    if (!e->dp.rccl.GetUniqueId || !e->dp.rccl.CommInitRank || !e->dp.rccl.CommDestroy || !e->dp.rccl.AllReduce || !e->dp.rccl.GetErrorString) {
+        e->dp.rccl.dl = nullptr;
         FAIL(e, GPE_ERR_STATE, "librccl.so lacks a required symbol");
     }
     return GPE_OK;
@@ -3414,7 +3013,7 @@ static int rccl_load(gpe_engine* e) {
 #define RCCLCHK(e, call)                                                                                             \
     do {                                                                                                             \
         ncclResult_t _r = (call);                                                                                    \
-        if (_r != ncclSuccess) FAIL(e, GPE_ERR_HIP, "%s:%d: %s -> %s", __FILE__, __LINE__, #call, (e)->rccl.GetErrorString(_r)); \
+        if (_r != ncclSuccess) FAIL(e, GPE_ERR_HIP, "%s:%d: %s -> %s", __FILE__, __LINE__, #call, (e)->dp.rccl.GetErrorString(_r)); \
     } while (0)
 
 int gpe_comm_unique_id(gpe_engine* e, void* out128) {
@@ -3423,14 +3022,14 @@ int gpe_comm_unique_id(gpe_engine* e, void* out128) {
     if (rc) return rc;
     static_assert(sizeof(ncclUniqueId) == GPE_COMM_ID_BYTES, "ncclUniqueId size");
     ncclUniqueId id;
-    RCCLCHK(e, e->rccl.GetUniqueId(&id));
+    RCCLCHK(e, e->dp.rccl.GetUniqueId(&id));
     memcpy(out128, &id, sizeof id);
     return GPE_OK;
 }
 
 int gpe_comm_init(gpe_engine* e, const void* id128, int rank, int world) {
     if (!e || !id128 || world < 1 || rank < 0 || rank >= world) return GPE_ERR_INVALID;
-    if (e->comm) FAIL(e, GPE_ERR_STATE, "communicator already initialised");
+    if (e->dp.on()) FAIL(e, GPE_ERR_STATE, "communicator already initialised");
     if (e->smp.adaptive()) FAIL(e, GPE_ERR_STATE, "comm_init: an adaptive sampler is bound, and a data-parallel allocation needs a mass exchange");
     if (world != (e->cfg.world_size > 0 ? e->cfg.world_size : 1))
         FAIL(e, GPE_ERR_INVALID, "comm world %d != gpe_config.world_size %d", world, e->cfg.world_size);
@@ -3439,61 +3038,69 @@ int gpe_comm_init(gpe_engine* e, const void* id128, int rank, int world) {
     HIPCHK(e, hipSetDevice(e->device));
     ncclUniqueId id;
     memcpy(&id, id128, sizeof id);
-    RCCLCHK(e, e->rccl.CommInitRank(&e->comm, world, id, rank));
-    e->comm_rank = rank; e->comm_world = world;
-    e->dp_inline = env_on("GPE_DP_INLINE");
-    HIPCHK(e, hipStreamCreateWithFlags(&e->comm_stream, hipStreamNonBlocking));
-    HIPCHK(e, hipEventCreateWithFlags(&e->ev_x0, hipEventDisableTiming));
-    HIPCHK(e, hipEventCreateWithFlags(&e->ev_x1, hipEventDisableTiming));
-    e->ev_bucket.resize(e->nd.n_lin);
-    for (auto& ev : e->ev_bucket) HIPCHK(e, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    e->dp_collectives = 0;
+    RCCLCHK(e, e->dp.rccl.CommInitRank(&e->dp.comm, world, id, rank));
+    e->dp.rank = rank; e->dp.world = world;
+    e->dp.inline_sync = env_on("GPE_DP_INLINE");
+    HIPCHK(e, hipStreamCreateWithFlags(&e->dp.stream, hipStreamNonBlocking));
+    HIPCHK(e, hipEventCreateWithFlags(&e->dp.ev_x0, hipEventDisableTiming));
+    HIPCHK(e, hipEventCreateWithFlags(&e->dp.ev_x1, hipEventDisableTiming));
+    e->dp.ev_bucket.resize(e->nd.n_lin);
+    for (auto& ev : e->dp.ev_bucket) HIPCHK(e, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    e->dp.collectives = 0;
     return GPE_OK;
+}
+
+// what gpe_comm_set_async allocated
+static void dp_async_free(gpe_engine* e) {
+    for (auto& ev : e->dp.ev_g) { if (ev) (void)hipEventDestroy(ev); ev = nullptr; }
+    if (e->dp.grad_alt) { (void)hipFree(e->dp.grad_alt); e->dp.grad_alt = nullptr; }
+    if (e->dp.dbl_prev) { (void)hipFree(e->dp.dbl_prev); e->dp.dbl_prev = nullptr; }
+    e->dp.async_grad = false;
 }
 
 int gpe_comm_destroy(gpe_engine* e) {
     if (!e) return GPE_ERR_INVALID;
-    if (!e->comm) return GPE_OK;
+    if (!e->dp.on()) return GPE_OK;
     (void)hipStreamSynchronize(e->stream);
-    (void)hipStreamSynchronize(e->comm_stream);
-    (void)e->rccl.CommDestroy(e->comm);
-    e->comm = nullptr;
-    (void)hipStreamDestroy(e->comm_stream); e->comm_stream = nullptr;
-    (void)hipEventDestroy(e->ev_x0); (void)hipEventDestroy(e->ev_x1); e->ev_x0 = e->ev_x1 = nullptr;
-    for (hipEvent_t ev : e->ev_bucket) (void)hipEventDestroy(ev);
-    e->ev_bucket.clear();
-    for (auto& ev : e->ev_g) { if (ev) (void)hipEventDestroy(ev); ev = nullptr; }
-    if (e->grad_alt) { (void)hipFree(e->grad_alt); e->grad_alt = nullptr; }
-    if (e->dbl_prev) { (void)hipFree(e->dbl_prev); e->dbl_prev = nullptr; }
-    e->async_grad = false;
+    (void)hipStreamSynchronize(e->dp.stream);
+    (void)e->dp.rccl.CommDestroy(e->dp.comm);
+    e->dp.comm = nullptr;
+    (void)hipStreamDestroy(e->dp.stream); e->dp.stream = nullptr;
+    (void)hipEventDestroy(e->dp.ev_x0); (void)hipEventDestroy(e->dp.ev_x1); e->dp.ev_x0 = e->dp.ev_x1 = nullptr;
+    for (hipEvent_t ev : e->dp.ev_bucket) (void)hipEventDestroy(ev);
+    e->dp.ev_bucket.clear();
+    dp_async_free(e);
     return GPE_OK;
 }
 
 int gpe_comm_info(const gpe_engine* e, int* rank, int* world, int64_t* collectives) {
     if (!e) return GPE_ERR_INVALID;
-    if (rank) *rank = e->comm ? e->comm_rank : -1;
-    if (world) *world = e->comm ? e->comm_world : 0;
-    if (collectives) *collectives = e->dp_collectives;
+    if (rank) *rank = e->dp.on() ? e->dp.rank : -1;
+    if (world) *world = e->dp.on() ? e->dp.world : 0;
+    if (collectives) *collectives = e->dp.collectives;
     return GPE_OK;
 }
 
-// all-reduce(sum) buf in place on the exchange stream once everything enqueued on the compute stream so far has finished
-static int dp_allreduce_after(gpe_engine* e, void* buf, size_t count, ncclDataType_t dt, hipEvent_t ev) {
-    HIPCHK(e, hipEventRecord(ev, e->stream));
-    HIPCHK(e, hipStreamWaitEvent(e->comm_stream, ev, 0));
-    RCCLCHK(e, e->rccl.AllReduce(buf, buf, count, dt, ncclSum, e->comm, e->comm_stream));
-    e->dp_collectives++;
-    return GPE_OK;
-}
-static int dp_allreduce_inline(gpe_engine* e, void* buf, size_t count, ncclDataType_t dt) {     // ... on the compute stream itself
-    RCCLCHK(e, e->rccl.AllReduce(buf, buf, count, dt, ncclSum, e->comm, e->stream));
-    e->dp_collectives++;
+// all-reduce(sum) buf in place.  behind == NULL: on the compute stream itself; an event: on the exchange stream, once everything enqueued
+// on the compute stream so far has finished (the event is recorded there)
+static int dp_allreduce(gpe_engine* e, void* buf, size_t count, ncclDataType_t dt, hipEvent_t behind) {
+    if (behind) {
+        HIPCHK(e, hipEventRecord(behind, e->stream));
+        HIPCHK(e, hipStreamWaitEvent(e->dp.stream, behind, 0));
+    }
+    RCCLCHK(e, e->dp.rccl.AllReduce(buf, buf, count, dt, ncclSum, e->dp.comm, behind ? e->dp.stream : e->stream));
+    e->dp.collectives++;
     return GPE_OK;
 }
 static int dp_join(gpe_engine* e) {       // the compute stream continues after everything on the exchange stream
-    HIPCHK(e, hipEventRecord(e->ev_x1, e->comm_stream));
-    HIPCHK(e, hipStreamWaitEvent(e->stream, e->ev_x1, 0));
+    HIPCHK(e, hipEventRecord(e->dp.ev_x1, e->dp.stream));
+    HIPCHK(e, hipStreamWaitEvent(e->stream, e->dp.ev_x1, 0));
     return GPE_OK;
+}
+// the exchange of the step sums between the passes: the reverse pass reads the global ones
+static int dp_exchange_sums(gpe_engine* e, bool inl) {
+    int rc = dp_allreduce(e, e->sums(), S_COUNT, ncclDouble, inl ? nullptr : e->dp.ev_x0);
+    return rc || inl ? rc : dp_join(e);
 }
 
 // First phase of an engine-driven data-parallel step: as in gpe_step nobody reads the step sums between the passes, so the forward
@@ -3518,8 +3125,8 @@ static int dp_begin(gpe_engine* e) {
 // the scalars of step t-1.  Step 0 applies nothing.  Records (gpe_read_scalars, history) therefore lag one step.
 static int step_dp_async(gpe_engine* e) {
     int rc;
-    const int cur = (int)(e->async_t & 1), prv = cur ^ 1;
-    float* gcur = (e->async_t & 1) ? e->grad_alt : e->grad;       // the two gradient buffers alternate
+    const int cur = (int)(e->dp.async_t & 1), prv = cur ^ 1;
+    float* gcur = (e->dp.async_t & 1) ? e->dp.grad_alt : e->grad;       // the two gradient buffers alternate
     e->acc_clean = e->acc_clean && e->path == GPE_PATH_FUSED;
     StepScope seq{e};
     {
@@ -3527,48 +3134,42 @@ static int step_dp_async(gpe_engine* e) {
         // step's update has applied it
         Redirect to_cur(e, e->stream, gcur, e->gslab);
         if ((rc = dp_begin(e))) return rc;
-        if ((rc = dp_allreduce_after(e, e->sums(), S_COUNT, ncclDouble, e->ev_x0))) return rc;
-        if ((rc = dp_join(e))) return rc;
+        if ((rc = dp_exchange_sums(e, /*inl=*/false))) return rc;
         if ((rc = step_backward(e, StepOpts{}))) return rc;
-        HIPCHK(e, hipEventRecord(e->ev_x0, e->stream));
-        HIPCHK(e, hipStreamWaitEvent(e->comm_stream, e->ev_x0, 0));
-        RCCLCHK(e, e->rccl.AllReduce(gcur, gcur, (size_t)e->P + GT_COUNT, ncclFloat, ncclSum, e->comm, e->comm_stream));
-        e->dp_collectives++;
-        (void)hipEventRecord(e->ev_g[cur], e->comm_stream);
+        if ((rc = dp_allreduce(e, gcur, (size_t)e->P + GT_COUNT, ncclFloat, e->dp.ev_x0))) return rc;
+        (void)hipEventRecord(e->dp.ev_g[cur], e->dp.stream);
     }
-    float* gprev = (prv == 1) ? e->grad_alt : e->grad;
-    const int apply = e->async_t > 0;
-    HIPCHK(e, hipStreamWaitEvent(e->stream, e->ev_g[apply ? prv : cur], 0));     // step 0 only records: it reads its own (reduced) tail
-    launch_update(e, apply ? gprev : gcur, apply ? (const double*)e->dbl_prev : (const double*)e->sums(),
-                  apply ? (const double*)(e->dbl_prev + S_COUNT) : (const double*)e->lsums(), bc_count(e), apply, 0, e->dbl_prev);
-    HIPCHK(e, hipGetLastError());
-    after_update(e);
-    e->async_t++;
+    float* gprev = (prv == 1) ? e->dp.grad_alt : e->grad;
+    const int apply = e->dp.async_t > 0;
+    HIPCHK(e, hipStreamWaitEvent(e->stream, e->dp.ev_g[apply ? prv : cur], 0));     // step 0 only records: it reads its own (reduced) tail
+    if ((rc = launch_update(e, update_form(e), apply ? gprev : gcur, apply ? e->dp.dbl_prev : e->sums(), apply ? e->dp.dbl_prev + S_COUNT : e->lsums(),
+                            bc_count(e), apply, 0, e->dp.dbl_prev))) return rc;
+    e->dp.async_t++;
     return GPE_OK;
 }
 
 int gpe_comm_set_async(gpe_engine* e, int on) {
     if (!e) return GPE_ERR_INVALID;
-    if (!e->comm) FAIL(e, GPE_ERR_STATE, "gpe_comm_set_async before gpe_comm_init");
+    if (!e->dp.on()) FAIL(e, GPE_ERR_STATE, "gpe_comm_set_async before gpe_comm_init");
     HIPCHK(e, hipStreamSynchronize(e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->comm_stream));
-    if (on && !e->grad_alt) {
-        HIPCHK(e, hipMalloc((void**)&e->grad_alt, ((size_t)e->P + GT_COUNT) * sizeof(float) + 256));
-        HIPCHK(e, hipMalloc((void**)&e->dbl_prev, (S_COUNT + LS_COUNT + 4) * sizeof(double) + 256));
-        HIPCHK(e, hipMemset(e->grad_alt, 0, ((size_t)e->P + GT_COUNT) * sizeof(float)));
-        HIPCHK(e, hipMemset(e->dbl_prev, 0, (S_COUNT + LS_COUNT + 4) * sizeof(double)));
-        for (auto& ev : e->ev_g) HIPCHK(e, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    HIPCHK(e, hipStreamSynchronize(e->dp.stream));
+    if (on && !e->dp.grad_alt) {
+        HIPCHK(e, hipMalloc((void**)&e->dp.grad_alt, ((size_t)e->P + GT_COUNT) * sizeof(float) + 256));
+        HIPCHK(e, hipMalloc((void**)&e->dp.dbl_prev, DBL_COUNT * sizeof(double) + 256));
+        HIPCHK(e, hipMemset(e->dp.grad_alt, 0, ((size_t)e->P + GT_COUNT) * sizeof(float)));
+        HIPCHK(e, hipMemset(e->dp.dbl_prev, 0, DBL_COUNT * sizeof(double)));
+        for (auto& ev : e->dp.ev_g) HIPCHK(e, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     }
-    e->async_grad = on != 0;
-    e->async_t = 0;
+    e->dp.async_grad = on != 0;
+    e->dp.async_t = 0;
     return GPE_OK;
 }
 
 int gpe_step_dp(gpe_engine* e) {
     if (!e) return GPE_ERR_INVALID;
     if (e->smp.adaptive()) FAIL(e, GPE_ERR_STATE, "gpe_step_dp: the adaptive sampler is single-rank");
-    if (!e->comm) FAIL(e, GPE_ERR_STATE, "gpe_step_dp before gpe_comm_init");
-    if (e->async_grad) return step_dp_async(e);
+    if (!e->dp.on()) FAIL(e, GPE_ERR_STATE, "gpe_step_dp before gpe_comm_init");
+    if (e->dp.async()) return step_dp_async(e);
     int rc;
     StepScope seq{e};
     if ((rc = dp_begin(e))) return rc;
@@ -3579,15 +3180,13 @@ int gpe_step_dp(gpe_engine* e) {
     // costs several microseconds on this runtime: 4 hops were most of the 35-40 us a world-1 step lost against the plain step,
     // profiles/r04/dp_world1_*.json).  The exchange stream stays for what does overlap: the generic set's layer buckets and the
     // opt-in stale-gradient mode.  GPE_DP_INLINE=0 restores the two-stream form.
-    const bool inl = !bucketed && e->dp_inline;
-    if (inl) rc = dp_allreduce_inline(e, e->sums(), S_COUNT, ncclDouble);
-    else if (!(rc = dp_allreduce_after(e, e->sums(), S_COUNT, ncclDouble, e->ev_x0))) rc = dp_join(e);
-    if (rc) return rc;
+    const bool inl = !bucketed && e->dp.inline_sync;
+    if ((rc = dp_exchange_sums(e, inl))) return rc;
     if ((rc = step_backward(e, StepOpts{}, bucketed))) return rc;
-    if (bucketed) rc = dp_allreduce_after(e, e->grad + e->P, GT_COUNT, ncclFloat, e->ev_x0);      // exchange tail (sum r^2)
-    else if (inl) rc = dp_allreduce_inline(e, e->grad, (size_t)e->P + GT_COUNT, ncclFloat);
-    else rc = dp_allreduce_after(e, e->grad, (size_t)e->P + GT_COUNT, ncclFloat, e->ev_x0);
-    if (rc) return rc;
+    // the gradient message: whole, or -- the layers went bucket by bucket -- the exchange tail alone (sum r^2)
+    float* msg = bucketed ? e->grad + e->P : e->grad;
+    const size_t count = bucketed ? (size_t)GT_COUNT : (size_t)e->P + GT_COUNT;
+    if ((rc = dp_allreduce(e, msg, count, ncclFloat, inl ? nullptr : e->dp.ev_x0))) return rc;
     if (!inl && (rc = dp_join(e))) return rc;
     return step_update(e);
 }
@@ -3614,8 +3213,7 @@ int gpe_exchange_grad(gpe_engine* e, void** p, int64_t* count) {
 
 int gpe_read_scalars(gpe_engine* e, gpe_scalars* out) {
     if (!e || !out) return GPE_ERR_INVALID;
-    HIPCHK(e, hipMemcpyAsync(out, e->last, sizeof *out, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
+    if (int rc = last_record_read(e, out)) return rc;
     if (out->nonfinite != 0.0) FAIL(e, GPE_ERR_NONFINITE, "non-finite loss or gradient at step %lld; parameters not updated", (long long)out->step + 1);
     return GPE_OK;
 }
@@ -3710,65 +3308,60 @@ static int graph_build(gpe_engine* e) {
     return GPE_OK;
 }
 
+// one replay: graph_steps whole steps in one launch.  The redraw a replay may start with is enqueued here, outside the graph
+static int graph_replay(gpe_engine* e) {
+    if (e->smp.bound()) {
+        int rc = sampler_before_step(e, /*capturing=*/false);
+        if (rc) return rc;
+        e->smp.steps += e->graph_steps;
+    }
+    HIPCHK(e, hipGraphLaunch(e->graph_exec, e->stream));
+    after_update(e);
+    e->st = StepState{};
+    return monitor_after_steps(e, e->graph_steps);
+}
+// true: gpe_run may replay -- the run is eligible and a graph of the engine as it stands exists (built here when the key changed; a build
+// that fails falls back to plain launches for good)
+static bool graph_ready(gpe_engine* e, int64_t n_steps) {
+    if (!(e->use_graph && !e->prof && n_steps >= e->graph_steps && e->main.n > 0 && (e->graph_forced || e->main.n <= e->graph_max_points))) return false;
+    if ((!e->graph_exec || e->graph_key != graph_key_of(e)) && graph_build(e) != GPE_OK) { graph_drop(e); e->use_graph = false; }
+    return e->graph_exec != nullptr;
+}
+
 int gpe_run(gpe_engine* e, int64_t n_steps) {
     if (!e) return GPE_ERR_INVALID;
-    if (e->use_graph && !e->prof && n_steps >= e->graph_steps && e->main.n > 0 && (e->graph_forced || e->main.n <= e->graph_max_points)) {
-        if (!e->graph_exec || e->graph_key != graph_key_of(e)) {
-            if (graph_build(e) != GPE_OK) { graph_drop(e); e->use_graph = false; }     // fall back to plain launches for good
-        }
-        if (e->graph_exec) {
-            int64_t done = 0;
-            while (done + e->graph_steps <= n_steps) {
-                // a replay must not run past a monitor step, nor across a redraw of the sampler: up to there with plain launches when
-                // fewer than a graph's steps are left to it
-                int64_t room = e->mon.bound() ? e->mon.room() : e->graph_steps;
-                if (e->smp.bound()) room = std::min(room, e->smp.every - e->smp.steps % e->smp.every);
-                if (room >= e->graph_steps) {
-                    if (e->smp.bound()) {         // the redraw a replay may start with is enqueued here, outside the graph
-                        int rc = sampler_before_step(e, /*capturing=*/false);
-                        if (rc) return rc;
-                        e->smp.steps += e->graph_steps;
-                    }
-                    HIPCHK(e, hipGraphLaunch(e->graph_exec, e->stream));
-                    after_update(e);
-                    e->st = StepState{};
-                    done += e->graph_steps;
-                    int rc = monitor_after_steps(e, e->graph_steps);
-                    if (rc) return rc;
-                } else {
-                    for (int64_t i = 0; i < room && done < n_steps; ++i, ++done) {
-                        int rc = gpe_step(e, nullptr);
-                        if (rc) return rc;
-                    }
-                }
-            }
-            for (; done < n_steps; ++done) {          // remainder: plain launches
-                int rc = gpe_step(e, nullptr);
-                if (rc) return rc;
-            }
-            return GPE_OK;
-        }
-    }
-    for (int64_t i = 0; i < n_steps; ++i) {
-        int rc = gpe_step(e, nullptr);
+    const bool graph = graph_ready(e, n_steps);
+    for (int64_t done = 0; done < n_steps;) {
+        // a replay must not run past a monitor step, nor across a redraw of the sampler: up to there with plain launches when fewer than
+        // a graph's steps are left to it
+        int64_t room = e->mon.bound() ? e->mon.room() : e->graph_steps;
+        if (e->smp.bound()) room = std::min(room, e->smp.every - e->smp.steps % e->smp.every);
+        const bool replay = graph && n_steps - done >= e->graph_steps && room >= e->graph_steps;
+        const int rc = replay ? graph_replay(e) : gpe_step(e, nullptr);
         if (rc) return rc;
+        done += replay ? e->graph_steps : 1;
     }
     return GPE_OK;
 }
 
+// the opening of a forward-only detour on the bound set (gpe_residual, gpe_mixture_energy).  It clears the per-step record itself and
+// files nothing in it, so the caller's StepScope starts behind it
+static int detour_begin(gpe_engine* e, const char* who) {
+    if (e->main.n <= 0) FAIL(e, GPE_ERR_STATE, "%s before bind_points", who);
+    e->st = StepState{};                          // forward-only evaluation: k_head_pde forms the sums, never the slots of an earlier step
+    int rc = launch_begin(e, /*force=*/true);     // no reverse pass here: the gradient buffer must read zero
+    return rc ? rc : mlp_forward(e, e->main, false);
+}
+
 int gpe_residual(gpe_engine* e, gpe_scalars* out, float* d_psi, float* d_resid) {
     if (!e || !out) return GPE_ERR_INVALID;
-    if (e->main.n <= 0) FAIL(e, GPE_ERR_STATE, "residual before bind_points");
     int rc;
-    e->st = StepState{};                          // forward-only evaluation: k_head_pde forms the sums, never the slots of an earlier step
+    if ((rc = detour_begin(e, "residual"))) return rc;
     StepScope seq{e};
-    if ((rc = launch_begin(e, /*force=*/true))) return rc;      // no reverse pass here: the gradient buffer must read zero
-    if ((rc = mlp_forward(e, e->main, false))) return rc;
     if ((rc = launch_head_pde(e))) return rc;
     if (e->cfg.w_sym != 0.f) {
         if ((rc = mlp_forward(e, e->sym, false))) return rc;
-        hipLaunchKernelGGL(k_head_sym, dim3(cdiv(e->n_pde, 256)), dim3(256), 0, e->stream, e->ph, e->sym.O, e->sums(),
-                           e->n_pde, e->sym.ld);
+        if ((rc = launch_head_sym(e))) return rc;
     }
     if ((rc = launch_seed_pde(e, d_resid, 0, /*head_slots=*/0))) return rc;
     if ((rc = bc_fork(e, false))) return rc;
@@ -3776,12 +3369,8 @@ int gpe_residual(gpe_engine* e, gpe_scalars* out, float* d_psi, float* d_resid) 
     if (d_psi) hipLaunchKernelGGL(k_copy_psi, dim3(cdiv(e->n_pde, 256)), dim3(256), 0, e->stream, e->main.u, d_psi, e->n_pde,
                                   e->main.ld, e->nd.n_out);
     if ((rc = launch_tail(e, false))) return rc;
-    launch_update(e, e->grad, e->sums(), e->lsums(), bc_count(e), 0, 0, nullptr);
-    HIPCHK(e, hipGetLastError());
-    after_update(e);
-    HIPCHK(e, hipMemcpyAsync(out, e->last, sizeof *out, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-    return GPE_OK;
+    if ((rc = launch_update(e, update_form(e), e->grad, e->sums(), e->lsums(), bc_count(e), 0, 0, nullptr))) return rc;
+    return last_record_read(e, out);
 }
 
 int gpe_set_gamma(gpe_engine* e, float g) { if (!e) return GPE_ERR_INVALID; e->cfg.gamma = g; fill_phys(e); return GPE_OK; }
@@ -3795,8 +3384,7 @@ int gpe_mixture_scalars(gpe_engine* e, double out[8]) {
     if (!e || !out) return GPE_ERR_INVALID;
     if (!e->cfg.mixture) FAIL(e, GPE_ERR_STATE, "mixture_scalars: not a mixture engine (gpe_config.mixture)");
     OptDev h;
-    HIPCHK(e, hipMemcpyAsync(&h, e->od, sizeof h, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
+    if (int rc = opt_state_read(e, &h)) return rc;
     for (int k = 0; k < 8; ++k) out[k] = h.mix[k];
     return GPE_OK;
 }
@@ -3811,14 +3399,11 @@ int gpe_mixture_energy_weight(gpe_engine* e, float w_E) {
 int gpe_mixture_energy(gpe_engine* e, double out[8]) {
     if (!e || !out) return GPE_ERR_INVALID;
     if (!e->cfg.mixture) FAIL(e, GPE_ERR_STATE, "mixture_energy: not a mixture engine (gpe_config.mixture)");
-    if (e->main.n <= 0) FAIL(e, GPE_ERR_STATE, "mixture_energy before bind_points");
     int rc;
-    e->st = StepState{};
+    if ((rc = detour_begin(e, "mixture_energy"))) return rc;
     StepScope seq{e};
-    if ((rc = launch_begin(e, /*force=*/true))) return rc;
-    if ((rc = mlp_forward(e, e->main, false))) return rc;
     if ((rc = launch_head_pde(e, /*energy=*/true))) return rc;
-    if (e->comm && (rc = dp_allreduce_inline(e, e->sums(), S_COUNT, ncclDouble))) return rc;      // over all ranks: the first phase's exchange
+    if (e->dp.on() && (rc = dp_allreduce(e, e->sums(), S_COUNT, ncclDouble, nullptr))) return rc;      // over all ranks: the first phase's exchange
     double s[S_COUNT];
     HIPCHK(e, hipMemcpyAsync(s, e->sums(), sizeof s, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));
@@ -3854,12 +3439,9 @@ int gpe_set_n_global(gpe_engine* e, int64_t n) {
 int gpe_set_lr(gpe_engine* e, float lr) {
     if (!e) return GPE_ERR_INVALID;
     OptDev h;
-    HIPCHK(e, hipMemcpyAsync(&h, e->od, sizeof h, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
+    if (int rc = opt_state_read(e, &h)) return rc;
     h.lr = lr; h.lr0 = lr;
-    HIPCHK(e, hipMemcpyAsync(e->od, &h, sizeof h, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-    return GPE_OK;
+    return opt_state_write(e, h);
 }
 
 int gpe_profile_enable(gpe_engine* e, int on) {
@@ -3886,8 +3468,7 @@ int gpe_profile_read(gpe_engine* e, double out[4]) {
 int gpe_stop_state(gpe_engine* e, int* stopped, int64_t* stop_step) {
     if (!e) return GPE_ERR_INVALID;
     OptDev h;
-    HIPCHK(e, hipMemcpyAsync(&h, e->od, sizeof h, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
+    if (int rc = opt_state_read(e, &h)) return rc;
     if (stopped) *stopped = h.stopped;
     if (stop_step) *stop_step = h.stop_step;
     return GPE_OK;

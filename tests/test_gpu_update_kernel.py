@@ -1,4 +1,4 @@
-"""The update kernel alone (update_core in csrc/gpe_engine.hip: gradient-norm clipping, Adam in torch's op order, bias-correction powers,
+"""The update kernel alone (update_core in csrc/gpe_update.h: gradient-norm clipping, Adam in torch's op order, bias-correction powers,
 both schedulers, early stop, non-finite skip, history ring, packed-weight scatter) against the float64 reference oracle/update_ref.py,
 which tests/test_update_reference_cpu.py holds to torch's own optimiser and schedulers.
 
