@@ -14,6 +14,7 @@ GPE_MAX_LAYERS = 12
 GPE_MAX_ORTH = 4
 GPE_MAX_DIM = 3
 GPE_COMM_ID_BYTES = 128
+GPE_MAX_POT_TERMS = 16
 
 GPE_OK = 0
 GPE_ERR_INVALID, GPE_ERR_HIP, GPE_ERR_NONFINITE, GPE_ERR_STATE, GPE_ERR_NOMEM = -1, -2, -3, -4, -5
@@ -28,6 +29,7 @@ RIESZ_PAPER, RIESZ_SUM, RIESZ_VARIATIONAL = 0, 1, 2
 NET_MLP, NET_RESIDUAL = 0, 1
 LAMBDA_RAYLEIGH, LAMBDA_ENERGY = 0, 1
 KEEP_NONE, KEEP_RES_RMS, KEEP_ENERGY = 0, 1, 2
+TERM_QUAD, TERM_QUARTIC, TERM_GAUSS, TERM_LATTICE, TERM_LINEAR = 0, 1, 2, 3, 4
 
 
 class gpe_config(C.Structure):
@@ -93,6 +95,11 @@ class gpe_sampler_spec(C.Structure):
                 ("draw0", C.c_int64), ("every", C.c_int64)]
 
 
+class gpe_pot_term(C.Structure):
+    """include/gpe_hip.h: gpe_pot_term -- one analytic potential term (kind, a, w[3], c[3]); 32 bytes."""
+    _fields_ = [("kind", C.c_int32), ("a", C.c_float), ("w", C.c_float * 3), ("c", C.c_float * 3)]
+
+
 _vp, _i64, _int, _f = C.c_void_p, C.c_int64, C.c_int, C.c_float
 _P = C.POINTER
 
@@ -136,6 +143,10 @@ SYMBOLS = {
     "gpe_sampler_adaptive_blocks": (_int, [_vp, _P(_i64), _P(_i64)]),
     "gpe_sampler_cells": (_int, [_vp, _P(gpe_sampler_spec), _vp, _i64, _vp, _vp, _vp]),
     "gpe_sampler_cells_read": (_int, [_vp, _P(_vp), _P(_i64), _P(_i64)]),
+    "gpe_potential_terms": (_int, [_vp, _P(gpe_pot_term), C.c_int32]),
+    "gpe_potential_terms_read": (_int, [_vp, _P(gpe_pot_term), _P(C.c_int32)]),
+    "gpe_potential_values": (_int, [_vp, _P(_vp), _P(_i64)]),
+    "gpe_potential_eval": (_int, [_vp, _vp, _i64, _vp]),
     "gpe_bind_boundary": (_int, [_vp, _vp, _i64, _vp]),
     "gpe_bind_orth": (_int, [_vp, _int, _vp]),
     "gpe_bind_orth_state": (_int, [_vp, _int, _vp, C.c_size_t, _int, _f, _f]),

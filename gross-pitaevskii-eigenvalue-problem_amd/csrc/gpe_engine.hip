@@ -34,6 +34,7 @@ typedef enum { ncclFloat = 7, ncclDouble = 8 } ncclDataType_t;
 #include "gpe_observe_mix.h"
 #include "gpe_sampler.h"
 #include "gpe_sampler_plan.h"
+#include "gpe_potential.h"
 #include "gpe_generic.h"
 #include "gpe_fused.h"
 #include "gpe_wide_api.h"
@@ -269,6 +270,7 @@ struct gpe_engine {
     struct Monitor {
         Batch b;
         const float* x = nullptr; const float* V = nullptr;
+        float* Vown = nullptr;                        // [n]: V of the monitor's set as the bound potential terms give it (V points here), else NULL
         float dv = 0.f;
         int64_t n = 0, every = 0;                     // every == 0: no monitor
         int64_t steps = 0, records = 0;               // steps enqueued / records appended since the bind
@@ -319,6 +321,15 @@ struct gpe_engine {
     // per-point quadrature weights (gpe_bind_weights): every collocation sum takes q_i, every N of a mean becomes W (Phys::n_global)
     const float* wq = nullptr;                        // [n_pde]: the caller's array, or smp.q; NULL: unweighted
     double wq_local = 0.0, wq_total = 0.0;            // sum of this rank's weights / W over all ranks
+    // analytic potential terms (gpe_potential_terms, gpe_potential.h): the engine owns V of the sets it holds and fills it from the table
+    struct PotTerms {
+        PotTable tab = {};                            // the table, by value into k_potential_terms
+        int n = 0;                                    // terms bound; 0: none
+        float* V = nullptr; int64_t nV = 0;           // V of the bound collocation set; uV points here while that set runs on the engine's V
+        float* Vtmp = nullptr; int64_t nVtmp = 0;     // scratch of one-off observables on other points, grown on demand
+        bool on() const { return n > 0; }
+    } pot;
+    bool pot_bound() const { return pot.V && uV == pot.V && ux; }      // the bound set runs on the engine's V
     float mix_wE = 0.f;                               // mixture energy term (gpe_mixture_energy_weight): its weight, 0 = the plain mixture step
     // device-resident L-BFGS (gpe_lbfgs.h): every buffer allocated by gpe_lbfgs_config, freed with the engine
     struct Lbfgs {
@@ -1479,7 +1490,7 @@ void gpe_destroy(gpe_engine* e) {
     for (int k = 0; k < GPE_MAX_ORTH; ++k) orth_state_free(e->ost[k]);
     for (hipEvent_t ev : e->ev_pool) (void)hipEventDestroy(ev);
     if (e->ext_exchange) { e->grad = nullptr; e->dbl = nullptr; }
-    void* ps[] = {e->theta, e->am, e->av, e->grad, e->dbl, e->od, e->hist, e->last, (void*)e->orth_dev, e->Wpk, e->WpkT, e->gslab, e->gslab_bc, e->grad_bc, (void*)e->upd_snap, (void*)e->head_slots, (void*)e->upd_ticket, (void*)e->upd_snap_small, (void*)e->obs_buf, (void*)e->obs_out, (void*)e->smp.wq_red};
+    void* ps[] = {e->theta, e->am, e->av, e->grad, e->dbl, e->od, e->hist, e->last, (void*)e->orth_dev, e->Wpk, e->WpkT, e->gslab, e->gslab_bc, e->grad_bc, (void*)e->upd_snap, (void*)e->head_slots, (void*)e->upd_ticket, (void*)e->upd_snap_small, (void*)e->obs_buf, (void*)e->obs_out, (void*)e->smp.wq_red, (void*)e->pot.V, (void*)e->pot.Vtmp};
     for (void* p : ps) if (p) (void)hipFree(p);
     sampler_free(e);
     monitor_free(e);                              // (the keeper with it)
@@ -1591,6 +1602,30 @@ static int rebuild_main(gpe_engine* e) {
     return GPE_OK;
 }
 
+// ---- analytic potential terms: the engine-owned V (gpe_potential.h) ----
+// V[i] = V(x[i, :]) from the bound table, enqueued on the engine's stream; nothing synchronises.  Never recorded into a graph: the binds,
+// sampler_launch and gpe_potential_terms are its callers, and a capture does none of these.
+static int pot_fill(gpe_engine* e, const float* x, int64_t n, float* V) {
+    hipLaunchKernelGGL(k_potential_terms, dim3(cdiv(n, POT_THREADS)), dim3(POT_THREADS), 0, e->stream, e->pot.tab, e->pot.n, e->nd.dim, x, n, V);
+    HIPCHK(e, hipGetLastError());
+    return GPE_OK;
+}
+// room for n values in a buffer that nothing enqueued reads (the stream is idle: callers synchronise first); a buffer of the right
+// size stays where it is, so a re-bind of as many rows moves no pointer
+static int pot_reserve(gpe_engine* e, const char* who, float** buf, int64_t* have, int64_t n) {
+    if (*buf && *have == n) return GPE_OK;
+    float* p = nullptr;
+    if (hipMalloc((void**)&p, (size_t)n * sizeof(float) + 256) != hipSuccess) {
+        (void)hipGetLastError();
+        FAIL(e, GPE_ERR_NOMEM, "%s: no memory for the potential on %lld points", who, (long long)n);
+    }
+    if (*buf) (void)hipFree(*buf);
+    *buf = p; *have = n;
+    return GPE_OK;
+}
+// the engine's V takes the place of a caller's d_V on the precomputed-potential path
+static bool pot_serves(const gpe_engine* e) { return e->cfg.potential == GPE_POT_PRECOMPUTED && e->pot.on(); }
+
 static void weights_clear(gpe_engine* e) { e->wq = nullptr; e->wq_local = 0.0; e->wq_total = 0.0; }      // (callers run fill_phys)
 static int orth_resize(gpe_engine* e);
 static int orth_refill(gpe_engine* e);
@@ -1628,8 +1663,24 @@ static int bind_points_impl(gpe_engine* e, const float* d_x, int64_t n_local, co
 int gpe_bind_points(gpe_engine* e, const float* d_x, int64_t n_local, const float* d_V) {
     if (!e) return GPE_ERR_INVALID;
     if (!d_x || n_local <= 0) FAIL(e, GPE_ERR_INVALID, "bind_points: need n_local > 0 points");
-    if (e->cfg.potential == GPE_POT_PRECOMPUTED && !d_V) FAIL(e, GPE_ERR_INVALID, "precomputed potential requested but d_V is NULL");
+    if (pot_serves(e) && d_V) FAIL(e, GPE_ERR_INVALID, "bind_points: potential terms are bound, and the engine fills V itself (pass d_V = NULL, or clear the terms)");
+    if (e->cfg.potential == GPE_POT_PRECOMPUTED && !d_V && !pot_serves(e)) FAIL(e, GPE_ERR_INVALID, "precomputed potential requested but d_V is NULL");
     HIPCHK(e, hipStreamSynchronize(e->stream));
+    if (pot_serves(e)) {                         // V of the new set, filled before anything of the engine changes: a failure leaves it as it was
+        if (e->side) HIPCHK(e, hipStreamSynchronize(e->side));
+        const bool fresh = !(e->pot.V && e->pot.nV == n_local);      // (a buffer of the right size stays where it is)
+        float* nv = e->pot.V;
+        if (fresh && hipMalloc((void**)&nv, (size_t)n_local * sizeof(float) + 256) != hipSuccess) {
+            (void)hipGetLastError();
+            FAIL(e, GPE_ERR_NOMEM, "bind_points: no memory for the potential on %lld points", (long long)n_local);
+        }
+        if (int rc = pot_fill(e, d_x, n_local, nv)) { if (fresh) (void)hipFree(nv); return rc; }
+        if (fresh) {                             // the old buffer goes; uV / main.V, which may still name it, are set by the bind below, and nothing returns in between
+            if (e->pot.V) (void)hipFree(e->pot.V);
+            e->pot.V = nv; e->pot.nV = n_local;
+        }
+        d_V = e->pot.V;
+    }
     sampler_free(e);                             // the caller's points take over
     return bind_points_impl(e, d_x, n_local, d_V);
 }
@@ -1682,7 +1733,10 @@ static int sampler_launch(gpe_engine* e, int64_t draw, bool with_weights = false
     }
     HIPCHK(e, hipGetLastError());
     e->smp.held = draw;
-    return orth_refill(e);                       // frozen orthogonality states: psi_k of the new set, before the step's first kernel
+    // potential terms: V of the new set, behind the draw and before anything reads it -- orth_refill's forward passes do not, the step's
+    // head does, and the adaptive detour before the NEXT redraw runs on this set with this V
+    if (e->pot_bound()) { int rc = pot_fill(e, s.x, s.n, e->pot.V); if (rc) return rc; }
+    return orth_refill(e);                      // frozen orthogonality states: psi_k of the new set, before the step's first kernel
 }
 
 // The adaptive sampler's detour, enqueued directly before a redraw: the PDE residual of the current parameters on the set held now, with
@@ -1743,7 +1797,8 @@ static int weights_total(gpe_engine* e, const float* d_q, int64_t n, double* tot
 // 1. what the engine's own state rules out; nothing is touched
 static int sampler_refuse_state(gpe_engine* e, const char* who, bool adaptive) {
     if (adaptive && e->dp.on()) FAIL(e, GPE_ERR_STATE, "%s: the engine has a communicator, and a data-parallel allocation needs a mass exchange", who);
-    if (e->cfg.potential == GPE_POT_PRECOMPUTED) FAIL(e, GPE_ERR_INVALID, "%s: a precomputed potential lives on fixed points", who);
+    if (e->cfg.potential == GPE_POT_PRECOMPUTED && !e->pot.on())        // (with terms bound the engine refills its own V behind every draw)
+        FAIL(e, GPE_ERR_INVALID, "%s: a precomputed potential lives on fixed points", who);
     if (precomputed_base(e)) FAIL(e, GPE_ERR_INVALID, "%s: a precomputed base lives on fixed points", who);
     for (int k = 0; k < GPE_MAX_ORTH; ++k)       // (a frozen state is re-evaluated behind every redraw: only caller arrays are refused)
         if (e->orth_host[k] && !e->ost[k].on) FAIL(e, GPE_ERR_INVALID, "%s: orthogonality array %d is bound, and lives on fixed points", who, k);
@@ -1785,6 +1840,11 @@ static int sampler_acquire(gpe_engine* e, const char* who, const gpe_sampler_spe
     else sampler_free_parts(e);
     if (e->mse_target) { e->mse_target = nullptr; free_batch(e->mse); }      // a pre-training target lived on the points that just went
     s.cl.list = d_cells; s.cl.n = cl ? cl->n_cells : 0;
+    if (pot_serves(e)) {                         // potential terms: V of the set, beside the point buffer (kept where the row count stays; a failure from here on is
+                                                 // sampler_bind_failed's, which leaves nothing bound: uV never outlives a buffer this frees)
+        int rc = pot_reserve(e, who, &e->pot.V, &e->pot.nV, plan.n_rows);
+        if (rc) return rc;
+    }
     if (edges) {
         if (hipMalloc((void**)&s.edges, (size_t)plan.n_edges * sizeof(float) + 256) != hipSuccess ||
             hipMalloc((void**)&s.q, (size_t)plan.n_rows * sizeof(float) + 256) != hipSuccess) {
@@ -1842,7 +1902,7 @@ static int sampler_commit(gpe_engine* e, const char* who, const gpe_sampler_spec
     }
     s.n = plan.n_rows; s.first = sp->first_cell; s.every = sp->every; s.draw0 = sp->draw0; s.steps = 0;
     s.held = sp->draw0;
-    int rc = bind_points_impl(e, s.x, s.n, nullptr);                 // allocates the symmetry batch; its copy kernel reads a buffer ...
+    int rc = bind_points_impl(e, s.x, s.n, pot_serves(e) ? e->pot.V : nullptr);      // (V: filled by the launch below, behind the draw); allocates the symmetry batch; its copy kernel reads a buffer ...
     if (!rc) rc = sampler_launch(e, sp->draw0, /*with_weights=*/s.graded());      // ... this launch fills, together with [x ; -x]
     if (!rc && s.graded()) {                     // the cell volumes become the bound weights, W the whole grid's (or list's) volume
         double wl = 0.0, bad = 0.0;
@@ -1861,7 +1921,7 @@ static int sampler_bind_failed(gpe_engine* e, int rc) {
     const std::string keep = e->err;
     (void)hipStreamSynchronize(e->stream);
     sampler_free(e);
-    e->ux = nullptr; e->n_pde = 0; free_batch(e->main); free_batch(e->sym);
+    e->ux = nullptr; e->uV = nullptr; e->n_pde = 0; free_batch(e->main); free_batch(e->sym);
     fill_phys(e);
     e->err = keep;
     return rc;
@@ -1883,22 +1943,27 @@ static int sampler_bind(gpe_engine* e, const gpe_sampler_spec* sp, const float* 
     return GPE_OK;
 }
 
+// no points stay bound (the streams are idle): what clearing a sampler leaves, and clearing potential terms whose V the bound set ran on
+static int unbind_points(gpe_engine* e) {
+    monitor_drop_if_on_bound_points(e);
+    graph_drop(e);
+    sampler_free(e);                             // (a graded sampler's weights go with it)
+    e->ux = nullptr; e->uV = nullptr; e->n_pde = 0;
+    free_batch(e->main); free_batch(e->sym);
+    if (e->uxb && e->nb_user > 0) { int rc = setup_batch(e, e->bc, e->uxb, e->nb_user, 1, 0, false, nullptr); if (rc) return rc; }
+    e->nb_merged = 0;
+    e->acc_clean = false;
+    fill_phys(e);
+    return GPE_OK;
+}
+
 int gpe_bind_sampler(gpe_engine* e, const gpe_sampler_spec* sp) {
     if (!e) return GPE_ERR_INVALID;
     if (!sp) {                                   // clear: the buffer goes, so nothing stays bound
         HIPCHK(e, hipStreamSynchronize(e->stream));
         if (e->side) HIPCHK(e, hipStreamSynchronize(e->side));
         if (!e->smp.bound()) return GPE_OK;
-        monitor_drop_if_on_bound_points(e);
-        graph_drop(e);
-        sampler_free(e);                         // (a graded sampler's weights go with it)
-        e->ux = nullptr; e->uV = nullptr; e->n_pde = 0;
-        free_batch(e->main); free_batch(e->sym);
-        if (e->uxb && e->nb_user > 0) { int rc = setup_batch(e, e->bc, e->uxb, e->nb_user, 1, 0, false, nullptr); if (rc) return rc; }
-        e->nb_merged = 0;
-        e->acc_clean = false;
-        fill_phys(e);
-        return GPE_OK;
+        return unbind_points(e);
     }
     return sampler_bind(e, sp, nullptr);
 }
@@ -2225,7 +2290,8 @@ static int obs_check_points(gpe_engine* e, const char* who, const float* d_x, in
             FAIL(e, GPE_ERR_INVALID, "%s needs an analytic base on other points than the bound ones (the precomputed base exists on the bound points only)", who);
         if (!e->orth_host[4] || !e->orth_host[5] || !e->orth_host[6]) FAIL(e, GPE_ERR_STATE, "%s: precomputed base not bound (gpe_bind_base)", who);
     }
-    if (e->cfg.potential == GPE_POT_PRECOMPUTED && !d_V) FAIL(e, GPE_ERR_INVALID, "%s: precomputed potential requested but d_V is NULL", who);
+    if (e->cfg.potential == GPE_POT_PRECOMPUTED && !d_V && !e->pot.on())      // (with terms bound the engine evaluates V on the set itself)
+        FAIL(e, GPE_ERR_INVALID, "%s: precomputed potential requested but d_V is NULL", who);
     return GPE_OK;
 }
 // The chain of kind K (ObsScalar, ObsMix): the two reduction passes over the full jets b.O of the points x, and the record into *dst
@@ -2276,6 +2342,14 @@ static int observables_impl(gpe_engine* e, const char* who, const float* d_x, in
     int rc;
     if ((rc = obs_check_points(e, who, d_x, n, d_V))) return rc;
     if ((rc = obs_ensure(e))) return rc;
+    if (pot_serves(e) && !d_V) {                 // potential terms on a set the engine holds no V for: a scratch V, filled here
+        if (e->pot.nVtmp < n) {
+            HIPCHK(e, hipStreamSynchronize(e->stream));
+            if ((rc = pot_reserve(e, who, &e->pot.Vtmp, &e->pot.nVtmp, n))) return rc;
+        }
+        if ((rc = pot_fill(e, d_x, n, e->pot.Vtmp))) return rc;
+        d_V = e->pot.Vtmp;
+    }
     if ((rc = aux_forward(e, d_x, n, 1 + 2 * e->nd.dim, e->nd.dim))) return rc;       // full diagonal second derivatives, as gpe_forward_jets
     if ((rc = launch_observe(e, e->aux, d_x, n, d_V, dv, e->obs_out, q))) return rc;
     HIPCHK(e, hipMemcpyAsync(out, e->obs_out, (size_t)e->obs_kind->rec_doubles * sizeof(double), hipMemcpyDeviceToHost, e->stream));
@@ -2317,6 +2391,7 @@ static void monitor_free(gpe_engine* e) {
     keeper_free(e);                                   // its metric exists on the monitor's points only
     free_batch(e->mon.b);
     if (e->mon.ring) (void)hipFree(e->mon.ring);
+    if (e->mon.Vown) (void)hipFree(e->mon.Vown);
     e->mon = gpe_engine::Monitor();
 }
 
@@ -2339,16 +2414,33 @@ static int monitor_bind(gpe_engine* e, const float* d_x, int64_t n, const float*
             FAIL(e, GPE_ERR_NOMEM, "monitor: no memory for a ring of %d records", cap);
         }
     }
+    float* vown = nullptr;                                           // potential terms, no caller array: the engine's own V of this set
+    if (pot_serves(e) && !d_V) {
+        if (hipMalloc((void**)&vown, (size_t)n * sizeof(float) + 256) != hipSuccess) {
+            (void)hipGetLastError();
+            if (ring != mn.ring) (void)hipFree(ring);
+            FAIL(e, GPE_ERR_NOMEM, "monitor: no memory for the potential on %lld points", (long long)n);
+        }
+        if ((rc = pot_fill(e, d_x, n, vown))) {                      // filled here, before the monitor changes, and at every change of the terms
+            (void)hipFree(vown);
+            if (ring != mn.ring) (void)hipFree(ring);
+            return rc;
+        }
+        d_V = vown;
+    }
     Batch nb;
     if (mn.b.n == n && mn.b.O) std::swap(nb, mn.b);                 // same size: the batch is reused
     if ((rc = setup_batch(e, nb, d_x, n, 1 + 2 * e->nd.dim, e->nd.dim, false, d_V, /*with_store=*/false))) {
         free_batch(nb);
         if (ring != mn.ring) (void)hipFree(ring);
+        if (vown) (void)hipFree(vown);
         return rc;                                                   // (a reused batch cannot fail: nothing is allocated for it)
     }
     free_batch(mn.b);
     mn.b = nb;
     if (ring != mn.ring) { if (mn.ring) (void)hipFree(mn.ring); mn.ring = ring; mn.cap = cap; }
+    if (mn.Vown) (void)hipFree(mn.Vown);                             // (the stream is idle)
+    mn.Vown = vown;
     HIPCHK(e, hipMemsetAsync(mn.ring, 0, (size_t)cap * rec_bytes, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));
     mn.x = d_x; mn.V = d_V; mn.n = n; mn.dv = dv; mn.every = every;
@@ -2367,6 +2459,60 @@ int gpe_mixture_monitor(gpe_engine* e, const float* d_x, int64_t n, const float*
     if (!e) return GPE_ERR_INVALID;
     if (!e->cfg.mixture) return obs_wrong_kind(e, "mixture_monitor", "gpe_bind_monitor");
     return monitor_bind(e, d_x, n, d_V, dv, every, capacity);
+}
+
+// ---- analytic potential terms: the entry points (gpe_potential.h) -------------------------------------------------------------------------
+int gpe_potential_terms(gpe_engine* e, const gpe_pot_term* terms, int32_t n_terms) {
+    if (!e) return GPE_ERR_INVALID;
+    if (e->cfg.potential != GPE_POT_PRECOMPUTED)
+        FAIL(e, GPE_ERR_INVALID, "potential_terms: the engine's potential is not GPE_POT_PRECOMPUTED (the terms fill the array that path reads)");
+    if (!terms) {                                // clear
+        if (!e->pot.on()) return GPE_OK;
+        if (e->smp.bound()) FAIL(e, GPE_ERR_STATE, "potential_terms: a sampler is bound, and its sets take their potential from the terms (clear the sampler first)");
+        if (e->mon.Vown) FAIL(e, GPE_ERR_STATE, "potential_terms: the monitor's potential is evaluated from the terms (clear the monitor first)");
+        HIPCHK(e, hipStreamSynchronize(e->stream));
+        if (e->side) HIPCHK(e, hipStreamSynchronize(e->side));
+        const bool unbind = e->pot_bound();
+        e->pot.n = 0;
+        return unbind ? unbind_points(e) : GPE_OK;
+    }
+    std::string msg;
+    if (int rc = potential_terms_check(terms, n_terms, e->nd.dim, &msg)) { e->err = msg; return rc; }
+    e->pot.tab = PotTable{};
+    for (int j = 0; j < n_terms; ++j) e->pot.tab.t[j] = terms[j];
+    e->pot.n = n_terms;
+    // a live engine: the sets whose V the engine owns, in stream order -- no synchronisation, no pointer moves, a captured graph stays valid
+    int rc;
+    if (e->pot_bound() && (rc = pot_fill(e, e->ux, e->n_pde, e->pot.V))) return rc;
+    if (e->mon.Vown && (rc = pot_fill(e, e->mon.x, e->mon.n, e->mon.Vown))) return rc;
+    return GPE_OK;
+}
+
+int gpe_potential_terms_read(gpe_engine* e, gpe_pot_term* terms_out, int32_t* n_out) {
+    if (!e) return GPE_ERR_INVALID;
+    if (terms_out) for (int j = 0; j < e->pot.n; ++j) terms_out[j] = e->pot.tab.t[j];
+    if (n_out) *n_out = e->pot.n;
+    return GPE_OK;
+}
+
+int gpe_potential_values(gpe_engine* e, const float** d_V, int64_t* n) {
+    if (!e) return GPE_ERR_INVALID;
+    if (!e->pot.on()) FAIL(e, GPE_ERR_STATE, "potential_values: no potential terms bound (gpe_potential_terms)");
+    if (!e->ux || e->n_pde <= 0) FAIL(e, GPE_ERR_STATE, "potential_values: no points bound");
+    if (!e->pot_bound()) FAIL(e, GPE_ERR_STATE, "potential_values: the bound set runs on a caller's array (bound before the terms)");
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    if (d_V) *d_V = e->pot.V;
+    if (n) *n = e->n_pde;
+    return GPE_OK;
+}
+
+int gpe_potential_eval(gpe_engine* e, const float* d_x, int64_t n, float* d_V_out) {
+    if (!e) return GPE_ERR_INVALID;
+    if (!d_x || !d_V_out || n <= 0) FAIL(e, GPE_ERR_INVALID, "potential_eval: need n > 0 points and an output array");
+    if (!e->pot.on()) FAIL(e, GPE_ERR_STATE, "potential_eval: no potential terms bound (gpe_potential_terms)");
+    if (int rc = pot_fill(e, d_x, n, d_V_out)) return rc;
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    return GPE_OK;
 }
 
 // gpe_bind_keeper / gpe_mixture_keeper: the field judged is one of the engine's kind of record (ObsKind)

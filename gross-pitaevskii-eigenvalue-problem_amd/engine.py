@@ -399,6 +399,50 @@ class Engine:
         out = torch.as_tensor(view, device=f"cuda:{self.device}").clone()    # ... and the copy the caller keeps
         return out, int(d.value)
 
+    # ---- analytic potential terms (include/gpe_hip.h: gpe_potential_terms; gpe_pinn/potential.py) -----------------------------------------
+    def bind_potential_terms(self, terms):
+        """Bind a table of analytic potential terms (potential.quadratic / quartic / gaussian / lattice / linear; at most
+        potential.MAX_TERMS) on an engine configured with POT_PRECOMPUTED: the engine owns V from here on.  bind_points(x), the four
+        samplers, observables(x) and bind_monitor(x, every) then work without V -- the engine fills its own array at every bind and
+        behind every redraw.  On a live engine the sets the engine holds are refilled in stream order (no synchronisation; a captured
+        graph stays valid).  Data-parallel: every rank binds the same table.  Checkpoints do not store it: bind it again after a load."""
+        from . import potential
+        terms = [terms] if isinstance(terms, potential.Term) else list(terms)
+        arr = potential.to_c(terms)
+        self._chk(self.lib.gpe_potential_terms(self._h, arr, len(terms)))
+
+    def clear_potential_terms(self):
+        """Drop the table.  Refused (GPE_ERR_STATE) while a sampler is bound or the monitor runs on an engine-evaluated V; points bound
+        with the engine's V become unbound."""
+        on_engine_v = self.lib.gpe_potential_values(self._h, None, None) == capi.GPE_OK      # the engine's own answer: the bound set runs on its V
+        self._chk(self.lib.gpe_potential_terms(self._h, None, 0))
+        if on_engine_v:
+            self.n_local = 0
+            self._keep["x"] = None
+
+    def potential_terms(self) -> list:
+        """The bound table as a list of potential.Term ([]: none bound)."""
+        from . import potential
+        arr, n = (capi.gpe_pot_term * capi.GPE_MAX_POT_TERMS)(), C.c_int32()
+        self._chk(self.lib.gpe_potential_terms_read(self._h, arr, C.byref(n)))
+        return potential.from_c(arr, int(n.value))
+
+    def potential_values(self) -> torch.Tensor:
+        """Copy of the engine-owned V [n_local] the bound collocation set runs on; synchronises."""
+        p, n = C.c_void_p(), C.c_int64()
+        self._chk(self.lib.gpe_potential_values(self._h, C.byref(p), C.byref(n)))
+        view = _DeviceArrayView(p.value, (int(n.value),))
+        return torch.as_tensor(view, device=f"cuda:{self.device}").clone()
+
+    def potential_at(self, x) -> torch.Tensor:
+        """V of the bound terms on any points x [N, dim], by the kernel that fills the engine's own arrays; synchronises."""
+        x = self._to_dev(x, "x")
+        if x.dim() != 2 or x.shape[1] != self.cfg.dim:
+            raise ValueError(f"x must be [N,{self.cfg.dim}]")
+        out = torch.empty((x.shape[0],), dtype=torch.float32, device=x.device)
+        self._chk(self.lib.gpe_potential_eval(self._h, C.c_void_p(x.data_ptr()), x.shape[0], C.c_void_p(out.data_ptr())))
+        return out
+
     # ---- per-point quadrature weights (include/gpe_hip.h: gpe_bind_weights) ---------------------------------------------------------------
     def bind_weights(self, q, total=None):
         """One weight q_i >= 0 per bound collocation row: every collocation sum takes q_i and every N of a mean becomes W = sum q over

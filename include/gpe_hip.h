@@ -255,6 +255,7 @@ int gpe_reset_optimizer(gpe_engine* e, float lr);                    /* new Adam
 
 /* ---- data binding: X_tensor, boundary_points (refine/...:260-264) ----------------------------------- */
 /* d_x [n_local, dim] row-major fp32; d_V [n_local] or NULL (precomputed_potential, refine/...:146,175-178).
+ * GPE_POT_PRECOMPUTED needs d_V -- unless terms are bound (gpe_potential_terms): then d_V must be NULL and the engine fills its own V.
  * Buffers stay owned by the caller and must outlive their use. */
 int gpe_bind_points(gpe_engine* e, const float* d_x, int64_t n_local, const float* d_V);
 int gpe_bind_boundary(gpe_engine* e, const float* d_xb, int64_t n_b, const float* d_target /* [n_b,out] or NULL = 0 */);
@@ -303,8 +304,8 @@ size_t gpe_sizeof_sampler_spec(void);   /* sizeof(gpe_sampler_spec) */
 /* Allocates the engine-owned point buffer [n_local, dim], draws draw0 into it and binds it as the collocation batch with no potential
  * array (and the [x ; -x] symmetry batch when w_sym != 0, refreshed by every redraw).  Every step entry point honours the sampler:
  * gpe_step, gpe_run (which cuts its graph replays at redraw steps), gpe_step_dp, gpe_run_dp and the three-phase gpe_step_begin.
- * spec == NULL clears the sampler and leaves no points bound.  GPE_ERR_INVALID: GPE_POT_PRECOMPUTED or GPE_BASE_PRECOMPUTED (their arrays
- * would be stale), a caller's orthogonality array bound (frozen states of gpe_bind_orth_state are fine), every <= 0, hi <= lo or clip_hi < clip_lo on a used axis, first_cell + n_local beyond
+ * spec == NULL clears the sampler and leaves no points bound.  GPE_ERR_INVALID: GPE_POT_PRECOMPUTED without bound terms or GPE_BASE_PRECOMPUTED (their arrays
+ * would be stale; with gpe_potential_terms the engine owns V and refills it behind every draw), a caller's orthogonality array bound (frozen states of gpe_bind_orth_state are fine), every <= 0, hi <= lo or clip_hi < clip_lo on a used axis, first_cell + n_local beyond
  * the product of shape, axes used other than the network's input dimension.  While a sampler is bound gpe_bind_orth with an array,
  * gpe_bind_target and the gpe_mse_* entry points return GPE_ERR_STATE (their arrays live on fixed points); gpe_bind_points clears
  * the sampler and the caller's points take over.
@@ -427,13 +428,60 @@ int gpe_sampler_adaptive_blocks(gpe_engine* e, int64_t* n_blocks, int64_t* n_poi
  * Replaces: the corner cells of tools/accuracy_nd.py's box, which a radially trapped state leaves empty (--ball), and, for any problem
  * whose potential the engine evaluates itself, a host-side draw on a disk like the reference's prepare_training_data
  * (src/gross_pitaevskii_2D.py).  Not the 2D classes of gpe_pinn/surface.py themselves: their two-dimensional Gaussian potential is fed as
- * GPE_POT_PRECOMPUTED (GPE_POT_GAUSSIAN is the notebook's exp(-(x - a)^2) along x), which every sampler refuses. */
+ * GPE_POT_PRECOMPUTED (GPE_POT_GAUSSIAN is the notebook's exp(-(x - a)^2) along x), which a sampler takes once the well is bound as a
+ * GPE_TERM_GAUSS term (gpe_potential_terms) and refuses as a caller's array. */
 int gpe_sampler_cells(gpe_engine* e, const gpe_sampler_spec* spec, const int64_t* h_cells, int64_t n_cells,
                       const float* h_edges0, const float* h_edges1, const float* h_edges2);
 /* synchronise; the engine-owned DEVICE copy of the list, its length and this engine's first row in it.  Any out pointer may be NULL.
  * GPE_ERR_STATE: no cell-subset sampler bound.
  * Replaces: the caller keeping its own copy of the list it bound. */
 int gpe_sampler_cells_read(gpe_engine* e, const int64_t** d_cells, int64_t* n_cells, int64_t* first);
+
+/* ---- analytic potential terms: any trap on sampler-drawn sets -------------------------------------------------------------------------
+ * The engine evaluates three potentials inside its kernels (GPE_POT_HARMONIC / GAUSSIAN / PERIODIC); every other one is an array on fixed
+ * points (GPE_POT_PRECOMPUTED).  With a TABLE OF TERMS bound, an engine configured GPE_POT_PRECOMPUTED owns that array: one small kernel
+ * (csrc/gpe_potential.h: k_potential_terms) fills it on the engine's stream at every bind of points and directly behind every redraw of a
+ * sampler -- before the frozen orthogonality states are refilled and before the step's first kernel -- and the step runs on the
+ * precomputed-potential path every kernel family already has.  No forward, head, seed or reverse kernel knows of the table.
+ *   t_k = w_k (x_k - c_k) for k < dim;  s = sum_k t_k^2, accumulated as s = fmaf(t_k, t_k, s) in ascending k (the arithmetic of the
+ *   harmonic case: one QUAD term with a = pot_scale, w = omega, c = (pot_a, 0, 0) gives GPE_POT_HARMONIC's V bit for bit)
+ *   GPE_TERM_QUAD     a s                     anisotropic harmonic trap, any centre
+ *   GPE_TERM_QUARTIC  a s s                   quartic confinement (fast rotation)
+ *   GPE_TERM_GAUSS    a expf(-s)              d-dimensional bump, dimple or (a < 0) well
+ *   GPE_TERM_LATTICE  a sum_{k: w_k != 0} cosf(t_k)^2      optical lattice along the axes with w_k != 0
+ *   GPE_TERM_LINEAR   a sum_k t_k             tilt, gravity
+ *   V(x) = sum_j term_j(x), fp32, added in table order starting from 0.f.  gpe_pinn/potential.py restates it in numpy (fp64: the reference). */
+#define GPE_MAX_POT_TERMS 16
+enum { GPE_TERM_QUAD = 0, GPE_TERM_QUARTIC = 1, GPE_TERM_GAUSS = 2, GPE_TERM_LATTICE = 3, GPE_TERM_LINEAR = 4 };
+typedef struct gpe_pot_term {
+    int32_t kind;                 /* GPE_TERM_* */
+    float a;
+    float w[3], c[3];             /* axes beyond the network's input dimension: 0 */
+} gpe_pot_term;                   /* 32 bytes */
+/* Copies the table into the engine (n_terms in 1 .. GPE_MAX_POT_TERMS).  On a live engine V of the bound set -- where the engine owns it --
+ * and of a monitor set the engine evaluates are refilled, enqueued on the compute stream in stream order with no host synchronisation;
+ * the buffers stay where they are, so a captured step graph stays valid: only contents move.  A set bound earlier with a caller's d_V
+ * stays on that array.  With terms bound
+ *   gpe_bind_points      takes d_V == NULL: the engine allocates V [n_local], fills it and binds it; a d_V is GPE_ERR_INVALID
+ *   the four samplers    are accepted on a GPE_POT_PRECOMPUTED engine: V lives beside the point buffer and is refilled behind every draw
+ *                        (gpe_step, gpe_run and its graph cutting, gpe_step_begin, gpe_step_dp / gpe_run_dp on each rank's block; the
+ *                        adaptive sampler's residual detour runs on the held set, whose V is still the held set's)
+ *   gpe_observables, gpe_mixture_observables, gpe_bind_monitor, gpe_mixture_monitor      take d_V == NULL on any point set: the monitor
+ *                        gets an engine-owned V for its set, filled at its bind and at every change of the terms; a one-off call fills a scratch V
+ * terms == NULL clears the table: GPE_ERR_STATE while a sampler is bound or a monitor holds an engine-evaluated V; otherwise points bound
+ * with the engine's V become unbound, as gpe_bind_sampler(NULL) leaves them.  Data-parallel runs: every rank binds the same table, nothing
+ * is exchanged.  Checkpoints do not store the table.
+ * GPE_ERR_INVALID: the engine's potential is not GPE_POT_PRECOMPUTED, n_terms out of range, an unknown kind, a non-finite a / w / c, a
+ * non-zero w_k or c_k on an axis k >= dim, a LATTICE term with every w_k == 0.  A call that fails leaves the table that was there.
+ * Replaces: the host-side evaluate-and-upload of V per point set (no reference counterpart: it trains on one fixed grid). */
+int gpe_potential_terms(gpe_engine* e, const gpe_pot_term* terms, int32_t n_terms);
+/* the bound table: up to GPE_MAX_POT_TERMS records into terms_out (may be NULL), their count into *n_out (0: none bound) */
+int gpe_potential_terms_read(gpe_engine* e, gpe_pot_term* terms_out, int32_t* n_out);
+/* synchronise; the engine-owned V [n] the bound collocation set runs on.  GPE_ERR_STATE: no terms bound, no points bound, or the bound
+ * set runs on a caller's array. */
+int gpe_potential_values(gpe_engine* e, const float** d_V, int64_t* n);
+/* the fill kernel on any caller points: d_V_out[i] = V(d_x[i, :]), d_x [n, dim]; synchronises.  GPE_ERR_STATE: no terms bound. */
+int gpe_potential_eval(gpe_engine* e, const float* d_x, int64_t n, float* d_V_out);
 
 /* ---- forward-only entry points ---------------------------------------------------------------- */
 /* model.forward(x) (refine/...:121-125): d_out [n, out] row-major */
@@ -450,7 +498,7 @@ int gpe_eval_density(gpe_engine* e, const float* d_x, int64_t n, float dx, int a
 /* ---- observables of the current state, on the device (replaces tools/accuracy_cfg4.py:state_numbers; no reference counterpart) ------
  * gpe_observables: jets of the current parameters on d_x [n, dim] (the forward pass behind gpe_forward_jets, one allocation of that
  * size: n is not cut into chunks), two reduction passes, synchronise, fill *out.  d_x == NULL: the bound collocation points and their
- * bound potential (d_V, n ignored).  d_V [n]: needed exactly where gpe_bind_points needs it (GPE_POT_PRECOMPUTED).  A precomputed base
+ * bound potential (d_V, n ignored).  d_V [n]: needed exactly where gpe_bind_points needs it (GPE_POT_PRECOMPUTED; NULL with terms bound).  A precomputed base
  * exists on the bound points only: other point sets are refused with GPE_ERR_INVALID.  dv: quadrature weight. */
 int gpe_observables(gpe_engine* e, const float* d_x, int64_t n, const float* d_V, float dv, struct gpe_observables* out);
 /* Held-out monitor: after every `every`-th step enqueued since this call by gpe_step / gpe_run, the observables of the parameters

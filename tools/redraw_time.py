@@ -1,10 +1,12 @@
 #!/usr/bin/env python3
 """HIP-event time of a sampler's redraw launch, NS network (2,64,64,64,64,1), by difference on the engine's own stream:
-    redraw_time.py {uniform|cells} N_PER_AXIS [steps] [blocks]
+    redraw_time.py {uniform|cells|terms} N_PER_AXIS [steps] [blocks]
 Two engines on the same grid and seed, one with every = 1 (a redraw is enqueued before every step) and one that never redraws; blocks of
 `steps` steps of gpe_run are bracketed by a pair of events on the stream the engine enqueues on (torch's current stream), the two engines
 alternating, and the best block of each is kept.  (every = 1) - (no redraw), per step, is what one redraw adds to the stream: the kernel
-and its launch, as the step sees them.  uniform = gpe_bind_sampler; cells = gpe_sampler_cells on the full list of the same grid."""
+and its launch, as the step sees them.  uniform = gpe_bind_sampler; cells = gpe_sampler_cells on the full list of the same grid;
+terms = gpe_bind_sampler on an engine whose potential is a 4-term table (gpe_potential_terms: the redraw is the draw kernel plus the fill
+of the engine-owned V; both engines run the step on the precomputed-potential path)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -17,7 +19,12 @@ HALF, LAYERS = 6.0, [2, 64, 64, 64, 64, 1]
 
 
 def engine(every):
-    eng = gpe_pinn.Engine(gpe_pinn.GPEConfig(layers=LAYERS, gamma=100.0, dx=(2.0 * HALF / n) ** 2, lr=1e-3, w_bc=0.0))
+    kw = dict(potential=gpe_pinn.POT_PRECOMPUTED) if mode == "terms" else {}
+    eng = gpe_pinn.Engine(gpe_pinn.GPEConfig(layers=LAYERS, gamma=100.0, dx=(2.0 * HALF / n) ** 2, lr=1e-3, w_bc=0.0, **kw))
+    if mode == "terms":
+        P = gpe_pinn.potential
+        eng.bind_potential_terms([P.quadratic(0.5, (1.0, 1.4), (0.3, -0.2)), P.gaussian(-2.0, (1.2, 1.2), (-0.5, 0.4)), P.quartic(0.01, (1.0, 1.0)),
+                                  P.lattice(1.5, (2.0, 0.0))])
     torch.manual_seed(0)
     eng.set_params((torch.randn(len(eng.get_params())) * 0.1).numpy())
     g = dict(lo=(-HALF,) * 2, hi=(HALF,) * 2, shape=(n, n), every=every, seed=7)
